@@ -39,6 +39,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0        # MI355X spec (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
+DUMP_LIMIT_BYTES = 60 * 10**6    # --dump-outputs: the data of all arrays (64 MB with the .npy headers to spare)
+DUMP_SAMPLE_SEED = 20240607      # --dump-outputs: which parameter elements the sample holds
 
 
 def parse():
@@ -68,7 +70,39 @@ def parse():
                          "report config.tuned_gemms = false)")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="(unused: the CPU sample is fixed) kept for compatibility")
     ap.add_argument("--kernel-report", default="", help="write the per-kernel-shape table (json) here")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): the loss "
+                         "and a fixed seeded sample of the updated parameters and of their gradients "
+                         f"({DUMP_LIMIT_BYTES // 10**6} MB of data at most)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def step_outputs(model: nn.Module, loss: torch.Tensor, limit_bytes: int = DUMP_LIMIT_BYTES) -> dict:
+    """What a caller of the training step receives after it: the loss, and the updated parameters and their
+    gradients, each flattened in parameters() order into one vector.  When the two vectors do not fit the byte
+    limit, both are sampled at the same sorted element indices drawn from a fixed seed, so that the sample depends
+    only on the model's shapes."""
+    params = [p for p in model.parameters() if p.requires_grad]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    n, room = flat_p.numel(), (limit_bytes - 4) // (2 * 4)
+    if n > room:
+        gen = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+        idx = torch.randperm(n, generator=gen)[:room].sort().values.to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    return {"loss": loss.detach().float().reshape(1).cpu().numpy(),
+            "params": flat_p.float().cpu().numpy(),
+            "grads": flat_g.float().cpu().numpy()}
+
+
+def dump_outputs(arrays: dict, directory: str) -> None:
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(v, dtype=np.float32))
 
 
 class KernelTimer:
@@ -259,6 +293,10 @@ def main():
     def start_timers():
         timer.enabled = True
 
+    def keep_outputs(loss):                                  # before any untimed step changes the model again
+        if a.dump_outputs and rank == 0:
+            dump_outputs(step_outputs(model, loss), a.dump_outputs)
+
     if use_graph:
         # kernel timings (HIP events per launch) cannot live inside a captured graph: take them from two
         # eager steps first, then capture and time replays of the identical step.  (Under a process group these eager
@@ -275,10 +313,12 @@ def main():
         else:
             gstep, _ = ts.make_graphed_step(net, opt, (rgb, mx, label))
         elapsed, loss = ts.timed_steps(gstep, a.steps, a.warmup, dev)
+        keep_outputs(loss)
     else:
         # the timed region runs WITHOUT the per-launch HIP events (two events around each of ~270 scan launches per step
         # perturb what they measure); the kernel table comes from two extra eager steps afterwards
         elapsed, loss = ts.timed_steps(step, a.steps, a.warmup, dev)
+        keep_outputs(loss)
         eager_scan_steps = 2
         start_timers()
         step(); step(); torch.cuda.synchronize()
