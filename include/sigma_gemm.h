@@ -47,9 +47,12 @@ typedef struct sigma_gemm_params {
                               error; 3 = (hi, mid, lo), six MFMAs, ~1e-6 = the accuracy of an fp32 GEMM          */
     /* ABI 8: fused epilogue inputs and shared outputs (nt / nn only)                                            */
     int32_t c_mod;         /* > 0: problem z writes C + (z % c_mod) * strideC and the problems that share an output are
-                              SUMMED into it with fp32 atomics (the caller zero-fills C, or passes accumulate = 1):
-                              weight gradients of a stacked projection summed over the batch, e.g. d x_proj_weight =
-                              sum_b dp[b] xs[b]^T (vmamba.py:193-196 under autograd)                                */
+                              SUMMED into it: weight gradients of a stacked projection summed over the batch, e.g.
+                              d x_proj_weight = sum_b dp[b] xs[b]^T (vmamba.py:193-196 under autograd).  batch need not be
+                              a multiple of c_mod (the outputs z % c_mod >= batch % c_mod then sum one problem less);
+                              c_mod >= batch shares nothing and is the same as c_mod = 0.  With the scratch of `workspace`
+                              the sums are two-stage (C = or C += per `accumulate`, no zero fill); without it they are
+                              fp32 atomics into C (the caller zero-fills C, or passes accumulate = 1)                     */
     int32_t reserved;      /* 0 */
     const float *residual; /* (M, N) per problem, element (m, n) at residual[z * strideR + m * ldr + n], or NULL:
                               C = A B (+ bias) + residual (+ residual2) -- the residual stream of a block added in the
@@ -63,13 +66,15 @@ typedef struct sigma_gemm_params {
                               (m, n) at C[m * ldc + n - t_cols].  SS2D.in_proj (vmamba.py:1067-1071) thus hands its x half
                               to the depthwise convolution channel-major, with no transposing pass in between.
                               Needs t_cols % 32 == 0, M % 4 == 0, ldct % 4 == 0, 16-byte aligned Ct and C, N % 4 == 0,
-                              ldc % 4 == 0, batch <= 1, accumulate = 0, no residual                                       */
+                              ldc % 4 == 0, batch <= 1 (strideC is then ignored), accumulate = 0, no residual; anything
+                              else is refused with SIGMA_OPS_ERR_ARG                                                      */
     int64_t ldct;
     int32_t t_cols;
-    int32_t k_slices;      /* nn only: 1 = the reduction may be cut into slices run by different workgroups and summed
-                              into C with fp32 atomics, as tn does (the CALLER zero-fills C, or passes accumulate = 1):
+    int32_t k_slices;      /* nn only: 1 = the reduction may be cut into slices run by different workgroups, as tn does:
                               products with few output tiles and a long reduction, e.g. the weight gradient
-                              dW = dX^T X with dX held channel-major                                                       */
+                              dW = dX^T X with dX held channel-major.  The slices are summed in two stages through
+                              `workspace` (C = or C += per `accumulate`); without the scratch with fp32 atomics into C
+                              (the CALLER then zero-fills C, or passes accumulate = 1)                                    */
     void *workspace;       /* scratch for launches whose work items do not each own their output -- the reduction slices of
                               tn (and of nn with k_slices), the problems sharing an output under c_mod: with at least
                               sigma_gemm_workspace_bytes() bytes (16-byte aligned) every item stores its partial result

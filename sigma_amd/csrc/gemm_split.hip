@@ -673,7 +673,10 @@ gemm_split3_kernel(const GemmArgs g) {
 #endif
             ck += kBK;
             if (ck >= cit.kend) {                      // tile (slice) complete
-                if (g.mode != 2 && rows_ok) {
+                // a transposed column range ALWAYS takes the row epilogue (the direct one below knows no t_cols and would
+                // write all N columns into the (N - t_cols)-wide C); plan_nt admits t_cols only with the row epilogue's
+                // preconditions (N % 4, ldc % 4, aligned C, sC = 0 for the single problem, plain stores)
+                if (g.t_cols != 0 || (g.mode != 2 && rows_ok)) {
                     epilogue_rows(cit, g.mode == 1);
                     lds_barrier();                     // staging areas free before the next tile's operands are written
                 } else if (g.mode == 0) epilogue(cit, [](float* dst, float v) { *dst = v; });
@@ -770,7 +773,8 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 // (the 96 x 96 weight gradient of the decoder's last linear: 2304 vectors x 512 parts) still fills the chip.
 template <bool VEC>
 __global__ void __launch_bounds__(1024)
-reduce_parts_kernel(const float* __restrict__ ws, float* __restrict__ C, long M, int N, long ldc, long sC, int nparts, long part_stride, int add) {
+reduce_parts_kernel(const float* __restrict__ ws, float* __restrict__ C, long M, int N, long ldc, long sC, int nparts, int full_outs,
+                    int nparts_short, long part_stride, int add) {
     constexpr int W = VEC ? 4 : 1;
     typedef float vec_t __attribute__((ext_vector_type(W)));
     __shared__ vec_t red[16][64];
@@ -783,15 +787,16 @@ reduce_parts_kernel(const float* __restrict__ ws, float* __restrict__ C, long M,
     const long row = flat / N;
     const int col = (int)(flat - row * N);
     const float* __restrict__ src = ws + (long)c * nparts * part_stride + flat;
+    const int np = c < full_outs ? nparts : nparts_short;        // ragged c_mod groups: the last group lacks these outputs
     vec_t acc = {};
     if (on) {
         int p = y;
-        for (; p + PG < nparts; p += 2 * PG) {
+        for (; p + PG < np; p += 2 * PG) {
             const vec_t a0 = *reinterpret_cast<const vec_t*>(src + (long)p * part_stride);
             const vec_t a1 = *reinterpret_cast<const vec_t*>(src + (long)(p + PG) * part_stride);
             acc += a0 + a1;
         }
-        if (p < nparts) acc += *reinterpret_cast<const vec_t*>(src + (long)p * part_stride);
+        if (p < np) acc += *reinterpret_cast<const vec_t*>(src + (long)p * part_stride);
     }
     if (PG > 1) {
         red[y][threadIdx.x] = acc;
@@ -806,11 +811,14 @@ reduce_parts_kernel(const float* __restrict__ ws, float* __restrict__ C, long M,
     }
 }
 
+// problem groups of a shared-output launch, ceil(batch / c_mod): with batch % c_mod != 0 the last group is short and the
+// outputs z % c_mod >= batch % c_mod have one group (g.slices parts) less, whose slots in the scratch stay unwritten
+int groups(const GemmArgs& g, int batch) { return g.c_mod > 0 ? (batch + g.c_mod - 1) / g.c_mod : 1; }
+
 // bytes of scratch the two-stage sum of a launch needs (0: a single part per output -- no second stage)
 int64_t parts_bytes(const GemmArgs& g, int batch) {
-    const int per_out = g.slices * (g.c_mod > 0 ? batch / g.c_mod : 1);
+    const int per_out = g.slices * groups(g, batch);
     if (per_out <= 1) return 0;
-    if (g.c_mod > 0 && batch % g.c_mod != 0) return 0;          // ragged groups keep the atomic path
     const long outs = g.c_mod > 0 ? g.c_mod : batch;
     return (int64_t)outs * per_out * g.M * g.N * (int64_t)sizeof(float);
 }
@@ -830,7 +838,9 @@ hipError_t launch_summed(GemmArgs& g, int batch, int pieces, void* ws, int64_t w
     float* const C = g.C;
     const long ldc = g.ldc, sC = g.sC;
     const int outs = g.c_mod > 0 ? g.c_mod : batch;
-    g.nparts = g.slices * (g.c_mod > 0 ? batch / g.c_mod : 1);
+    g.nparts = g.slices * groups(g, batch);
+    const int rag = g.c_mod > 0 ? batch % g.c_mod : 0;
+    const int full_outs = rag ? rag : outs, nparts_short = rag ? g.nparts - g.slices : g.nparts;
     g.part_stride = g.M * g.N;
     g.C = static_cast<float*>(ws);
     g.ldc = g.N;
@@ -844,8 +854,10 @@ hipError_t launch_summed(GemmArgs& g, int batch, int pieces, void* ws, int64_t w
     int pg = 1;                                          // part groups per block: until ~2 waves per SIMD are in flight
     while (pg < 16 && 2 * pg <= g.nparts && blocks * outs * pg < 2048) pg *= 2;
     const dim3 grid((unsigned)blocks, (unsigned)outs), block(64, pg);
-    if (vec) hipLaunchKernelGGL(reduce_parts_kernel<true>, grid, block, 0, stream, (const float*)g.C, C, g.M, g.N, ldc, sC, g.nparts, g.part_stride, accumulate ? 1 : 0);
-    else hipLaunchKernelGGL(reduce_parts_kernel<false>, grid, block, 0, stream, (const float*)g.C, C, g.M, g.N, ldc, sC, g.nparts, g.part_stride, accumulate ? 1 : 0);
+    if (vec) hipLaunchKernelGGL(reduce_parts_kernel<true>, grid, block, 0, stream, (const float*)g.C, C, g.M, g.N, ldc, sC, g.nparts, full_outs, nparts_short,
+                                    g.part_stride, accumulate ? 1 : 0);
+    else hipLaunchKernelGGL(reduce_parts_kernel<false>, grid, block, 0, stream, (const float*)g.C, C, g.M, g.N, ldc, sC, g.nparts, full_outs, nparts_short,
+                                    g.part_stride, accumulate ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -859,7 +871,8 @@ int fill_common(const sigma_gemm_params* p, GemmArgs& g) {
     if (p->batch > 1 && (p->strideA % 4 != 0 || p->strideB % 4 != 0)) return SIGMA_OPS_ERR_ARG;
     g.A = p->A; g.B = p->Bt; g.C = p->C; g.bias = p->bias;
     g.lda = p->lda; g.ldb = p->ldb; g.ldc = p->ldc;
-    g.sA = p->strideA; g.sB = p->strideB; g.sC = p->strideC;
+    // a single problem never steps by strideC: ignored there, so that a stale value cannot unalign the row epilogue
+    g.sA = p->strideA; g.sB = p->strideB; g.sC = p->batch > 1 ? p->strideC : 0;
     g.slices = 1; g.a_mod = 0; g.c_mod = 0;
     g.mode = p->accumulate ? 1 : 0;
     g.R = p->residual; g.R2 = p->residual ? p->residual2 : nullptr; g.ldr = p->ldr; g.sR = p->strideR;
@@ -898,11 +911,12 @@ int plan_nt(const sigma_gemm_params* p, Planned& pl) {
     if (p->c_mod > 0 && pl.batch > p->c_mod) {       // several problems per output: summed
         if (p->residual || p->bias) return SIGMA_OPS_ERR_ARG;
         g.c_mod = p->c_mod; pl.summed = true;
-    } else if (p->c_mod > 0) g.c_mod = p->c_mod;
+    }   // batch <= c_mod: problem z owns output z (z % c_mod == z), i.e. the same as c_mod = 0 -- kept at 0 here, so that
+        // the scratch of k_slices is sized and reduced for the `batch` outputs that exist, not for c_mod of them
     if (p->t_cols != 0) {                                // transposed column range: row-contiguous epilogue, plain stores only
         if (p->t_cols < 0 || p->t_cols > p->N || p->t_cols % 32 != 0 || !p->Ct || !aligned16(p->Ct) || p->ldct % 4 != 0 ||
             p->ldct < p->M || p->M % 4 != 0 || p->N % 4 != 0 || p->ldc % 4 != 0 || !aligned16(p->C) || pl.batch != 1 ||
-            p->accumulate || p->residual || pl.summed || !SIGMA_GEMM_ROW_EPILOGUE)
+            p->accumulate || p->residual || pl.summed || !SIGMA_GEMM_ROW_EPILOGUE || (SIGMA_GEMM_ABL & 4))
             return SIGMA_OPS_ERR_ARG;
         g.Ct = p->Ct; g.ldct = p->ldct; g.t_cols = p->t_cols;
     }
@@ -926,7 +940,8 @@ int plan_nn(const sigma_gemm_params* p, Planned& pl) {
     if (p->c_mod > 0 && pl.batch > p->c_mod) {       // several problems per output: summed
         if (p->residual || p->bias) return SIGMA_OPS_ERR_ARG;
         g.c_mod = p->c_mod; pl.summed = true;
-    } else if (p->c_mod > 0) g.c_mod = p->c_mod;
+    }   // batch <= c_mod: problem z owns output z (z % c_mod == z), i.e. the same as c_mod = 0 -- kept at 0 here, so that
+        // the scratch of k_slices is sized and reduced for the `batch` outputs that exist, not for c_mod of them
     if (p->k_slices == 1 && !pl.summed && !p->residual && !p->bias && pl.batch == 1) {
         // few output tiles, long reduction: reduction slices, one round of resident workgroups (as tn)
         const int bn = pick_bn(g.N);

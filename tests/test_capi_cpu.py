@@ -191,3 +191,48 @@ def test_gemm_workspace_query_is_host_side_planning():
     assert q(params(19200, 1536, 384, 384, 384, 1536), 7) == -1
     bad = params(19200, 1536, 383, 384, 384, 1536)
     assert q(bad, 0) == -1
+
+
+def test_gemm_ragged_shared_outputs_and_transposed_range_are_planned_on_the_host():
+    """Two C-ABI answers decided before any launch: ragged shared outputs (batch % c_mod != 0) ask for scratch sized by
+    ceil(batch / c_mod) parts per output -- the query used to answer 0, "no scratch needed", and the launch then fell
+    back to atomics onto a C the caller had not zero-filled; c_mod >= batch changes nothing (every problem owns its
+    output): the sliced nn form of a single problem asks for the scratch of ONE output whatever c_mod says.  The t_cols
+    part pins the accepted contract (a single problem's strideC is not checked; what t_cols cannot take is refused, -1,
+    by the query as by the launch); that such a strideC no longer reaches the direct epilogue is a GPU matter
+    (tests/test_gemm_gpu.py::test_transposed_column_range_ignores_the_batch_stride_of_a_single_problem)."""
+    lib = _capi.load()
+
+    def params(M, N, K, lda, ldb, ldc, **kw):
+        p = _capi.GemmParams()
+        p.M, p.N, p.K, p.lda, p.ldb, p.ldc = M, N, K, lda, ldb, ldc
+        p.A, p.Bt, p.C = 0x10000, 0x20000, 0x30000          # never dereferenced by the query (16-byte aligned non-null)
+        p.batch, p.pieces = kw.pop("batch", 1), 2
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+    q = lambda p, form: int(lib.sigma_gemm_workspace_bytes(ctypes.byref(p), form))
+    M, N, K = 32, 192, 1200
+    for form in (0, 1):
+        for Z, cm in ((5, 2), (7, 3), (3, 2), (6, 4)):
+            p = params(M, N, K, K, K if form == 0 else N, N, batch=Z, c_mod=cm, strideA=M * K, strideB=N * K, strideC=M * N)
+            assert q(p, form) == cm * -(-Z // cm) * M * N * 4, (form, Z, cm)
+        # batch <= c_mod: every problem owns its output
+        assert q(params(M, N, K, K, K, N, batch=2, c_mod=2, strideA=M * K, strideB=N * K, strideC=M * N), form) == 0
+    # sliced nn, one problem: the scratch of its slices for one output, for any c_mod (c_mod >= batch = no sharing)
+    base = q(params(64, 64, 19200, 19200, 64, 64, k_slices=1), 1)
+    assert base > 0 and base % (64 * 64 * 4) == 0
+    for cm in (1, 2, 4):
+        assert q(params(64, 64, 19200, 19200, 64, 64, k_slices=1, c_mod=cm, strideC=64 * 64), 1) == base, cm
+    Ct = 0x40000
+    tc = params(64, 128, 32, 32, 32, 96, Ct=Ct, ldct=64, t_cols=32)
+    for sC in (0, 2, 3, 96):
+        tc.strideC = sC
+        assert q(tc, 0) == 0, sC
+    for field, value in (("batch", 2), ("t_cols", 48), ("ldct", 60), ("accumulate", 1), ("M", 66), ("ldc", 98)):
+        bad = params(64, 128, 32, 32, 32, 96, Ct=Ct, ldct=64, t_cols=32, strideC=2)
+        setattr(bad, field, value)
+        if field == "batch":
+            bad.strideA, bad.strideB = 64 * 32, 128 * 32
+        assert q(bad, 0) == -1, field

@@ -370,7 +370,7 @@ def test_sliced_reductions_sum_in_two_stages_without_a_zero_fill(shape):
 
 def test_shared_outputs_sum_in_two_stages():
     """bgemm_nt_sum (weight gradients of the stacked projections summed over the batch): overwrite into NaN, accumulate,
-    bit-identical repeats; a ragged problem count per output keeps the atomic path (zero-filled / accumulated C)"""
+    bit-identical repeats (ragged problem counts per output: test_ragged_shared_outputs_follow_the_workspace_contract)"""
     from sigma_amd import gemm
     B, d, c, L = 8, 192, 16, 1200
     dp, xs = _rand(2 * B, 2 * c, L, seed=51), _rand(2 * B, d, L, seed=52)
@@ -385,3 +385,108 @@ def test_shared_outputs_sum_in_two_stages():
     acc = torch.ones(2, 2 * c, d, device=DEV)
     gemm.bgemm_nt_sum(dp, xs, acc)
     _assert_close(acc, want + 1.0, bound + 1.0, "nt_sum accumulate")
+
+
+def _guarded(n, margin, fill=float("nan")):
+    """(buffer, view of n floats inside it): the margins on both sides (>= one row + 64 floats, multiples of 4 so that the
+    view stays 16-byte aligned) belong to the same allocation, so a store past either end of the view lands in memory the
+    test owns and is detected afterwards instead of faulting"""
+    assert margin % 4 == 0
+    buf = torch.full((n + 2 * margin,), fill, device=DEV)
+    return buf, buf[margin:margin + n]
+
+
+def _margins_intact(buf, n, margin):
+    torch.cuda.synchronize()
+    head, tail = buf[:margin], buf[margin + n:]
+    return bool(torch.isnan(head).all()) and bool(torch.isnan(tail).all())
+
+
+def _call(name, p, dev):
+    import ctypes
+    from sigma_amd import _capi
+    with torch.cuda.device(dev):
+        return int(getattr(_capi.load(), name)(ctypes.byref(p), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+
+
+def test_ragged_shared_outputs_follow_the_workspace_contract():
+    """c_mod with batch % c_mod != 0 (5 problems into 2 outputs: output 0 sums z = 0, 2, 4, output 1 sums z = 1, 3), called
+    exactly as include/sigma_gemm.h says: query the scratch, pass what it asks for, accumulate = 0, no zero fill (C holds
+    NaN).  The query used to answer 0 ("no scratch needed") for ragged groups and the launch then added fp32 atomics onto
+    the uninitialised C.  Same bound as the other nt cases; the guard bands around C stay NaN."""
+    import ctypes
+    from sigma_amd import _capi, gemm
+    Z, cm, M, N, K = 5, 2, 32, 192, 1200
+    a, b = _rand(Z, M, K, seed=61), _rand(Z, N, K, seed=62, scale=0.05)
+    margin = N + 64
+    buf, flat = _guarded(cm * M * N, margin)
+    c = flat.view(cm, M, N)
+    p = gemm._params(M, N, K, a, b, c, None, K, K, N, False, batch=Z, sA=M * K, sB=N * K, sC=M * N, c_mod=cm)
+    need = int(_capi.load().sigma_gemm_workspace_bytes(ctypes.byref(p), 0))
+    assert need > 0, "a shared-output launch must ask for the scratch of its two-stage sum"
+    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), need
+    gemm._selftest(a.device)
+    assert _call("sigma_gemm_nt_split3", p, a.device) == 0
+    prod = torch.matmul(a.double(), b.double().transpose(-1, -2))
+    absp = torch.matmul(a.double().abs(), b.double().abs().transpose(-1, -2))
+    want = torch.stack([prod[0::2].sum(0), prod[1::2].sum(0)])
+    bound = torch.stack([absp[0::2].sum(0), absp[1::2].sum(0)])
+    assert _margins_intact(buf, cm * M * N, margin), "ragged c_mod wrote outside C"
+    _assert_close(c, want, bound, "ragged c_mod")
+    # accumulate = 1 through the same scratch adds to what C holds
+    c.copy_(torch.ones_like(c))
+    p.accumulate = 1
+    assert _call("sigma_gemm_nt_split3", p, a.device) == 0
+    _assert_close(c, want + 1.0, bound + 1.0, "ragged c_mod accumulate")
+    assert _margins_intact(buf, cm * M * N, margin)
+
+
+def test_transposed_column_range_ignores_the_batch_stride_of_a_single_problem():
+    """t_cols = 32 with batch = 1 and strideC = 2: a single problem never steps by strideC, but a stride that was not a
+    multiple of 4 used to switch the kernel to its direct epilogue, which knows no t_cols -- it wrote all N columns into
+    the (N - t_cols)-wide C (past its end) and none into Ct.  Both outputs sit inside NaN guard bands."""
+    from sigma_amd import gemm
+    M, N, K, T = 64, 128, 32, 32
+    a, w = _rand(M, K, seed=71), _rand(N, K, seed=72)
+    mc, mt = (N - T) + 64, M + 64
+    cbuf, cflat = _guarded(M * (N - T), mc)
+    tbuf, tflat = _guarded(T * M, mt)
+    c, ct = cflat.view(M, N - T), tflat.view(T, M)
+    p = gemm._params(M, N, K, a, w, c, None, K, K, N - T, sC=2, out_t=ct, ldct=M, t_cols=T)
+    gemm._selftest(a.device)
+    assert _call("sigma_gemm_nt_split3", p, a.device) == 0
+    assert _margins_intact(cbuf, M * (N - T), mc), "C overrun"
+    assert _margins_intact(tbuf, T * M, mt), "Ct overrun"
+    want = a.double() @ w.double().t()
+    bound = _bound(a.double(), w.double().t())
+    _assert_close(ct.t(), want[:, :T], bound[:, :T], "transposed columns")
+    _assert_close(c, want[:, T:], bound[:, T:], "plain columns")
+
+
+@pytest.mark.parametrize("c_mod", [0, 2, 4])
+def test_sliced_nn_of_one_problem_ignores_a_larger_c_mod(c_mod):
+    """nn with k_slices, batch = 1 and c_mod >= 2 (legal: c_mod >= batch means no output is shared): the two-stage sum of
+    the slices must cover the one output that exists -- scratch sized for c_mod outputs made the reduce kernel write a
+    zero (or race with the real sum) for outputs no problem owns.  Called by the header's contract into a NaN guard band:
+    query, the scratch it asks for, accumulate = 0."""
+    import ctypes
+    from sigma_amd import _capi, gemm
+    M, N, K = 64, 64, 19200
+    a, b = _rand(M, K, seed=81), _rand(K, N, seed=82, scale=0.05)
+    margin = N + 64
+    buf, flat = _guarded(M * N, margin)
+    c = flat.view(M, N)
+    p = gemm._params(M, N, K, a, b, c, None, K, N, N, False, sC=M * N, c_mod=c_mod, k_slices=1)
+    need = int(_capi.load().sigma_gemm_workspace_bytes(ctypes.byref(p), 1))
+    assert need > 0 and need % (M * N * 4) == 0
+    ws = torch.full((need // 4,), float("nan"), device=DEV)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), need
+    gemm._selftest(a.device)
+    assert _call("sigma_gemm_nn_split3", p, a.device) == 0
+    assert _margins_intact(buf, M * N, margin), "sliced nn wrote outside C"
+    want = a.double() @ b.double()
+    _assert_close(c, want, _bound(a.double(), b.double()), f"sliced nn, c_mod {c_mod}")
+    first = c.clone()
+    assert _call("sigma_gemm_nn_split3", p, a.device) == 0
+    assert torch.equal(c, first)                                  # fixed summation order, no racing stores
