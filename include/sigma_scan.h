@@ -226,7 +226,10 @@ int sigma_scan_set_option(const char *name, int value);
 int sigma_scan_get_option(const char *name);
 
 /* Launch geometry the heuristic picks for a problem (for reports/tests): writes
- * {items_per_lane, rows_per_workgroup, workgroups, lds_bytes, tiles_per_workgroup, states_per_block} */
+ * {items_per_lane, rows_per_workgroup, workgroups, lds_bytes, tiles_per_workgroup, states_per_block}, or refuses the
+ * problem as the launch would.  The pointers in params may be NULL: the queries (these and the workspace queries) plan
+ * for 4-element aligned operands and strides, the launch for the operands it is given -- which may refuse misaligned
+ * ones (ckpt_pitch 16 / 160) or pick another kernel variant, never another workspace size. */
 int sigma_scan_fwd_plan(const sigma_scan_fwd_params *params, int32_t plan[6]);
 int sigma_scan_bwd_plan(const sigma_scan_bwd_params *params, int32_t plan[6]);
 

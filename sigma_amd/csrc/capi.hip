@@ -8,6 +8,8 @@
 #include "scan_device.h"
 #include "scan_launch.h"
 
+#include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
@@ -245,10 +247,8 @@ Plan plan_bwd(const sigma_scan_fwd_params* p, bool vec) {
         // measured (tools/scan_bench.py --sweep): with enough rows the largest workgroup wins (B/C
         // staging and the dB/dC column sums are per-workgroup costs); with few rows 8 rows per
         // workgroup beat both 3 (fixed costs dominate) and 12 (too few workgroups)
-        const long nwg = total_rows / R;
         const bool many = total_rows / maxw >= kCUs;
         const double cost = many ? (double)(maxw - R) : (R <= 8 ? (double)(8 - R) : 100.0 + R);
-        (void)nwg;
         if (cost < best) { best = cost; pl.rows = R; }
     }
     pl.grid = (int)(total_rows / pl.rows);
@@ -550,7 +550,8 @@ PlanR plan_rowlane(const sigma_scan_fwd_params* p, bool vec, bool backward) {
     return pl;
 }
 
-int64_t rowlane_summary_floats(const sigma_scan_fwd_params* p, int S) {
+// summaries of a sequence cut into S segments (row-lane and quad-row kernels): [(S-1)][batch][dim][N][2] floats
+int64_t summary_floats(const sigma_scan_fwd_params* p, int S) {
     return S > 1 ? (int64_t)(S - 1) * p->batch * p->dim * (int64_t)p->dstate * 2 : 0;
 }
 
@@ -563,21 +564,187 @@ int64_t rowlane_chain_floats(const sigma_scan_fwd_params* p) {
 
 // tiles per workgroup of the chained walk, or 0: used when the row blocks do not fill whole rounds of resident
 // workgroups (768 blocks on 512 slots = two rounds, the second half empty: 1.5 rounds' worth of work in the time of 2)
-int rowlane_chain_tiles(const sigma_scan_fwd_params* p, const PlanR& pr) {
+int rowlane_chain_tiles(const sigma_scan_fwd_params* p, int P, int S) {
     const int mode = g_opt_rl_chain.load();
     // measured (profiles/r04_rowlane_chain.txt): (16,3072,1200,N16) 800 us chained against 779 us in 1.5 plain rounds --
     // the kernel is bound by the issue rate of a SIMD, and the workgroups of a half-empty last round simply run faster;
     // the walk is kept for launches that are latency-bound per wave, on request only
-    if (mode != 2 || pr.S != 1) return 0;
-    const long nrb = (long)p->batch * p->n_groups * pr.P;
+    if (mode != 2 || S != 1) return 0;
+    const long nrb = (long)p->batch * p->n_groups * P;
     const int ntiles = (p->seqlen + 15) / 16;
     const long cap = (long)kCUs * sigma::bwdr_resident_per_cu(p->dstate);
     if (nrb <= cap || nrb * ntiles >= (1L << 31)) return 0;
-    const long rounds = (nrb + cap - 1) / cap;
-    (void)rounds;
     return (int)((nrb * ntiles + cap - 1) / cap);
 }
 
+bool vec_ok_bwd(const sigma_scan_bwd_params* q) {
+    const sigma_scan_fwd_params* p = &q->fwd;
+    const size_t al = 4 * (size_t)elem_size(p->io_dtype);
+    return vec_ok_fwd(p, false) && aligned_to(q->dout, al) && aligned_to(q->du, al) && aligned_to(q->ddelta, al) &&
+           q->dout_batch_stride % 4 == 0 && q->dout_d_stride % 4 == 0 && q->du_batch_stride % 4 == 0 &&
+           q->du_d_stride % 4 == 0 && q->ddelta_batch_stride % 4 == 0 && q->ddelta_d_stride % 4 == 0 &&
+           (p->rev_group_mask == 0 || p->seqlen % 4 == 0);
+}
+
+// ---------------------------------------------------------------- one plan per problem
+enum class Family { Fwd, Fwd4, Fwdr, Bwd, Bwd2, Bwd3, Bwd4, Bwdr };
+
+// Everything the plan query, the workspace query and the launch of one problem need, decided once by plan_forward /
+// plan_backward so that the three cannot disagree.
+struct ScanPlan {
+    int status = SIGMA_OK;                 // else the refusal (its message is in sigma_scan_last_error())
+    Family family = Family::Fwd;
+    std::array<int32_t, 6> report{};       // the answer of sigma_scan_{fwd,bwd}_plan
+    bool vec = true;                       // 4-element aligned operands
+    // geometry: FwdArgs R / W / NB, BwdArgs P / S / seg_tiles / RB / slab2 / flags, the launchers' T and glds
+    int items = 0, rows = 0, tiles = 1, nb = 0, P = 1, S = 1, seg_tiles = 0, RB = 0, slab2 = 0, flags = 0;
+    bool glds = false;
+    size_t lds = 0;
+    // workspace layout in floats: [dB partials][dC partials][segment summaries][hand-over area of the chained walk]
+    int64_t slab = 0, summ = 0, chain = 0;
+    int64_t workspace_bytes() const { return (2 * slab + summ + chain) * (int64_t)sizeof(float); }
+};
+
+int refuse_rowlane(bool launch) {
+    return launch ? fail(SIGMA_ERR_BAD_SHAPE, "ckpt_pitch 16 needs f32 IO, 16-byte aligned operands, dstate in {4,8,16}, seqlen %% 4 == 0 and rows per group divisible by 64")
+                  : fail(SIGMA_ERR_BAD_SHAPE, "ckpt_pitch 16 (row-lane kernels) is not available for this problem");
+}
+
+// launch = false: the queries.  They may see NULL operands, so they plan for 4-element aligned ones (no workspace
+// depends on alignment) and word their refusals for a planner.  launch = true: the operands' real alignment.
+ScanPlan plan_forward(const sigma_scan_fwd_params* p, bool launch) {
+    ScanPlan s;
+    s.vec = !launch || (vec_ok_fwd(p, true) && (p->rev_group_mask == 0 || p->seqlen % 4 == 0));
+    s.nb = p->dstate;
+    if (p->ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_16) {
+        const PlanR r = plan_rowlane(p, s.vec, false);
+        if (!r.ok) { s.status = refuse_rowlane(launch); return s; }
+        s.family = Family::Fwdr;
+        s.rows = r.NW; s.P = r.P; s.S = r.S; s.seg_tiles = r.seg_tiles;
+        s.lds = sigma::fwdr_lds_bytes(r.NW);
+        // items 16, rows slot = state waves, tiles slot = segments, states_per_block slot = -200
+        s.report = {16, r.NW, r.grid, (int32_t)s.lds, r.S, -200};
+    } else if (const PlanF4 f4 = plan_fwd4(p, s.vec); f4.ok) {
+        s.family = Family::Fwd4;
+        s.rows = f4.W; s.P = f4.P; s.lds = f4.lds;
+        // quad-row forward: items 10, rows slot = waves (4 rows each), states_per_block slot = -100
+        s.report = {10, f4.W, f4.grid, (int32_t)f4.lds, 1, -100};
+    } else {
+        const Plan pl = plan_fwd(p, s.vec);
+        s.family = Family::Fwd;
+        s.items = pl.items; s.rows = pl.rows; s.tiles = pl.tiles; s.nb = pl.nb; s.glds = pl.glds; s.lds = pl.lds;
+        s.report = {pl.items, pl.rows, pl.grid, (int32_t)pl.lds, pl.tiles, pl.nb};
+    }
+    if (s.lds > kLdsLimit) s.status = fail(SIGMA_ERR_BAD_SHAPE, "LDS budget exceeded (%zu B)", s.lds);
+    s.summ = summary_floats(p, s.S);
+    return s;
+}
+
+// The backward's kernel family by checkpoint pitch: 16 row-lane, 160 quad-row, 320 state-parallel or else second
+// generation, 640 second generation, 0 first generation (also where no second-generation plan fits).
+ScanPlan plan_backward(const sigma_scan_bwd_params* q, bool launch) {
+    const sigma_scan_fwd_params* p = &q->fwd;
+    const int N = p->dstate;
+    ScanPlan s;
+    s.vec = !launch || vec_ok_bwd(q);
+    s.nb = N;
+    if (p->ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_16) {
+        const PlanR r = plan_rowlane(p, s.vec, true);
+        if (!r.ok) { s.status = refuse_rowlane(launch); return s; }
+        s.family = Family::Bwdr;
+        s.rows = r.NW; s.P = r.P; s.S = r.S; s.seg_tiles = r.seg_tiles;
+        s.lds = sigma::bwdr_lds_bytes(4);
+        s.chain = rowlane_chain_floats(p);
+        s.report = {16, r.NW, r.grid, (int32_t)s.lds, r.S, -200};
+    } else if (p->ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_160) {
+        // B/C alignment is part of the plan: the caller chose the pitch at forward time with the same tensors
+        const Plan4 b4 = plan_bwd4(p, !launch || vec_ok_fwd(p, false));
+        if (!b4.ok) {
+            s.status = launch ? fail(SIGMA_ERR_BAD_SHAPE, "ckpt_pitch 160 needs f32 IO, 16-byte aligned B/C, dstate in {4,8,16} and rows per group divisible by 4")
+                              : fail(SIGMA_ERR_BAD_SHAPE, "ckpt_pitch 160 (quad-row backward) is not available for this problem");
+            return s;
+        }
+        s.family = Family::Bwd4;
+        s.rows = b4.W; s.nb = b4.nbuf; s.P = b4.P; s.S = b4.S; s.seg_tiles = b4.seg_tiles; s.RB = b4.RB; s.slab2 = b4.SB;
+        s.flags = b4.wgs == 2 ? 2 : 0;
+        s.lds = b4.lds;
+        // items = 10 (+ 1000 x sequence segments when the sequence is split), rows slot = waves (4 rows each),
+        // tiles slot = -(row blocks), states_per_block slot = -(100 + states per barrier)
+        s.report = {10 + (b4.S > 1 ? 1000 * b4.S : 0), b4.W, b4.grid, (int32_t)b4.lds, -b4.RB, -(100 + b4.SB)};
+    } else if (const Plan3 b3 = plan_bwd3(p, s.vec); b3.ok) {
+        s.family = Family::Bwd3;
+        s.items = 5; s.rows = b3.nw; s.P = b3.P; s.RB = b3.RB; s.glds = b3.glds; s.lds = b3.lds;
+        // states_per_block slot = -(waves per row) marks the state-parallel kernel
+        s.report = {5, b3.nw, b3.grid, (int32_t)b3.lds, -b3.RB, -(N / 4)};
+    } else if (const Plan2 b2 = plan_bwd2(p, s.vec); b2.ok) {
+        s.family = Family::Bwd2;
+        s.items = b2.items; s.rows = b2.rows; s.nb = b2.nb; s.P = b2.P; s.RB = b2.RB; s.slab2 = b2.slab2;
+        s.glds = b2.glds; s.lds = b2.lds;
+        // tiles_per_workgroup slot: -(row blocks per workgroup) marks the second-generation kernel
+        s.report = {b2.items, b2.rows, b2.grid, (int32_t)b2.lds, -b2.RB, b2.nb};
+    } else if (p->ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_320 && g_opt_bwd_gen.load() == 1) {
+        s.status = fail(SIGMA_ERR_BAD_OPTION, "ckpt_pitch 320 needs the second-generation backward (option bwd_gen != 1)");
+        return s;
+    } else {
+        const Plan pl = plan_bwd(p, s.vec);
+        s.family = Family::Bwd;
+        s.items = pl.items; s.rows = pl.rows; s.nb = pl.nb; s.P = (p->dim / p->n_groups) / pl.rows; s.RB = 1;
+        s.slab2 = pl.slab2; s.glds = pl.glds; s.lds = pl.lds;
+        s.report = {pl.items, pl.rows, pl.grid, (int32_t)pl.lds, pl.tiles, pl.nb};
+    }
+    if (s.family != Family::Bwdr) {
+        const int t = g_opt_bwd_touch.load();        // bit 0 of flags = NO touches
+        s.flags |= (t == 1 || (t == 0 && s.family == Family::Bwd4)) ? 0 : 1;
+    }
+    if (s.lds > kLdsLimit) s.status = fail(SIGMA_ERR_BAD_SHAPE, "LDS budget exceeded (%zu B)", s.lds);
+    s.slab = s.P > 1 ? (int64_t)s.P * p->batch * p->n_groups * (int64_t)N * p->seqlen : 0;
+    s.summ = summary_floats(p, s.S);
+    return s;
+}
+
+// everything of the backward's arguments but the chained walk's tiles (rowlane_chain_tiles, a launch-time decision)
+sigma::BwdArgs make_bwd_args(const sigma_scan_bwd_params* q, const ScanPlan& s) {
+    const sigma_scan_fwd_params* p = &q->fwd;
+    sigma::BwdArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.f = make_fwd_args(p, s.rows, 1, s.nb, s.vec);
+    a.dout = q->dout; a.du = q->du; a.ddelta = q->ddelta;
+    a.dA = q->dA; a.dB = q->dB; a.dC = q->dC; a.dD = q->dD; a.dbias = q->ddelta_bias;
+    a.g_bs = q->dout_batch_stride; a.g_ds = q->dout_d_stride;
+    a.du_bs = q->du_batch_stride; a.du_ds = q->du_d_stride;
+    a.dd_bs = q->ddelta_batch_stride; a.dd_ds = q->ddelta_d_stride;
+    a.dA_ds = q->dA_d_stride; a.dA_ns = q->dA_dstate_stride;
+    a.dB_bs = q->dB_batch_stride; a.dB_gs = q->dB_group_stride; a.dB_ns = q->dB_dstate_stride;
+    a.dC_bs = q->dC_batch_stride; a.dC_gs = q->dC_group_stride; a.dC_ns = q->dC_dstate_stride;
+    a.P = s.P; a.S = s.S; a.seg_tiles = s.seg_tiles; a.RB = s.RB; a.slab2 = s.slab2; a.flags = s.flags;
+    a.g_gshift = q->dout_group_shift;
+    a.out_vec_ok = (aligned_to(q->dB, 16) && aligned_to(q->dC, 16) && q->dB_batch_stride % 4 == 0 &&
+                    q->dB_group_stride % 4 == 0 && q->dB_dstate_stride % 4 == 0 && q->dC_batch_stride % 4 == 0 &&
+                    q->dC_group_stride % 4 == 0 && q->dC_dstate_stride % 4 == 0) ? 1 : 0;
+    float* ws = static_cast<float*>(q->workspace);
+    a.ws_dB = s.slab ? ws : nullptr;
+    a.ws_dC = s.slab ? ws + s.slab : nullptr;
+    a.summ = s.summ ? ws + 2 * s.slab : nullptr;
+    if (s.chain) {
+        a.chain_carry = ws + 2 * s.slab + s.summ;
+        a.chain_flag = reinterpret_cast<int*>(a.chain_carry + (int64_t)p->batch * (p->dim / 64) * p->dstate * 64);
+    }
+    return a;
+}
+
+// the caller's scratch against the plan's layout: checked before any HIP call
+int check_workspace(const void* ws, int64_t have, int64_t need, const char* what) {
+    if (need == 0) return SIGMA_OK;
+    if (!ws || have < need)
+        return fail(SIGMA_ERR_NULL_ARG, "%sworkspace of %lld bytes required (got %lld)", what, (long long)need, (long long)have);
+    if (!aligned_to(ws, 16)) return fail(SIGMA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
+    return SIGMA_OK;
+}
+
+int copy_report(const ScanPlan& s, int32_t plan[6]) {
+    if (s.status == SIGMA_OK) std::copy(s.report.begin(), s.report.end(), plan);
+    return s.status;
+}
 }  // namespace
 
 extern "C" {
@@ -643,21 +810,7 @@ int sigma_scan_fwd_plan(const sigma_scan_fwd_params* p, int32_t plan[6]) {
     int rc = check_fwd(p, false, false);
     if (rc) return rc;
     if (!plan) return fail(SIGMA_ERR_NULL_ARG, "plan is NULL");
-    if (p->ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_16) {
-        const PlanR pr = plan_rowlane(p, true, false);
-        if (!pr.ok) return fail(SIGMA_ERR_BAD_SHAPE, "ckpt_pitch 16 (row-lane kernels) is not available for this problem");
-        // items 16, rows slot = state waves, tiles slot = segments, states_per_block slot = -200
-        plan[0] = 16; plan[1] = pr.NW; plan[2] = pr.grid; plan[3] = (int32_t)sigma::fwdr_lds_bytes(pr.NW); plan[4] = pr.S; plan[5] = -200;
-        return SIGMA_OK;
-    }
-    const PlanF4 p4 = plan_fwd4(p, true);
-    if (p4.ok) {      // quad-row forward: items 10, rows slot = waves (4 rows each), states_per_block slot = -100
-        plan[0] = 10; plan[1] = p4.W; plan[2] = p4.grid; plan[3] = (int32_t)p4.lds; plan[4] = 1; plan[5] = -100;
-        return SIGMA_OK;
-    }
-    Plan pl = plan_fwd(p, true);
-    plan[0] = pl.items; plan[1] = pl.rows; plan[2] = pl.grid; plan[3] = (int32_t)pl.lds; plan[4] = pl.tiles; plan[5] = pl.nb;
-    return SIGMA_OK;
+    return copy_report(plan_forward(p, false), plan);
 }
 
 int sigma_scan_bwd_plan(const sigma_scan_bwd_params* p, int32_t plan[6]) {
@@ -665,122 +818,54 @@ int sigma_scan_bwd_plan(const sigma_scan_bwd_params* p, int32_t plan[6]) {
     int rc = check_fwd(&p->fwd, false, false);
     if (rc) return rc;
     if (!plan) return fail(SIGMA_ERR_NULL_ARG, "plan is NULL");
-    if (p->fwd.ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_16) {
-        const PlanR pr = plan_rowlane(&p->fwd, true, true);
-        if (!pr.ok) return fail(SIGMA_ERR_BAD_SHAPE, "ckpt_pitch 16 (row-lane kernels) is not available for this problem");
-        plan[0] = 16; plan[1] = pr.NW; plan[2] = pr.grid; plan[3] = (int32_t)sigma::bwdr_lds_bytes(4); plan[4] = pr.S; plan[5] = -200;
-        return SIGMA_OK;
-    }
-    if (p->fwd.ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_160) {
-        const Plan4 p4 = plan_bwd4(&p->fwd, true);
-        if (!p4.ok) return fail(SIGMA_ERR_BAD_SHAPE, "ckpt_pitch 160 (quad-row backward) is not available for this problem");
-        // items = 10, rows slot = waves (4 rows each), states_per_block slot = -(100 + states per barrier)
-        // items slot: 10 (+ 1000 x sequence segments when the sequence is split)
-        plan[0] = 10 + (p4.S > 1 ? 1000 * p4.S : 0); plan[1] = p4.W; plan[2] = p4.grid; plan[3] = (int32_t)p4.lds; plan[4] = -p4.RB; plan[5] = -(100 + p4.SB);
-        return SIGMA_OK;
-    }
-    const Plan3 p3 = plan_bwd3(&p->fwd, true);
-    if (p3.ok) {       // items = 5, states_per_block slot = -(waves per row) marks the state-parallel kernel
-        plan[0] = 5; plan[1] = p3.nw; plan[2] = p3.grid; plan[3] = (int32_t)p3.lds; plan[4] = -p3.RB; plan[5] = -(p->fwd.dstate / 4);
-        return SIGMA_OK;
-    }
-    const Plan2 p2 = plan_bwd2(&p->fwd, true);
-    if (p2.ok) {       // tiles_per_workgroup slot: -(row blocks per workgroup) marks the second-generation kernel
-        plan[0] = p2.items; plan[1] = p2.rows; plan[2] = p2.grid; plan[3] = (int32_t)p2.lds; plan[4] = -p2.RB; plan[5] = p2.nb;
-        return SIGMA_OK;
-    }
-    Plan pl = plan_bwd(&p->fwd, true);
-    plan[0] = pl.items; plan[1] = pl.rows; plan[2] = pl.grid; plan[3] = (int32_t)pl.lds; plan[4] = pl.tiles; plan[5] = pl.nb;
-    return SIGMA_OK;
+    return copy_report(plan_backward(p, false), plan);
+}
+
+int64_t sigma_scan_fwd_workspace_bytes(const sigma_scan_fwd_params* p) {
+    if (check_fwd(p, false, false)) return -1;
+    if (p->batch == 0 || p->seqlen == 0) return 0;
+    const ScanPlan s = plan_forward(p, false);
+    return s.status ? -1 : s.workspace_bytes();
+}
+
+int64_t sigma_scan_bwd_workspace_bytes(const sigma_scan_bwd_params* q) {
+    if (!q) { fail(SIGMA_ERR_NULL_ARG, "params is NULL"); return -1; }
+    if (check_fwd(&q->fwd, false, false)) return -1;
+    if (q->fwd.batch == 0 || q->fwd.seqlen == 0) return 0;
+    const ScanPlan s = plan_backward(q, false);
+    return s.status ? -1 : s.workspace_bytes();
 }
 
 int sigma_selective_scan_fwd(const sigma_scan_fwd_params* p, void* stream) {
     int rc = check_fwd(p, true);
     if (rc) return rc;
     if (p->batch == 0 || p->seqlen == 0) return SIGMA_OK;
-    const bool vec = vec_ok_fwd(p, true) && (p->rev_group_mask == 0 || p->seqlen % 4 == 0);
-    if (p->ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_16) {
-        const PlanR pr = plan_rowlane(p, vec, false);
-        if (!pr.ok)
-            return fail(SIGMA_ERR_BAD_SHAPE, "ckpt_pitch 16 needs f32 IO, 16-byte aligned operands, dstate in {4,8,16}, seqlen %% 4 == 0 and rows per group divisible by 64");
-        const int64_t need = rowlane_summary_floats(p, pr.S) * (int64_t)sizeof(float);
-        if (need > 0) {
-            if (!p->workspace || p->workspace_bytes < need)
-                return fail(SIGMA_ERR_NULL_ARG, "forward workspace of %lld bytes required (got %lld)", (long long)need, (long long)p->workspace_bytes);
-            if (!aligned_to(p->workspace, 16)) return fail(SIGMA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
-        }
-        sigma::FwdArgs a = make_fwd_args(p, pr.NW, 1, p->dstate, vec);
-        a.rowblocks = pr.P; a.segs = pr.S; a.seg_tiles = pr.seg_tiles;
-        a.fsumm = need > 0 ? static_cast<float*>(p->workspace) : nullptr;
-        hipError_t e = sigma::launch_scan_fwdr(a, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return fail(SIGMA_ERR_LAUNCH, "scan_fwdr launch failed: %s", hipGetErrorString(e));
-        return SIGMA_OK;
+    const ScanPlan s = plan_forward(p, true);
+    if (s.status) return s.status;
+    rc = check_workspace(p->workspace, p->workspace_bytes, s.workspace_bytes(), "forward ");
+    if (rc) return rc;
+    sigma::FwdArgs a = make_fwd_args(p, s.rows, s.tiles, s.nb, s.vec);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const char* kernel;
+    hipError_t e;
+    switch (s.family) {
+        case Family::Fwdr:
+            a.rowblocks = s.P; a.segs = s.S; a.seg_tiles = s.seg_tiles;
+            a.fsumm = s.summ ? static_cast<float*>(p->workspace) : nullptr;
+            kernel = "scan_fwdr";
+            e = sigma::launch_scan_fwdr(a, st);
+            break;
+        case Family::Fwd4:
+            a.rowblocks = s.P;
+            kernel = "scan_fwd4";
+            e = sigma::launch_scan_fwd4(a, st);
+            break;
+        default:
+            kernel = "scan_fwd";
+            e = sigma::launch_scan_fwd(a, p->io_dtype, s.items, s.glds, g_opt_fwd_prefetch.load() != 2, st);
     }
-    const PlanF4 p4 = plan_fwd4(p, vec);
-    if (p4.ok) {
-        sigma::FwdArgs a = make_fwd_args(p, p4.W, 1, p->dstate, vec);
-        a.rowblocks = p4.P;
-        hipError_t e = sigma::launch_scan_fwd4(a, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return fail(SIGMA_ERR_LAUNCH, "scan_fwd4 launch failed: %s", hipGetErrorString(e));
-        return SIGMA_OK;
-    }
-    const Plan pl = plan_fwd(p, vec);
-    if (pl.lds > kLdsLimit) return fail(SIGMA_ERR_BAD_SHAPE, "LDS budget exceeded (%zu B)", pl.lds);
-    const sigma::FwdArgs a = make_fwd_args(p, pl.rows, pl.tiles, pl.nb, vec);
-    hipError_t e = sigma::launch_scan_fwd(a, p->io_dtype, pl.items, pl.glds, g_opt_fwd_prefetch.load() != 2,
-                                          static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(SIGMA_ERR_LAUNCH, "scan_fwd launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(SIGMA_ERR_LAUNCH, "%s launch failed: %s", kernel, hipGetErrorString(e));
     return SIGMA_OK;
-}
-
-namespace {
-bool vec_ok_bwd(const sigma_scan_bwd_params* q) {
-    const sigma_scan_fwd_params* p = &q->fwd;
-    const size_t al = 4 * (size_t)elem_size(p->io_dtype);
-    return vec_ok_fwd(p, false) && aligned_to(q->dout, al) && aligned_to(q->du, al) && aligned_to(q->ddelta, al) &&
-           q->dout_batch_stride % 4 == 0 && q->dout_d_stride % 4 == 0 && q->du_batch_stride % 4 == 0 &&
-           q->du_d_stride % 4 == 0 && q->ddelta_batch_stride % 4 == 0 && q->ddelta_d_stride % 4 == 0 &&
-           (p->rev_group_mask == 0 || p->seqlen % 4 == 0);
-}
-}  // namespace
-
-int64_t sigma_scan_fwd_workspace_bytes(const sigma_scan_fwd_params* p) {
-    if (!p) { fail(SIGMA_ERR_NULL_ARG, "params is NULL"); return -1; }
-    if (check_fwd(p, false, false)) return -1;
-    if (p->batch == 0 || p->seqlen == 0 || p->ckpt_pitch != SIGMA_SCAN_CKPT_PITCH_16) return 0;
-    const PlanR pr = plan_rowlane(p, true, false);
-    if (!pr.ok) { fail(SIGMA_ERR_BAD_SHAPE, "ckpt_pitch 16 (row-lane kernels) is not available for this problem"); return -1; }
-    return rowlane_summary_floats(p, pr.S) * (int64_t)sizeof(float);
-}
-
-int64_t sigma_scan_bwd_workspace_bytes(const sigma_scan_bwd_params* q) {
-    if (!q) { fail(SIGMA_ERR_NULL_ARG, "params is NULL"); return -1; }
-    const sigma_scan_fwd_params* p = &q->fwd;
-    if (check_fwd(p, false, false)) return -1;
-    if (p->batch == 0 || p->seqlen == 0) return 0;
-    if (p->ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_16) {
-        const PlanR pr = plan_rowlane(p, true, true);
-        if (!pr.ok) { fail(SIGMA_ERR_BAD_SHAPE, "ckpt_pitch 16 (row-lane kernels) is not available for this problem"); return -1; }
-        const int64_t slabs = pr.P <= 1 ? 0 : (int64_t)2 * pr.P * p->batch * p->n_groups * (int64_t)p->dstate * p->seqlen;
-        return (slabs + rowlane_summary_floats(p, pr.S) + rowlane_chain_floats(p)) * (int64_t)sizeof(float);
-    }
-    if (p->ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_160) {
-        const Plan4 p4 = plan_bwd4(p, true);
-        if (!p4.ok) { fail(SIGMA_ERR_BAD_SHAPE, "ckpt_pitch 160 (quad-row backward) is not available for this problem"); return -1; }
-        const int64_t slabs = p4.P <= 1 ? 0 : (int64_t)2 * p4.P * p->batch * p->n_groups * (int64_t)p->dstate * p->seqlen * (int64_t)sizeof(float);
-        const int64_t summ = p4.S <= 1 ? 0 : (int64_t)(p4.S - 1) * p->batch * p->dim * (int64_t)p->dstate * 2 * (int64_t)sizeof(float);
-        return slabs + summ;
-    }
-    const Plan3 p3 = plan_bwd3(p, true);     // no plan's workgroup count depends on alignment
-    if (p3.ok)
-        return p3.P <= 1 ? 0 : (int64_t)2 * p3.P * p->batch * p->n_groups * (int64_t)p->dstate * p->seqlen * (int64_t)sizeof(float);
-    const Plan2 p2 = plan_bwd2(p, true);
-    if (p2.ok)
-        return p2.P <= 1 ? 0 : (int64_t)2 * p2.P * p->batch * p->n_groups * (int64_t)p->dstate * p->seqlen * (int64_t)sizeof(float);
-    const Plan pl = plan_bwd(p, true);
-    const int P = (p->dim / p->n_groups) / pl.rows;
-    if (P <= 1) return 0;
-    return (int64_t)2 * P * p->batch * p->n_groups * (int64_t)p->dstate * p->seqlen * (int64_t)sizeof(float);
 }
 
 int sigma_selective_scan_bwd(const sigma_scan_bwd_params* q, void* stream) {
@@ -795,114 +880,27 @@ int sigma_selective_scan_bwd(const sigma_scan_bwd_params* q, void* stream) {
         return fail(SIGMA_ERR_NULL_ARG, "x (forward checkpoints) is required when seqlen > the checkpoint pitch");
     if ((p->D == nullptr) != (q->dD == nullptr) || (p->delta_bias == nullptr) != (q->ddelta_bias == nullptr))
         return fail(SIGMA_ERR_NULL_ARG, "dD / ddelta_bias must be given exactly when D / delta_bias are");
-    const bool vec = vec_ok_bwd(q);
     if (q->dout_group_shift < 0 || q->dout_group_shift > 5)
         return fail(SIGMA_ERR_BAD_SHAPE, "dout_group_shift must be in [0, 5] (got %d)", q->dout_group_shift);
-    if (p->ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_16) {
-        const PlanR pr = plan_rowlane(p, vec, true);
-        if (!pr.ok)
-            return fail(SIGMA_ERR_BAD_SHAPE, "ckpt_pitch 16 needs f32 IO, 16-byte aligned operands, dstate in {4,8,16}, seqlen %% 4 == 0 and rows per group divisible by 64");
-        if (p->seqlen > SIGMA_SCAN_CKPT_PITCH_16 && !p->x)
-            return fail(SIGMA_ERR_NULL_ARG, "x (forward checkpoints) is required when seqlen > the checkpoint pitch");
-        const int64_t slab = pr.P > 1 ? (int64_t)pr.P * p->batch * p->n_groups * (int64_t)p->dstate * p->seqlen : 0;
-        const int64_t summ = rowlane_summary_floats(p, pr.S);
-        const int64_t need = (2 * slab + summ + rowlane_chain_floats(p)) * (int64_t)sizeof(float);
-        if (need > 0) {
-            if (!q->workspace || q->workspace_bytes < need)
-                return fail(SIGMA_ERR_NULL_ARG, "workspace of %lld bytes required (got %lld)", (long long)need, (long long)q->workspace_bytes);
-            if (!aligned_to(q->workspace, 16)) return fail(SIGMA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
-        }
-        sigma::BwdArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.f = make_fwd_args(p, pr.NW, 1, p->dstate, vec);
-        a.dout = q->dout; a.du = q->du; a.ddelta = q->ddelta;
-        a.dA = q->dA; a.dB = q->dB; a.dC = q->dC; a.dD = q->dD; a.dbias = q->ddelta_bias;
-        a.g_bs = q->dout_batch_stride; a.g_ds = q->dout_d_stride;
-        a.du_bs = q->du_batch_stride; a.du_ds = q->du_d_stride;
-        a.dd_bs = q->ddelta_batch_stride; a.dd_ds = q->ddelta_d_stride;
-        a.dA_ds = q->dA_d_stride; a.dA_ns = q->dA_dstate_stride;
-        a.dB_bs = q->dB_batch_stride; a.dB_gs = q->dB_group_stride; a.dB_ns = q->dB_dstate_stride;
-        a.dC_bs = q->dC_batch_stride; a.dC_gs = q->dC_group_stride; a.dC_ns = q->dC_dstate_stride;
-        a.P = pr.P; a.S = pr.S; a.seg_tiles = pr.seg_tiles;
-        a.g_gshift = q->dout_group_shift;
-        a.out_vec_ok = (aligned_to(q->dB, 16) && aligned_to(q->dC, 16) && q->dB_batch_stride % 4 == 0 &&
-                        q->dB_group_stride % 4 == 0 && q->dB_dstate_stride % 4 == 0 && q->dC_batch_stride % 4 == 0 &&
-                        q->dC_group_stride % 4 == 0 && q->dC_dstate_stride % 4 == 0) ? 1 : 0;
-        a.ws_dB = pr.P > 1 ? static_cast<float*>(q->workspace) : nullptr;
-        a.ws_dC = pr.P > 1 ? static_cast<float*>(q->workspace) + slab : nullptr;
-        a.summ = summ > 0 ? static_cast<float*>(q->workspace) + 2 * slab : nullptr;
-        a.chain_W = rowlane_chain_tiles(p, pr);
-        a.chain_carry = static_cast<float*>(q->workspace) + 2 * slab + summ;
-        a.chain_flag = reinterpret_cast<int*>(a.chain_carry + (int64_t)p->batch * (p->dim / 64) * p->dstate * 64);
-        hipError_t e = sigma::launch_scan_bwdr(a, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return fail(SIGMA_ERR_LAUNCH, "scan_bwdr launch failed: %s", hipGetErrorString(e));
-        return SIGMA_OK;
+    const ScanPlan s = plan_backward(q, true);
+    if (s.status) return s.status;
+    rc = check_workspace(q->workspace, q->workspace_bytes, s.workspace_bytes(), "");
+    if (rc) return rc;
+    sigma::BwdArgs a = make_bwd_args(q, s);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t e;
+    switch (s.family) {
+        case Family::Bwdr:
+            a.chain_W = rowlane_chain_tiles(p, s.P, s.S);      // asks the device for occupancy
+            e = sigma::launch_scan_bwdr(a, st);
+            break;
+        case Family::Bwd4: e = sigma::launch_scan_bwd4(a, st); break;
+        case Family::Bwd3: e = sigma::launch_scan_bwd3(a, p->io_dtype, s.glds, st); break;
+        case Family::Bwd2: e = sigma::launch_scan_bwd2(a, p->io_dtype, s.items, s.glds, st); break;
+        default: e = sigma::launch_scan_bwd(a, p->io_dtype, s.items, s.glds, st);
     }
-    Plan4 p4;
-    std::memset(&p4, 0, sizeof(p4));
-    if (p->ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_160) {
-        // B/C alignment is part of the plan: the caller chose the pitch at forward time with the same tensors
-        p4 = plan_bwd4(p, vec_ok_fwd(p, false));
-        if (!p4.ok)
-            return fail(SIGMA_ERR_BAD_SHAPE, "ckpt_pitch 160 needs f32 IO, 16-byte aligned B/C, dstate in {4,8,16} and rows per group divisible by 4");
-    }
-    const Plan3 p3 = p4.ok ? Plan3{} : plan_bwd3(p, vec);
-    Plan2 p2;
-    std::memset(&p2, 0, sizeof(p2));
-    if (!p3.ok && !p4.ok) p2 = plan_bwd2(p, vec);
-    Plan pl;
-    if (p4.ok) { pl.items = 10; pl.rows = p4.W; pl.tiles = 1; pl.nb = p->dstate; pl.grid = p4.grid; pl.glds = true; pl.lds = p4.lds; pl.slab2 = false; }
-    else if (p3.ok) { pl.items = 5; pl.rows = p3.nw; pl.tiles = 1; pl.nb = p->dstate; pl.grid = p3.grid; pl.glds = p3.glds; pl.lds = p3.lds; pl.slab2 = false; }
-    else if (p2.ok) { pl.items = p2.items; pl.rows = p2.rows; pl.tiles = 1; pl.nb = p2.nb; pl.grid = p2.grid; pl.glds = p2.glds; pl.lds = p2.lds; pl.slab2 = p2.slab2; }
-    else pl = plan_bwd(p, vec);
-    if (!p2.ok && !p3.ok && p->ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_320 && g_opt_bwd_gen.load() == 1)
-        return fail(SIGMA_ERR_BAD_OPTION, "ckpt_pitch 320 needs the second-generation backward (option bwd_gen != 1)");
-    if (pl.lds > kLdsLimit) return fail(SIGMA_ERR_BAD_SHAPE, "LDS budget exceeded (%zu B)", pl.lds);
-    const int P = p4.ok ? p4.P : p3.ok ? p3.P : (p2.ok ? p2.P : (p->dim / p->n_groups) / pl.rows);
-    const int64_t slab = P > 1 ? (int64_t)P * p->batch * p->n_groups * (int64_t)p->dstate * p->seqlen : 0;
-    const int S = p4.ok ? p4.S : 1;
-    const int64_t summ_floats = S > 1 ? (int64_t)(S - 1) * p->batch * p->dim * (int64_t)p->dstate * 2 : 0;
-    if (P > 1 || S > 1) {
-        const int64_t need = (2 * slab + summ_floats) * (int64_t)sizeof(float);
-        if (!q->workspace || q->workspace_bytes < need)
-            return fail(SIGMA_ERR_NULL_ARG, "workspace of %lld bytes required (got %lld)", (long long)need, (long long)q->workspace_bytes);
-        if (!aligned_to(q->workspace, 16)) return fail(SIGMA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
-    }
-    sigma::BwdArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.f = make_fwd_args(p, pl.rows, 1, pl.nb, vec);
-    a.dout = q->dout; a.du = q->du; a.ddelta = q->ddelta;
-    a.dA = q->dA; a.dB = q->dB; a.dC = q->dC; a.dD = q->dD; a.dbias = q->ddelta_bias;
-    a.g_bs = q->dout_batch_stride; a.g_ds = q->dout_d_stride;
-    a.du_bs = q->du_batch_stride; a.du_ds = q->du_d_stride;
-    a.dd_bs = q->ddelta_batch_stride; a.dd_ds = q->ddelta_d_stride;
-    a.dA_ds = q->dA_d_stride; a.dA_ns = q->dA_dstate_stride;
-    a.dB_bs = q->dB_batch_stride; a.dB_gs = q->dB_group_stride; a.dB_ns = q->dB_dstate_stride;
-    a.dC_bs = q->dC_batch_stride; a.dC_gs = q->dC_group_stride; a.dC_ns = q->dC_dstate_stride;
-    if (q->dout_group_shift < 0 || q->dout_group_shift > 5)
-        return fail(SIGMA_ERR_BAD_SHAPE, "dout_group_shift must be in [0, 5] (got %d)", q->dout_group_shift);
-    a.P = P;
-    a.slab2 = pl.slab2 ? 1 : 0;
-    a.g_gshift = q->dout_group_shift;
-    a.out_vec_ok = (aligned_to(q->dB, 16) && aligned_to(q->dC, 16) && q->dB_batch_stride % 4 == 0 &&
-                    q->dB_group_stride % 4 == 0 && q->dB_dstate_stride % 4 == 0 && q->dC_batch_stride % 4 == 0 &&
-                    q->dC_group_stride % 4 == 0 && q->dC_dstate_stride % 4 == 0) ? 1 : 0;
-    a.ws_dB = P > 1 ? static_cast<float*>(q->workspace) : nullptr;
-    a.ws_dC = P > 1 ? static_cast<float*>(q->workspace) + slab : nullptr;
-    {
-        const int t = g_opt_bwd_touch.load();        // bit 0 of flags = NO touches
-        a.flags = (t == 1 || (t == 0 && p4.ok)) ? 0 : 1;
-    }
-    a.RB = p4.ok ? p4.RB : p3.ok ? p3.RB : (p2.ok ? p2.RB : 1);
-    a.S = 1;
-    if (p4.ok) {
-        a.slab2 = p4.SB; a.f.NB = p4.nbuf; if (p4.wgs == 2) a.flags |= 2;
-        a.S = p4.S; a.seg_tiles = p4.seg_tiles;
-        a.summ = S > 1 ? static_cast<float*>(q->workspace) + 2 * slab : nullptr;
-    }
-    hipError_t e = p4.ok ? sigma::launch_scan_bwd4(a, static_cast<hipStream_t>(stream)) : p3.ok ? sigma::launch_scan_bwd3(a, p->io_dtype, pl.glds, static_cast<hipStream_t>(stream)) : p2.ok ? sigma::launch_scan_bwd2(a, p->io_dtype, pl.items, pl.glds, static_cast<hipStream_t>(stream))
-                         : sigma::launch_scan_bwd(a, p->io_dtype, pl.items, pl.glds, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(SIGMA_ERR_LAUNCH, "scan_bwd launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess)
+        return fail(SIGMA_ERR_LAUNCH, "%s launch failed: %s", s.family == Family::Bwdr ? "scan_bwdr" : "scan_bwd", hipGetErrorString(e));
     return SIGMA_OK;
 }
 

@@ -491,18 +491,8 @@ template <typename io_t, int T, bool GLDS, int MAXW>
 static hipError_t launch_bwd2_t(const BwdArgs& a, hipStream_t stream) {
     const size_t lds = bwd2_lds_bytes(T, a.f.R, a.f.NB, a.f.N, a.slab2 != 0, a.RB);
     const int grid = a.f.batch * a.f.G * a.P;
-    auto kern = scan_bwd2_kernel<io_t, T, GLDS, MAXW>;
-    // raise the dynamic-LDS cap per device and kernel (the attribute is per device)
-    static std::atomic<size_t> lds_cap[kMaxDevices];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (lds > 48 * 1024 && lds > lds_cap[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_cap[dev].store(lds, std::memory_order_relaxed);
-    }
+    constexpr auto kern = scan_bwd2_kernel<io_t, T, GLDS, MAXW>;
+    if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || a.P == 1) return e;

@@ -363,17 +363,8 @@ static hipError_t launch_bwd3_w(const BwdArgs& a, hipStream_t stream) {
     const int nw = a.f.R;                                  // waves per workgroup = slots * Q
     const size_t lds = bwd3_lds_bytes(nw, a.f.N, a.RB);
     const int grid = a.f.batch * a.f.G * a.P;
-    auto kern = scan_bwd3_kernel<io_t, GLDS, MAXW>;
-    static std::atomic<size_t> lds_cap[kMaxDevices];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (lds > 48 * 1024 && lds > lds_cap[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_cap[dev].store(lds, std::memory_order_relaxed);
-    }
+    constexpr auto kern = scan_bwd3_kernel<io_t, GLDS, MAXW>;
+    if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(nw * 64), lds, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || a.P == 1) return e;

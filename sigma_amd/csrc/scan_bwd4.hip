@@ -643,17 +643,8 @@ template <int MAXW>
 static hipError_t launch_bwd4_t(const BwdArgs& a, hipStream_t stream) {
     const size_t lds = bwd4_lds_bytes(a.f.R, a.f.N, a.slab2, a.RB, a.f.NB);
     const int grid = a.f.batch * a.f.G * a.P * a.S;
-    auto kern = scan_bwd4_kernel<MAXW>;
-    static std::atomic<size_t> lds_cap[kMaxDevices];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (lds > 48 * 1024 && lds > lds_cap[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_cap[dev].store(lds, std::memory_order_relaxed);
-    }
+    constexpr auto kern = scan_bwd4_kernel<MAXW>;
+    if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || a.P == 1) return e;
@@ -668,17 +659,8 @@ static hipError_t launch_rev_summary4(const BwdArgs& a, hipStream_t stream) {
     const int Pq = quads / W4;
     const size_t lds = fwd4_lds_bytes(a.f.N);
     const int grid = a.f.batch * a.f.G * Pq * (a.S - 1);
-    auto kern = rev_summary4_kernel;
-    static std::atomic<size_t> lds_cap[kMaxDevices];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (lds > 48 * 1024 && lds > lds_cap[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_cap[dev].store(lds, std::memory_order_relaxed);
-    }
+    constexpr auto kern = rev_summary4_kernel;
+    if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(W4 * 64), lds, stream, a, Pq);
     return hipGetLastError();
 }

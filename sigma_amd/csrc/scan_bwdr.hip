@@ -970,16 +970,8 @@ static hipError_t launch_bwdr_t(const BwdArgs& a, hipStream_t stream) {
     const long nrb = (long)a.f.batch * a.f.G * a.P;
     const int grid = MODE == 2 ? (int)((nrb * ntiles + a.chain_W - 1) / a.chain_W) : (int)(nrb * S);
     const size_t lds = bwdr_lds_bytes(4);
-    auto kern = scan_bwdr_kernel<NS, MODE>;
-    static std::atomic<size_t> lds_cap[kMaxDevices];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (lds > 48 * 1024 && lds > lds_cap[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_cap[dev].store(lds, std::memory_order_relaxed);
-    }
+    constexpr auto kern = scan_bwdr_kernel<NS, MODE>;
+    if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
     if (MODE == 2) {
         hipError_t e = hipMemsetAsync(a.chain_flag, 0, (size_t)nrb * sizeof(int), stream);
         if (e != hipSuccess) return e;

@@ -274,18 +274,8 @@ template <typename io_t, int T, bool GLDS, bool PREFETCH, bool WSPLIT>
 static hipError_t launch_fwd_w(const FwdArgs& a, hipStream_t stream) {
     const size_t lds = fwd_lds_bytes(T, a.R, a.W, a.NB, a.N);
     const int grid = a.rowblocks * a.batch;
-    auto kern = scan_fwd_kernel<io_t, T, GLDS, PREFETCH, WSPLIT>;
-    // raise the dynamic-LDS cap once per device, kernel and size (not per launch: the call is host-expensive)
-    static std::atomic<size_t> lds_cap[kMaxDevices];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (lds > 48 * 1024 && lds > lds_cap[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_cap[dev].store(lds, std::memory_order_relaxed);
-    }
+    constexpr auto kern = scan_fwd_kernel<io_t, T, GLDS, PREFETCH, WSPLIT>;
+    if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(a.R * a.W * 64), lds, stream, a);
     return hipGetLastError();
 }

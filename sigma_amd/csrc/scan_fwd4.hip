@@ -167,17 +167,8 @@ scan_fwd4_kernel(const FwdArgs p) {
 hipError_t launch_scan_fwd4(const FwdArgs& a, hipStream_t stream) {
     const size_t lds = fwd4_lds_bytes(a.N);
     const int grid = a.batch * a.G * a.rowblocks;
-    auto kern = scan_fwd4_kernel;
-    static std::atomic<size_t> lds_cap[kMaxDevices];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (lds > 48 * 1024 && lds > lds_cap[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_cap[dev].store(lds, std::memory_order_relaxed);
-    }
+    constexpr auto kern = scan_fwd4_kernel;
+    if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(a.R * 64), lds, stream, a);
     return hipGetLastError();
 }

@@ -613,16 +613,8 @@ static hipError_t launch_fwdr_t(const FwdArgs& a, hipStream_t stream) {
     const int S = MODE == 2 ? a.segs - 1 : a.segs;
     const int grid = a.batch * a.G * a.rowblocks * S;
     const size_t lds = fwdr_lds_bytes(NW);
-    auto kern = scan_fwdr_kernel<NS, NW, MODE>;
-    static std::atomic<size_t> lds_cap[kMaxDevices];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (lds > 48 * 1024 && lds > lds_cap[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_cap[dev].store(lds, std::memory_order_relaxed);
-    }
+    constexpr auto kern = scan_fwdr_kernel<NS, NW, MODE>;
+    if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, stream, a);
     return hipGetLastError();
 }

@@ -1,6 +1,7 @@
 // scan_launch.h -- host-side launch helpers shared by the kernel TUs and the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include "scan_device.h"
 
 // rows (waves) per workgroup the backward kernel may use with T = 10 (640-element tiles):
@@ -69,6 +70,20 @@ inline size_t bwdr_lds_bytes(int NW) { return 16 * (size_t)(5 * 256 + NW * 2 * 2
 #endif
 
 constexpr int kMaxDevices = 16;    // per-device cache of the raised dynamic-LDS cap (hipFuncSetAttribute is per device)
+
+// Raise the dynamic-LDS cap of Kern to `lds` bytes once per device and size (not per launch: the call is host-expensive).
+// The cache is keyed by the kernel itself: all instantiations of a scan kernel share one function type.
+template <auto Kern>
+hipError_t raise_lds_cap(size_t lds) {
+    static std::atomic<size_t> cap[kMaxDevices];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= kMaxDevices) dev = 0;
+    if (lds <= 48 * 1024 || lds <= cap[dev].load(std::memory_order_relaxed)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) cap[dev].store(lds, std::memory_order_relaxed);
+    return e;
+}
 
 hipError_t launch_scan_bwd2(const BwdArgs& a, int dtype, int T, bool glds, hipStream_t stream);
 hipError_t launch_scan_bwd3(const BwdArgs& a, int dtype, bool glds, hipStream_t stream);   // a.f.R = waves per workgroup

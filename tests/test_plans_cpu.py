@@ -160,3 +160,88 @@ def test_row_lane_policy_matches_the_measured_table():
     assert ckpt_pitch_for(19200, 16, 768, True, True, 4) == 16
     assert ckpt_pitch_for(1200, 16, 16 * 3072, True, False, 4) == 160
     assert ckpt_pitch_for(19200, 16, 16 * 768, True, True, 4) == 160
+
+
+FAKE = 1 << 40                   # 16-byte aligned stand-ins for device pointers: these calls end before any HIP call
+ERR_NULL_ARG, ERR_BAD_OPTION = 1, 7
+
+
+def _fake_pointers(bp, offset=0):
+    for i, name in enumerate(("u", "delta", "A", "B", "C", "out", "x")):
+        setattr(bp.fwd, name, FAKE + (i << 32) + offset)
+    for i, name in enumerate(("dout", "du", "ddelta", "dA", "dB", "dC")):
+        setattr(bp, name, FAKE + ((8 + i) << 32) + offset)
+
+
+def _bwd_family(plan):
+    t4, t5 = plan[4], plan[5]
+    if t5 == -200:
+        return "row-lane"
+    if t5 <= -100:
+        return "quad-row"
+    if t4 < 0:
+        return "state-parallel" if t5 < 0 else "second generation"
+    return "first generation"
+
+
+@pytest.mark.parametrize("family,pitch,dtype,shape", [
+    ("first generation", 0, _capi.DTYPE_F32, (8, 3072, 1200, 16, 4)),
+    ("first generation", 0, _capi.DTYPE_F16, (8, 3072, 1200, 16, 4)),
+    ("first generation", 0, _capi.DTYPE_BF16, (8, 3072, 1200, 16, 4)),
+    ("second generation", 640, _capi.DTYPE_F32, (8, 3072, 1200, 16, 4)),
+    ("state-parallel", 320, _capi.DTYPE_F32, (8, 3072, 1200, 4, 4)),
+    ("second generation", 320, _capi.DTYPE_F32, (8, 3072, 1200, 16, 4)),
+    ("quad-row", 160, _capi.DTYPE_F32, (16, 3072, 1200, 16, 4)),
+    ("row-lane", 16, _capi.DTYPE_F32, (16, 3072, 1200, 16, 4)),
+    ("row-lane", 16, _capi.DTYPE_F32, (1, 768, 19200, 16, 4)),
+])
+def test_backward_launch_needs_exactly_the_queried_workspace(family, pitch, dtype, shape):
+    """The launch checks the caller's scratch against the same plan the workspace query answers from: one byte short is
+    refused with the queried size -- also with misaligned operands (the queries assume aligned ones), where they are legal."""
+    lib = _capi.load()
+    bp = _params(*shape, pitch)
+    bp.fwd.io_dtype = dtype
+    rc, b = _plan(lib.sigma_scan_bwd_plan, bp)
+    assert rc == 0 and _bwd_family(b) == family, (b, _capi.last_error())
+    need = lib.sigma_scan_bwd_workspace_bytes(ctypes.byref(bp))
+    assert need > 0
+    for offset in ((0, 4) if pitch in (0, 640, 320) else (0,)):
+        _fake_pointers(bp, offset)
+        bp.workspace, bp.workspace_bytes = FAKE + (32 << 32), need - 1
+        assert lib.sigma_selective_scan_bwd(ctypes.byref(bp), None) == ERR_NULL_ARG
+        assert _capi.last_error() == f"workspace of {need} bytes required (got {need - 1})"
+
+
+def test_row_lane_forward_launch_needs_exactly_the_queried_workspace():
+    lib = _capi.load()
+    bp = _params(1, 768, 19200, 16, 4, 16)
+    rc, f = _plan(lib.sigma_scan_fwd_plan, bp)
+    assert rc == 0 and f[5] == -200 and f[4] > 1                 # row-lane forward, sequence in segments
+    need = lib.sigma_scan_fwd_workspace_bytes(ctypes.byref(bp.fwd))
+    assert need > 0
+    _fake_pointers(bp)
+    bp.fwd.workspace, bp.fwd.workspace_bytes = FAKE + (32 << 32), need - 1
+    assert lib.sigma_selective_scan_fwd(ctypes.byref(bp.fwd), None) == ERR_NULL_ARG
+    assert _capi.last_error() == f"forward workspace of {need} bytes required (got {need - 1})"
+
+
+def test_first_generation_option_refuses_pitch_320_in_every_entry_point():
+    """bwd_gen = 1 forces the first-generation backward, which cannot serve ckpt_pitch 320: the plan and workspace queries
+    refuse the problem exactly as the launch does, instead of answering for a plan the launch would not run."""
+    lib = _capi.load()
+    bp = _params(8, 3072, 1200, 4, 4, 320)
+    message = "ckpt_pitch 320 needs the second-generation backward (option bwd_gen != 1)"
+    _capi.set_option("bwd_gen", 1)
+    try:
+        rc, _ = _plan(lib.sigma_scan_bwd_plan, bp)
+        assert rc == ERR_BAD_OPTION and _capi.last_error() == message
+        assert lib.sigma_scan_bwd_workspace_bytes(ctypes.byref(bp)) == -1 and _capi.last_error() == message
+        _fake_pointers(bp)
+        bp.workspace, bp.workspace_bytes = FAKE + (32 << 32), 1 << 40
+        assert lib.sigma_selective_scan_bwd(ctypes.byref(bp), None) == ERR_BAD_OPTION and _capi.last_error() == message
+        rc, f = _plan(lib.sigma_scan_fwd_plan, bp)                # the forward is not affected
+        assert rc == 0
+        rc, b = _plan(lib.sigma_scan_bwd_plan, _params(8, 3072, 1200, 4, 4, 640))
+        assert rc == 0 and _bwd_family(b) == "first generation"
+    finally:
+        _capi.set_option("bwd_gen", 0)
