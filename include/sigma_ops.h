@@ -35,7 +35,7 @@ typedef struct sigma_dwconv_params {
     int32_t n_orders;      /* 2: out2/g2 hold the row-major AND the column-major sequence (SS2D);
                               1: row-major only, i.e. plain conv + SiLU (CroMB / ConMB, vmamba.py:1629-1630,
                               1271-1272) */
-    int32_t reserved_;
+    int32_t flags;         /* ABI 11: SIGMA_DWCONV_* bits; 0 = the contract below                   */
     const float *x;        /* (B, d, H, W)   input of the convolution                              */
     const float *weight;   /* (d, 1, 3, 3)                                                         */
     const float *bias;     /* (d) or NULL                                                          */
@@ -46,17 +46,30 @@ typedef struct sigma_dwconv_params {
     const float *g2;       /* (B, n_orders, d, H*W) gradient of out2                                      */
     float *gpre;           /* (B, d, H, W) scratch: gradient w.r.t. the pre-activation (planes that fit
                               LDS keep it there: then not written)                                  */
-    float *dweight;        /* (d, 1, 3, 3) ACCUMULATED into (caller zeroes)                        */
-    float *dbias;          /* (d) ACCUMULATED into, or NULL                                        */
+    float *dweight;        /* (d, 1, 3, 3) ACCUMULATED into (caller zeroes); WRITTEN with
+                              SIGMA_DWCONV_DETERMINISTIC                                            */
+    float *dbias;          /* (d) ACCUMULATED into, or NULL; WRITTEN with SIGMA_DWCONV_DETERMINISTIC */
     float *dx;             /* (B, d, H, W) fully written                                           */
     /* ABI 10: planes of x and dx need not be packed as (B, d): plane (b, c) starts at b * x_batch_stride + c * x_channel_stride
      * floats (each plane H*W contiguous); 0 / 0 = the contiguous (B, d, H, W) tensor.  SS2D hands the x half of in_proj over
      * in CHANNEL-major order (d, B, H, W) -- written transposed by the GEMM epilogue (sigma_gemm.h, t_cols), read here in place. */
     int64_t x_batch_stride, x_channel_stride;
+    /* ABI 11: device scratch of >= sigma_dwconv3x3_silu_bwd_workspace_bytes() bytes, 16-byte aligned; read only by the
+     * backward with SIGMA_DWCONV_DETERMINISTIC (NULL / 0 otherwise). */
+    void *workspace;
+    int64_t workspace_bytes;
 } sigma_dwconv_params;
+
+/* ABI 11, bit of sigma_dwconv_params.flags: deterministic backward.  Every workgroup stores its dweight / dbias sums to a
+ * slot of the workspace with plain stores and one more pass adds the slots in a fixed order: dweight and dbias are fully
+ * WRITTEN (no zero fill needed) and bitwise reproducible from run to run. */
+#define SIGMA_DWCONV_DETERMINISTIC 1
 
 int sigma_dwconv3x3_silu_fwd(const sigma_dwconv_params *params, void *stream);
 int sigma_dwconv3x3_silu_bwd(const sigma_dwconv_params *params, void *stream);
+/* Scratch bytes of sigma_dwconv3x3_silu_bwd: 0 without SIGMA_DWCONV_DETERMINISTIC, else 40 bytes per channel and
+ * workgroup slot (batch x 32x32 tiles, or batch when a plane fits LDS); negative = invalid params. */
+int64_t sigma_dwconv3x3_silu_bwd_workspace_bytes(const sigma_dwconv_params *params);
 
 /*   sigma_cross_merge_nhwc / sigma_cross_split_nhwc
  *       CrossMerge (vmamba.py:100-108) + the transpose to channels-last in front of out_norm
@@ -159,6 +172,14 @@ int sigma_softmax_ce_bwd(const float *logits, const int64_t *labels, const float
  *       operands.                                                                                                   */
 int sigma_colscale_bwd(const float *dy, const float *x, const float *scale, float *dx, float *dscale, int64_t rows,
                        int32_t channels, void *stream);
+/*   sigma_colscale_bwd_ws (ABI 11)
+ *       the same backward with dscale fully WRITTEN through a deterministic two-stage sum: every block stores its column
+ *       sums to a row of `workspace` (>= sigma_colscale_bwd_workspace_bytes(rows, channels) bytes, 16-byte aligned), a
+ *       second pass adds the rows in a fixed order.  Bitwise reproducible; no zero fill of dscale.  The size query returns
+ *       a negative value for invalid sizes.                                                                           */
+int sigma_colscale_bwd_ws(const float *dy, const float *x, const float *scale, float *dx, float *dscale, int64_t rows,
+                          int32_t channels, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t sigma_colscale_bwd_workspace_bytes(int64_t rows, int32_t channels);
 
 /*   sigma_layernorm_fwd / sigma_layernorm_bwd
  *       nn.LayerNorm(C, eps=1e-5, affine) over the last dimension of a contiguous (rows, C) fp32

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SIGMA_SCAN_ABI_VERSION 10
+#define SIGMA_SCAN_ABI_VERSION 11
 
 /* dtype of u, delta, B, C, out, dout, du, ddelta  (input_t of the reference,
  * selective_scan.cpp:174: float / half / bfloat16).  A, D, delta_bias, x, dA,
@@ -149,21 +149,23 @@ typedef struct sigma_scan_bwd_params {
     const void *dout;            /* (B, dim >> dout_group_shift, L)   io_dtype */
     void *du;                    /* (B, dim, L)   io_dtype, fully written */
     void *ddelta;                /* (B, dim, L)   io_dtype, fully written */
-    float *dA;                   /* (dim, N)      f32, ACCUMULATED into (caller zeroes, :331) */
+    float *dA;                   /* (dim, N)      f32, ACCUMULATED into (caller zeroes, :331); fully WRITTEN when flags has
+                                    SIGMA_SCAN_BWD_DETERMINISTIC (the same holds for dD and ddelta_bias) */
     float *dB;                   /* (B, G, N, L)  f32, fully WRITTEN (the reference zero-fills and
                                     atomically accumulates, :332; here a deterministic 2-stage sum) */
     float *dC;                   /* (B, G, N, L)  f32, fully WRITTEN */
-    float *dD;                   /* (dim) or NULL f32, ACCUMULATED into */
-    float *ddelta_bias;          /* (dim) or NULL f32, ACCUMULATED into */
+    float *dD;                   /* (dim) or NULL f32, ACCUMULATED into (WRITTEN in deterministic mode) */
+    float *ddelta_bias;          /* (dim) or NULL f32, ACCUMULATED into (WRITTEN in deterministic mode) */
     void *workspace;             /* device scratch of >= sigma_scan_bwd_workspace_bytes() bytes,
                                     16-byte aligned; may be NULL when that function returns 0.
-                                    Holds the per-workgroup dB/dC partials; contents are garbage
+                                    Holds the per-workgroup dB/dC partials (deterministic mode: also
+                                    the per-workgroup dA/dD/ddelta_bias partials); contents are garbage
                                     after the call.  Provided by the caller because the callee
                                     never allocates. */
     int64_t workspace_bytes;
     int32_t dout_group_shift;    /* like u_group_shift for dout: CrossMerge's adjoint hands the same
                                     gradient to the directions that share a memory order */
-    int32_t reserved_;
+    int32_t flags;               /* ABI 11: SIGMA_SCAN_BWD_* bits; 0 = the contract above */
     int64_t dout_batch_stride, dout_d_stride;
     int64_t du_batch_stride, du_d_stride;
     int64_t ddelta_batch_stride, ddelta_d_stride;
@@ -172,10 +174,19 @@ typedef struct sigma_scan_bwd_params {
     int64_t dC_batch_stride, dC_group_stride, dC_dstate_stride;
 } sigma_scan_bwd_params;
 
+/* ABI 11, bit of sigma_scan_bwd_params.flags: deterministic backward.  Every workgroup stores its dA / dD / ddelta_bias
+ * partials to a slot of its own in the workspace with plain stores (summed over its tiles in a fixed order), and the
+ * pass that adds the dB / dC partials adds the slots in a fixed order too: the results are bitwise reproducible from run
+ * to run, and dA, dD, ddelta_bias are fully WRITTEN (the caller need not zero them).  The plan (kernel family and
+ * geometry) is the one without the bit; the workspace grows by the slots (sigma_scan_bwd_workspace_bytes).  The
+ * chained walk of the row-lane backward (option "rl_chain") is not used in this mode. */
+#define SIGMA_SCAN_BWD_DETERMINISTIC 1
+
 /* Forward: out, x <- scan(u, delta, A, B, C, D, delta_bias). */
 int sigma_selective_scan_fwd(const sigma_scan_fwd_params *params, void *stream);
 
-/* Backward: du, ddelta, dB, dC written; dA, dD, ddelta_bias accumulated (+=). */
+/* Backward: du, ddelta, dB, dC written; dA, dD, ddelta_bias accumulated (+=), or written with
+ * SIGMA_SCAN_BWD_DETERMINISTIC. */
 int sigma_selective_scan_bwd(const sigma_scan_bwd_params *params, void *stream);
 
 /* Scratch bytes sigma_selective_scan_fwd needs for this problem under the current options (non-zero only for
@@ -183,7 +194,8 @@ int sigma_selective_scan_bwd(const sigma_scan_bwd_params *params, void *stream);
 int64_t sigma_scan_fwd_workspace_bytes(const sigma_scan_fwd_params *params);
 
 /* Scratch bytes sigma_selective_scan_bwd needs for this problem under the current options: the per-workgroup dB/dC
- * partials (0 when one workgroup covers a whole (batch, group)) plus the segment summaries of a split sequence;
+ * partials (0 when one workgroup covers a whole (batch, group)) plus the segment summaries of a split sequence, plus
+ * with SIGMA_SCAN_BWD_DETERMINISTIC the per-row partials: batch x sequence segments x dim x (dstate + 2) floats;
  * negative = invalid params. */
 int64_t sigma_scan_bwd_workspace_bytes(const sigma_scan_bwd_params *params);
 

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SIGMA_HIP_LIB lets a benchmark A/B an experimental build of the same ABI; default is the in-tree library
 LIB_PATH = os.environ.get("SIGMA_HIP_LIB") or os.path.join(_HERE, "lib", "libsigma_hip.so")
 
-SIGMA_SCAN_ABI_VERSION = 10
+SIGMA_SCAN_ABI_VERSION = 11
 SIGMA_SCAN_CHUNK = 2048
 SIGMA_SCAN_CKPT_PITCH = 1280
 SIGMA_SCAN_CKPT_PITCH_FINE = 640
@@ -22,6 +22,8 @@ SIGMA_SCAN_CKPT_PITCH_320 = 320
 SIGMA_SCAN_CKPT_PITCH_160 = 160
 SIGMA_SCAN_CKPT_PITCH_16 = 16
 SIGMA_SCAN_MAX_DSTATE = 256
+SIGMA_SCAN_BWD_DETERMINISTIC = 1    # sigma_scan_bwd_params.flags
+SIGMA_DWCONV_DETERMINISTIC = 1      # sigma_dwconv_params.flags (include/sigma_ops.h)
 
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
 
@@ -58,7 +60,7 @@ class BwdParams(ctypes.Structure):
         ("dA", ctypes.c_void_p), ("dB", ctypes.c_void_p), ("dC", ctypes.c_void_p),
         ("dD", ctypes.c_void_p), ("ddelta_bias", ctypes.c_void_p),
         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
-        ("dout_group_shift", ctypes.c_int32), ("reserved_", ctypes.c_int32),
+        ("dout_group_shift", ctypes.c_int32), ("flags", ctypes.c_int32),
         ("dout_batch_stride", ctypes.c_int64), ("dout_d_stride", ctypes.c_int64),
         ("du_batch_stride", ctypes.c_int64), ("du_d_stride", ctypes.c_int64),
         ("ddelta_batch_stride", ctypes.c_int64), ("ddelta_d_stride", ctypes.c_int64),
@@ -72,12 +74,13 @@ class DwConvParams(ctypes.Structure):
     """mirror of sigma_dwconv_params (include/sigma_ops.h)"""
     _fields_ = [
         ("batch", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
-        ("n_orders", ctypes.c_int32), ("reserved_", ctypes.c_int32),
+        ("n_orders", ctypes.c_int32), ("flags", ctypes.c_int32),
         ("x", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p),
         ("out2", ctypes.c_void_p),
         ("g2", ctypes.c_void_p), ("gpre", ctypes.c_void_p), ("dweight", ctypes.c_void_p), ("dbias", ctypes.c_void_p),
         ("dx", ctypes.c_void_p),
         ("x_batch_stride", ctypes.c_int64), ("x_channel_stride", ctypes.c_int64),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
     ]
 
 
@@ -149,7 +152,10 @@ GEMM_AUX_SYMBOLS = ("sigma_gemm_selftest", "sigma_gemm_workspace_bytes")
 OPS_SYMBOLS = ("sigma_dwconv3x3_silu_fwd", "sigma_dwconv3x3_silu_bwd", "sigma_cross_merge_nhwc", "sigma_cross_split_nhwc",
                "sigma_layernorm_fwd", "sigma_layernorm_bwd", "sigma_layernorm_bwd_partial_rows", "sigma_transpose2d",
                "sigma_pair_sum_add", "sigma_upsample2x_nhwc", "sigma_plane_pool", "sigma_plane_scale",
-               "sigma_plane_dot", "sigma_plane_gate_bwd", "sigma_softmax_ce_fwd", "sigma_softmax_ce_bwd", "sigma_colscale_bwd")
+               "sigma_plane_dot", "sigma_plane_gate_bwd", "sigma_softmax_ce_fwd", "sigma_softmax_ce_bwd", "sigma_colscale_bwd",
+               "sigma_colscale_bwd_ws")
+# the size queries include/sigma_ops.h declares (int64_t results)
+OPS_AUX_SYMBOLS = ("sigma_dwconv3x3_silu_bwd_workspace_bytes", "sigma_colscale_bwd_workspace_bytes")
 
 # every symbol include/sigma_scan.h declares; tests check the library exports all of them
 EXPORTED_SYMBOLS = (
@@ -229,6 +235,9 @@ def load() -> ctypes.CDLL:
         elif name == "sigma_colscale_bwd":
             fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                            ctypes.c_int32, ctypes.c_void_p]
+        elif name == "sigma_colscale_bwd_ws":
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
         elif name == "sigma_softmax_ce_fwd":
             fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
                            ctypes.c_void_p, ctypes.c_void_p]
@@ -240,6 +249,10 @@ def load() -> ctypes.CDLL:
                   TransposeParams if "transpose" in name else DwConvParams)
             fn.argtypes = [P(st), ctypes.c_void_p]
         fn.restype = ctypes.c_int
+    lib.sigma_dwconv3x3_silu_bwd_workspace_bytes.argtypes = [P(DwConvParams)]
+    lib.sigma_dwconv3x3_silu_bwd_workspace_bytes.restype = ctypes.c_int64
+    lib.sigma_colscale_bwd_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32]
+    lib.sigma_colscale_bwd_workspace_bytes.restype = ctypes.c_int64
     for name in GEMM_SYMBOLS:
         fn = getattr(lib, name)
         fn.argtypes = [P(GemmParams), ctypes.c_void_p]

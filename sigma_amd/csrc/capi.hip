@@ -601,8 +601,10 @@ struct ScanPlan {
     bool glds = false;
     size_t lds = 0;
     // workspace layout in floats: [dB partials][dC partials][segment summaries][hand-over area of the chained walk]
-    int64_t slab = 0, summ = 0, chain = 0;
-    int64_t workspace_bytes() const { return (2 * slab + summ + chain) * (int64_t)sizeof(float); }
+    // [per-row partials of the deterministic backward: rpart_K slots of dim x (dstate + 2)]
+    int64_t slab = 0, summ = 0, chain = 0, rpart = 0;
+    int rpart_K = 0;
+    int64_t workspace_bytes() const { return (2 * slab + summ + chain + rpart) * (int64_t)sizeof(float); }
 };
 
 int refuse_rowlane(bool launch) {
@@ -646,6 +648,10 @@ ScanPlan plan_backward(const sigma_scan_bwd_params* q, bool launch) {
     const sigma_scan_fwd_params* p = &q->fwd;
     const int N = p->dstate;
     ScanPlan s;
+    if (q->flags & ~SIGMA_SCAN_BWD_DETERMINISTIC) {
+        s.status = fail(SIGMA_ERR_BAD_OPTION, "unknown bits in sigma_scan_bwd_params.flags (0x%x)", (unsigned)q->flags);
+        return s;
+    }
     s.vec = !launch || vec_ok_bwd(q);
     s.nb = N;
     if (p->ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_16) {
@@ -699,6 +705,11 @@ ScanPlan plan_backward(const sigma_scan_bwd_params* q, bool launch) {
     if (s.lds > kLdsLimit) s.status = fail(SIGMA_ERR_BAD_SHAPE, "LDS budget exceeded (%zu B)", s.lds);
     s.slab = s.P > 1 ? (int64_t)s.P * p->batch * p->n_groups * (int64_t)N * p->seqlen : 0;
     s.summ = summary_floats(p, s.S);
+    if (q->flags & SIGMA_SCAN_BWD_DETERMINISTIC) {
+        // one slot per (batch, sequence segment): the workgroups that share a row differ in exactly those two
+        s.rpart_K = p->batch * s.S;
+        s.rpart = (int64_t)s.rpart_K * p->dim * (N + 2);
+    }
     return s;
 }
 
@@ -728,6 +739,10 @@ sigma::BwdArgs make_bwd_args(const sigma_scan_bwd_params* q, const ScanPlan& s) 
     if (s.chain) {
         a.chain_carry = ws + 2 * s.slab + s.summ;
         a.chain_flag = reinterpret_cast<int*>(a.chain_carry + (int64_t)p->batch * (p->dim / 64) * p->dstate * 64);
+    }
+    if (s.rpart) {
+        a.rpart = ws + 2 * s.slab + s.summ + s.chain;
+        a.rpart_K = s.rpart_K;
     }
     return a;
 }
@@ -891,7 +906,8 @@ int sigma_selective_scan_bwd(const sigma_scan_bwd_params* q, void* stream) {
     hipError_t e;
     switch (s.family) {
         case Family::Bwdr:
-            a.chain_W = rowlane_chain_tiles(p, s.P, s.S);      // asks the device for occupancy
+            // asks the device for occupancy; the deterministic backward never chains (a cut row block has two writers)
+            a.chain_W = s.rpart ? 0 : rowlane_chain_tiles(p, s.P, s.S);
             e = sigma::launch_scan_bwdr(a, st);
             break;
         case Family::Bwd4: e = sigma::launch_scan_bwd4(a, st); break;

@@ -35,7 +35,20 @@ struct DwArgs {
     float* dx;              // bwd2 out: (B, d, H, W)
     int B, d, H, W, orders;
     long x_bs, x_cs;        // plane (b, c) of x / dx at b * x_bs + c * x_cs floats (packed: d * L, L)
+    float* part;            // deterministic mode: [b * tiles + tile][d][10] per-workgroup sums (dW[9], dbias), else NULL
 };
+
+// the 10 per-channel sums of a workgroup (threads 0..9): one atomic each, or (DET) a plain store into the workgroup's slot
+template <bool DET>
+__device__ __forceinline__ void dw_leave(const DwArgs& a, int c, int slot, int k, float s) {
+    if constexpr (DET) {
+        a.part[((long)slot * a.d + c) * 10 + k] = s;
+    } else {
+        (void)slot;
+        if (k < 9) atomicAdd(a.dw + c * 9 + k, s);
+        else if (a.dbias) atomicAdd(a.dbias + c, s);
+    }
+}
 
 // first element of plane `plane_id` = b * d + c of x / dx (the other tensors are packed)
 __device__ __forceinline__ long x_plane_offset(const DwArgs& a, int plane_id) {
@@ -109,7 +122,8 @@ __global__ void __launch_bounds__(256) dwconv_silu_fwd_kernel(const DwArgs a) {
     }
 }
 
-__global__ void __launch_bounds__(256) dwconv_silu_bwd1_kernel(const DwArgs a) {
+template <bool DET>
+__device__ __forceinline__ void dwconv_silu_bwd1_body(const DwArgs& a) {
     __shared__ float tile[kTile][kTile + 1];
     __shared__ float red[4][10];
     const int H = a.H, W = a.W;
@@ -173,10 +187,13 @@ __global__ void __launch_bounds__(256) dwconv_silu_bwd1_kernel(const DwArgs a) {
     __syncthreads();
     if (threadIdx.x < 10) {
         const float s = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        if (threadIdx.x < 9) atomicAdd(a.dw + c * 9 + threadIdx.x, s);
-        else if (a.dbias) atomicAdd(a.dbias + c, s);
+        dw_leave<DET>(a, c, b * (tw * th) + tile_id, threadIdx.x, s);
     }
 }
+
+__global__ void __launch_bounds__(256) dwconv_silu_bwd1_kernel(const DwArgs a) { dwconv_silu_bwd1_body<false>(a); }
+// deterministic mode (SIGMA_DWCONV_DETERMINISTIC): the sums go to a.part, dwconv_reduce_kernel adds them
+__global__ void __launch_bounds__(256) dwconv_silu_bwd1_det_kernel(const DwArgs a) { dwconv_silu_bwd1_body<true>(a); }
 
 __global__ void __launch_bounds__(256) dwconv_bwd2_kernel(const DwArgs a) {
     const int H = a.H, W = a.W;
@@ -262,7 +279,8 @@ __global__ void __launch_bounds__(256) dwconv_silu_fwd_plane_kernel(const DwArgs
     for (int idx = tid; idx < L; idx += 256) { const int w = idx / H, h = idx - w * H; o_cm[idx] = sOut[h * pitch + w]; }
 }
 
-__global__ void __launch_bounds__(256) dwconv_silu_bwd_plane_kernel(const DwArgs a) {
+template <bool DET>
+__device__ __forceinline__ void dwconv_silu_bwd_plane_body(const DwArgs& a) {
     extern __shared__ float smem[];
     __shared__ float red[4][10];
     const int H = a.H, W = a.W, L = H * W, pitch = plane_pitch(W);
@@ -338,8 +356,22 @@ __global__ void __launch_bounds__(256) dwconv_silu_bwd_plane_kernel(const DwArgs
     __syncthreads();
     if (tid < 10) {
         const float s = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-        if (tid < 9) atomicAdd(a.dw + c * 9 + tid, s);
-        else if (a.dbias) atomicAdd(a.dbias + c, s);
+        dw_leave<DET>(a, c, b, tid, s);
+    }
+}
+
+__global__ void __launch_bounds__(256) dwconv_silu_bwd_plane_kernel(const DwArgs a) { dwconv_silu_bwd_plane_body<false>(a); }
+__global__ void __launch_bounds__(256) dwconv_silu_bwd_plane_det_kernel(const DwArgs a) { dwconv_silu_bwd_plane_body<true>(a); }
+
+// deterministic mode: dweight / dbias = the sums of the `slots` workgroup slots of a.part, slot 0 first (fixed order)
+__global__ void __launch_bounds__(256) dwconv_reduce_kernel(const DwArgs a, int slots) {
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < a.d * 10; e += gridDim.x * blockDim.x) {
+        const int c = e / 10, k = e - c * 10;
+        if (k == 9 && !a.dbias) continue;
+        float acc = 0.0f;
+        for (int sl = 0; sl < slots; ++sl) acc += a.part[(long)sl * a.d * 10 + e];
+        if (k < 9) a.dw[c * 9 + k] = acc;
+        else a.dbias[c] = acc;
     }
 }
 
@@ -352,6 +384,7 @@ size_t plane_lds_bytes(const sigma_dwconv_params* p) {
 
 int check(const sigma_dwconv_params* p) {
     if (!p) return SIGMA_OPS_ERR_ARG;
+    if (p->flags & ~SIGMA_DWCONV_DETERMINISTIC) return SIGMA_OPS_ERR_ARG;
     if (p->batch < 0 || p->channels <= 0 || p->height <= 0 || p->width <= 0) return SIGMA_OPS_ERR_ARG;
     if (p->n_orders != 1 && p->n_orders != 2) return SIGMA_OPS_ERR_ARG;
     const long tiles = (long)((p->width + kTile - 1) / kTile) * ((p->height + kTile - 1) / kTile);
@@ -362,6 +395,12 @@ int check(const sigma_dwconv_params* p) {
 dim3 grid_for(const sigma_dwconv_params* p) {
     const long tiles = (long)((p->width + kTile - 1) / kTile) * ((p->height + kTile - 1) / kTile);
     return dim3((unsigned)(tiles * p->batch * p->channels));
+}
+
+// workgroup slots of the deterministic backward: one per (batch, spatial tile) and channel (whole-plane kernel: one tile)
+long det_slots(const sigma_dwconv_params* p) {
+    const long tiles = plane_lds_bytes(p) ? 1 : (long)((p->width + kTile - 1) / kTile) * ((p->height + kTile - 1) / kTile);
+    return tiles * p->batch;
 }
 
 }  // namespace
@@ -398,25 +437,51 @@ int sigma_dwconv3x3_silu_fwd(const sigma_dwconv_params* p, void* stream) {
     return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
 }
 
+int64_t sigma_dwconv3x3_silu_bwd_workspace_bytes(const sigma_dwconv_params* p) {
+    if (sigma::check(p)) return -1;
+    if (!(p->flags & SIGMA_DWCONV_DETERMINISTIC)) return 0;
+    return (int64_t)sigma::det_slots(p) * p->channels * 10 * (int64_t)sizeof(float);
+}
+
 int sigma_dwconv3x3_silu_bwd(const sigma_dwconv_params* p, void* stream) {
     int rc = sigma::check(p);
     if (rc) return rc;
-    if (p->batch == 0) return SIGMA_OPS_OK;
+    if (p->batch == 0) {
+        // deterministic mode: dweight / dbias are written -- with no batch, as zeros
+        if (!(p->flags & SIGMA_DWCONV_DETERMINISTIC)) return SIGMA_OPS_OK;
+        if (!p->dweight) return SIGMA_OPS_ERR_ARG;
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        hipError_t e = hipMemsetAsync(p->dweight, 0, (size_t)p->channels * 9 * sizeof(float), s);
+        if (e == hipSuccess && p->dbias) e = hipMemsetAsync(p->dbias, 0, (size_t)p->channels * sizeof(float), s);
+        return e == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    }
     if (!p->x || !p->weight || !p->g2 || !p->gpre || !p->dweight || !p->dx) return SIGMA_OPS_ERR_ARG;
+    const bool det = (p->flags & SIGMA_DWCONV_DETERMINISTIC) != 0;
+    const int64_t need = sigma_dwconv3x3_silu_bwd_workspace_bytes(p);
+    if (det && (!p->workspace || p->workspace_bytes < need || (reinterpret_cast<uintptr_t>(p->workspace) & 15u))) return SIGMA_OPS_ERR_ARG;
     sigma::DwArgs a{};
     a.x = p->x; a.w = p->weight; a.bias = p->bias; a.g2 = p->g2; a.gpre = p->gpre;
     a.dw = p->dweight; a.dbias = p->dbias; a.dx = p->dx;
     a.B = p->batch; a.d = p->channels; a.H = p->height; a.W = p->width; a.orders = p->n_orders;
+    a.part = det ? static_cast<float*>(p->workspace) : nullptr;
     if (!sigma::plane_strides(p, a)) return SIGMA_OPS_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (const size_t lds = sigma::plane_lds_bytes(p)) {      // one launch, gpre stays in LDS (p->gpre is not written)
-        hipLaunchKernelGGL(sigma::dwconv_silu_bwd_plane_kernel, dim3((unsigned)(p->batch * p->channels)), dim3(256), lds, s, a);
-        return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+        hipLaunchKernelGGL(det ? sigma::dwconv_silu_bwd_plane_det_kernel : sigma::dwconv_silu_bwd_plane_kernel,
+                           dim3((unsigned)(p->batch * p->channels)), dim3(256), lds, s, a);
+        if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+    } else {
+        hipLaunchKernelGGL(det ? sigma::dwconv_silu_bwd1_det_kernel : sigma::dwconv_silu_bwd1_kernel, sigma::grid_for(p), dim3(256), 0, s, a);
+        if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+        hipLaunchKernelGGL(sigma::dwconv_bwd2_kernel, sigma::grid_for(p), dim3(256), 0, s, a);
+        if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(sigma::dwconv_silu_bwd1_kernel, sigma::grid_for(p), dim3(256), 0, s, a);
-    if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
-    hipLaunchKernelGGL(sigma::dwconv_bwd2_kernel, sigma::grid_for(p), dim3(256), 0, s, a);
-    return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    if (det) {
+        const int blocks = (p->channels * 10 + 255) / 256;
+        hipLaunchKernelGGL(sigma::dwconv_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, (int)sigma::det_slots(p));
+        if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+    }
+    return SIGMA_OPS_OK;
 }
 
 }  // extern "C"

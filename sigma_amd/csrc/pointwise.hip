@@ -288,9 +288,11 @@ bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // whole kernel (chunk = tid % (C / 4), row slot = tid / (C / 4); 256 / (C / 4) rows per block iteration), so its part of
 // ds lives in four registers; the row slots of a block meet in LDS and one thread per chunk adds the block's sum to ds
 // (float atomics: grid x C / 4 of them).  C % 4 == 0, C <= 1024.
-__global__ void __launch_bounds__(256) colscale_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                           const float* __restrict__ s, float* __restrict__ dx,
-                                                           float* __restrict__ ds, long rows, int C) {
+// DET (sigma_colscale_bwd_ws): the block's sum is stored to row blockIdx.x of `ds` = the workspace instead.
+template <bool DET>
+__device__ __forceinline__ void colscale_bwd_body(const float* __restrict__ dy, const float* __restrict__ x,
+                                                  const float* __restrict__ s, float* __restrict__ dx,
+                                                  float* __restrict__ ds, long rows, int C) {
     extern __shared__ float part[];                       // [slots][C]
     const int chunks = C >> 2;
     const int slots = 256 / chunks;
@@ -313,8 +315,46 @@ __global__ void __launch_bounds__(256) colscale_bwd_kernel(const float* __restri
             const float4 o = *reinterpret_cast<const float4*>(part + k * C + 4 * ch);
             t.x += o.x; t.y += o.y; t.z += o.z; t.w += o.w;
         }
-        atomicAdd(ds + 4 * ch, t.x); atomicAdd(ds + 4 * ch + 1, t.y); atomicAdd(ds + 4 * ch + 2, t.z); atomicAdd(ds + 4 * ch + 3, t.w);
+        if constexpr (DET) *reinterpret_cast<float4*>(ds + (long)blockIdx.x * C + 4 * ch) = t;
+        else { atomicAdd(ds + 4 * ch, t.x); atomicAdd(ds + 4 * ch + 1, t.y); atomicAdd(ds + 4 * ch + 2, t.z); atomicAdd(ds + 4 * ch + 3, t.w); }
     }
+}
+
+__global__ void __launch_bounds__(256) colscale_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                           const float* __restrict__ s, float* __restrict__ dx,
+                                                           float* __restrict__ ds, long rows, int C) {
+    colscale_bwd_body<false>(dy, x, s, dx, ds, rows, C);
+}
+
+__global__ void __launch_bounds__(256) colscale_bwd_part_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                const float* __restrict__ s, float* __restrict__ dx,
+                                                                float* __restrict__ ws, long rows, int C) {
+    colscale_bwd_body<true>(dy, x, s, dx, ws, rows, C);
+}
+
+// ds[c] = sum over the `blocks` rows of ws in a fixed order: thread (x, y) of a 64 x 16 block adds the rows y, y + 16, ...
+// of column blockIdx.x * 64 + x, then the 16 partial sums meet in LDS and are added y = 0 .. 15
+__global__ void __launch_bounds__(1024) colscale_reduce_kernel(const float* __restrict__ ws, float* __restrict__ ds, int blocks, int C) {
+    __shared__ float part[16][64];
+    const int x = threadIdx.x & 63, y = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + x;
+    float acc = 0.0f;
+    if (c < C)
+        for (int b = y; b < blocks; b += 16) acc += ws[(long)b * C + c];
+    part[y][x] = acc;
+    __syncthreads();
+    if (y == 0 && c < C) {
+        float t = part[0][x];
+        for (int k = 1; k < 16; ++k) t += part[k][x];
+        ds[c] = t;
+    }
+}
+
+// blocks of the colscale backward (two workgroups per CU: every block ends with C atomics on the same C addresses)
+long colscale_grid(long rows, int channels) {
+    const int slots = 256 / (channels / 4);
+    long grid = (rows + slots - 1) / slots;
+    return grid > 512 ? 512 : grid;
 }
 
 unsigned stream_grid(long work_items) {
@@ -372,6 +412,31 @@ int sigma_colscale_bwd(const float* dy, const float* x, const float* scale, floa
     if (grid > 512) grid = 512;                       // two workgroups per CU: every block ends with C atomics on the same C addresses
     hipLaunchKernelGGL(sigma::colscale_bwd_kernel, dim3((unsigned)grid), dim3(256), (size_t)slots * channels * sizeof(float),
                        static_cast<hipStream_t>(stream), dy, x, scale, dx, dscale, (long)rows, (int)channels);
+    return sigma::done();
+}
+
+int64_t sigma_colscale_bwd_workspace_bytes(int64_t rows, int32_t channels) {
+    if (rows < 0 || channels <= 0 || channels % 4 != 0 || channels > 1024) return -1;
+    return (int64_t)sigma::colscale_grid((long)rows, channels) * channels * (int64_t)sizeof(float);
+}
+
+int sigma_colscale_bwd_ws(const float* dy, const float* x, const float* scale, float* dx, float* dscale, int64_t rows, int32_t channels,
+                          void* workspace, int64_t workspace_bytes, void* stream) {
+    if (rows < 0 || channels <= 0 || channels % 4 != 0 || channels > 1024) return SIGMA_OPS_ERR_ARG;
+    if (!dscale) return SIGMA_OPS_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (rows == 0) return hipMemsetAsync(dscale, 0, (size_t)channels * sizeof(float), st) == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    if (!dy || !x || !scale || !dx) return SIGMA_OPS_ERR_ARG;
+    if (!sigma::al16(dy) || !sigma::al16(x) || !sigma::al16(scale) || !sigma::al16(dx)) return SIGMA_OPS_ERR_ARG;
+    if (!workspace || !sigma::al16(workspace) || workspace_bytes < sigma_colscale_bwd_workspace_bytes(rows, channels)) return SIGMA_OPS_ERR_ARG;
+    const int slots = 256 / (channels / 4);
+    const long grid = sigma::colscale_grid((long)rows, channels);
+    float* ws = static_cast<float*>(workspace);
+    hipLaunchKernelGGL(sigma::colscale_bwd_part_kernel, dim3((unsigned)grid), dim3(256), (size_t)slots * channels * sizeof(float),
+                       st, dy, x, scale, dx, ws, (long)rows, (int)channels);
+    if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+    hipLaunchKernelGGL(sigma::colscale_reduce_kernel, dim3((unsigned)((channels + 63) / 64)), dim3(1024), 0, st, ws, dscale,
+                       (int)grid, (int)channels);
     return sigma::done();
 }
 

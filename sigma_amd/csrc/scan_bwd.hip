@@ -59,7 +59,7 @@ __device__ __forceinline__ void stage_tile(float* __restrict__ dst, const io_t* 
 
 }  // namespace
 
-template <typename io_t, int T, bool GLDS, bool REV>
+template <typename io_t, int T, bool GLDS, bool REV, bool DET = false>
 __device__ __forceinline__ void scan_bwd_body(const BwdArgs& q, float* smem, int b, int row0, int g) {
     constexpr int TILE = 64 * T;
     constexpr int TPSMAX = kCkptPitch / TILE;         // LDS sizing: tiles per span at the default pitch
@@ -385,12 +385,13 @@ __device__ __forceinline__ void scan_bwd_body(const BwdArgs& q, float* smem, int
 
     dD_acc = wave_sum(dD_acc);
     dbias_acc = wave_sum(dbias_acc);
+    // one contribution per (batch, row): slot b of the deterministic row partials
     if (lane == 0) {
-        if (q.dD) atomicAdd(q.dD + pr, dD_acc);
-        if (q.dbias) atomicAdd(q.dbias + pr, dbias_acc);
+        if (q.dD) row_result<DET>(&q, q.dD + pr, b, pr, N, true, dD_acc);
+        if (q.dbias) row_result<DET>(&q, q.dbias + pr, b, pr, N + 1, true, dbias_acc);
     }
     for (int n = lane; n < N; n += 64)
-        atomicAdd(q.dA + (long)pr * q.dA_ds + (long)n * q.dA_ns, sdA[wave * N + n]);
+        row_result<DET>(&q, q.dA + (long)pr * q.dA_ds + (long)n * q.dA_ns, b, pr, n, true, sdA[wave * N + n]);
 }
 
 // T = 10 keeps ~90 values per lane live (5 per-element accumulators + a, x, g*C per state): it
@@ -411,18 +412,33 @@ scan_bwd_kernel(const BwdArgs q) {
     else scan_bwd_body<io_t, T, GLDS, false>(q, smem, b, row0, g);
 }
 
+// deterministic mode (SIGMA_SCAN_BWD_DETERMINISTIC): the same backward with its per-row results stored to q.rpart
+template <typename io_t, int T, bool GLDS>
+__global__ void __launch_bounds__(64 * bwd_max_waves<T>::value)
+scan_bwd_det_kernel(const BwdArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int R = blockDim.x >> 6;
+    const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
+    const int b = lb / q.f.rowblocks;
+    const int rb = lb - b * q.f.rowblocks;
+    const int row0 = rb * R;
+    const int g = row0 / q.f.rows_per_group;
+    if ((q.f.rev_mask >> g) & 1u) scan_bwd_body<io_t, T, GLDS, true, true>(q, smem, b, row0, g);
+    else scan_bwd_body<io_t, T, GLDS, false, true>(q, smem, b, row0, g);
+}
+
 // out[b, g, n, l] = sum_p ws[p][b][g][n][l]   (deterministic order; 4 elements per thread).
 // L % 4 == 0 (VEC): the four elements share (b, g, n), so the index is decomposed once per float4 -- in 32-bit
 // arithmetic, the 64-bit divisions of the first version cost more than the memory traffic (63 us for 98 MB at P = 4)
 // -- and the sum leaves as one 16-byte store when the destination rows are 16-byte aligned (OVEC).
+// Blocks [0, nblk) of the grid (blk = this one) share the elements.
 template <bool VEC, bool OVEC>
-__global__ void __launch_bounds__(256)
-reduce_partials_kernel(const float* __restrict__ wsB, const float* __restrict__ wsC, float* __restrict__ dB,
-                       float* __restrict__ dC, int P, int batch, int G, int N, int L, long dB_bs, long dB_gs,
-                       long dB_ns, long dC_bs, long dC_gs, long dC_ns) {
+__device__ __forceinline__ void reduce_partials_body(const float* __restrict__ wsB, const float* __restrict__ wsC, float* __restrict__ dB,
+                                                     float* __restrict__ dC, int P, int batch, int G, int N, int L, long dB_bs,
+                                                     long dB_gs, long dB_ns, long dC_bs, long dC_gs, long dC_ns, int blk, int nblk) {
     const long per = (long)batch * G * N * L;
     const long nvec = (per + 3) / 4;
-    for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (long)gridDim.x * blockDim.x) {
+    for (long v = (long)blk * blockDim.x + threadIdx.x; v < nvec; v += (long)nblk * blockDim.x) {
         const long e0 = v * 4;
         float accB[4] = {0.f, 0.f, 0.f, 0.f}, accC[4] = {0.f, 0.f, 0.f, 0.f};
         if (VEC) {
@@ -467,6 +483,39 @@ reduce_partials_kernel(const float* __restrict__ wsB, const float* __restrict__ 
     }
 }
 
+template <bool VEC, bool OVEC>
+__global__ void __launch_bounds__(256)
+reduce_partials_kernel(const float* __restrict__ wsB, const float* __restrict__ wsC, float* __restrict__ dB,
+                       float* __restrict__ dC, int P, int batch, int G, int N, int L, long dB_bs, long dB_gs,
+                       long dB_ns, long dC_bs, long dC_gs, long dC_ns) {
+    reduce_partials_body<VEC, OVEC>(wsB, wsC, dB, dC, P, batch, G, N, L, dB_bs, dB_gs, dB_ns, dC_bs, dC_gs, dC_ns,
+                                    (int)blockIdx.x, (int)gridDim.x);
+}
+
+// Deterministic backward: blocks [0, bc_blocks) = reduce_partials_body (dB / dC over the P slabs, when P > 1); the others
+// write dA, dD, ddelta_bias as the sums of the a.rpart_K per-row slots, slot 0 first (fixed order).
+template <bool VEC, bool OVEC>
+__global__ void __launch_bounds__(256)
+reduce_partials_det_kernel(const BwdArgs a, int bc_blocks) {
+    if ((int)blockIdx.x < bc_blocks) {
+        reduce_partials_body<VEC, OVEC>(a.ws_dB, a.ws_dC, a.dB, a.dC, a.P, a.f.batch, a.f.G, a.f.N, a.f.L, a.dB_bs, a.dB_gs,
+                                        a.dB_ns, a.dC_bs, a.dC_gs, a.dC_ns, (int)blockIdx.x, bc_blocks);
+        return;
+    }
+    const int cols = a.f.N + 2;
+    const long per = (long)a.f.dim * cols;
+    const long nthr = (long)((int)gridDim.x - bc_blocks) * blockDim.x;
+    for (long e = (long)((int)blockIdx.x - bc_blocks) * blockDim.x + threadIdx.x; e < per; e += nthr) {
+        const int pr = (int)(e / cols), col = (int)(e - (long)pr * cols);
+        float* dst = col < a.f.N ? a.dA + (long)pr * a.dA_ds + (long)col * a.dA_ns : col == a.f.N ? (a.dD ? a.dD + pr : nullptr)
+                                                                                                : (a.dbias ? a.dbias + pr : nullptr);
+        if (!dst) continue;
+        float acc = 0.0f;
+        for (int k = 0; k < a.rpart_K; ++k) acc += a.rpart[k * per + e];
+        *dst = acc;
+    }
+}
+
 hipError_t launch_reduce_partials(const BwdArgs& a, hipStream_t stream) {
     const long per = (long)a.f.batch * a.f.G * a.f.N * a.f.L;
     long blocks = (per / 4 + 255) / 256;
@@ -483,16 +532,48 @@ hipError_t launch_reduce_partials(const BwdArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// the reduce pass of a deterministic backward: dB / dC (when P > 1) and the per-row slots in ONE launch
+hipError_t launch_reduce_det(const BwdArgs& a, hipStream_t stream) {
+    long bc = 0;
+    if (a.P > 1) {
+        const long per = (long)a.f.batch * a.f.G * a.f.N * a.f.L;
+        bc = (per / 4 + 255) / 256;
+        if (bc > 4096) bc = 4096;
+        if (bc < 1) bc = 1;
+    }
+    long rows = ((long)a.f.dim * (a.f.N + 2) + 255) / 256;
+    if (rows > 1024) rows = 1024;
+    const bool vec = (a.f.L & 3) == 0 && (long)a.f.batch * a.f.G * a.f.N < (1L << 31);
+    const bool ovec = vec && a.out_vec_ok != 0;
+    const dim3 grid((unsigned)(bc + rows));
+    if (ovec) hipLaunchKernelGGL((reduce_partials_det_kernel<true, true>), grid, dim3(256), 0, stream, a, (int)bc);
+    else if (vec) hipLaunchKernelGGL((reduce_partials_det_kernel<true, false>), grid, dim3(256), 0, stream, a, (int)bc);
+    else hipLaunchKernelGGL((reduce_partials_det_kernel<false, false>), grid, dim3(256), 0, stream, a, (int)bc);
+    return hipGetLastError();
+}
+
+// after a backward kernel: the dB / dC slab sum, and in deterministic mode (a.rpart) the per-row slots with it
+hipError_t launch_reduce_after(const BwdArgs& a, hipStream_t stream) {
+    if (a.rpart) return launch_reduce_det(a, stream);
+    return a.P == 1 ? hipSuccess : launch_reduce_partials(a, stream);
+}
+
 template <typename io_t, int T, bool GLDS>
 static hipError_t launch_bwd_t(const BwdArgs& a, hipStream_t stream) {
     const size_t lds = bwd_lds_bytes(T, a.f.R, a.f.NB, a.f.N, a.slab2 != 0);
     const int grid = a.f.rowblocks * a.f.batch;
-    constexpr auto kern = scan_bwd_kernel<io_t, T, GLDS>;
-    if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
+    if (a.rpart) {
+        constexpr auto kern = scan_bwd_det_kernel<io_t, T, GLDS>;
+        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
+    } else {
+        constexpr auto kern = scan_bwd_kernel<io_t, T, GLDS>;
+        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
+    }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess || a.P == 1) return e;
-    return launch_reduce_partials(a, stream);
+    if (e != hipSuccess) return e;
+    return launch_reduce_after(a, stream);
 }
 
 template <typename io_t, bool GLDS>

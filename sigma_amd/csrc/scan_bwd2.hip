@@ -163,7 +163,7 @@ __device__ __forceinline__ float2 colsum(const float* __restrict__ colp, int str
 
 }  // namespace
 
-template <typename io_t, int T, bool GLDS, bool REV>
+template <typename io_t, int T, bool GLDS, bool REV, bool DET>
 __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, int b, int g, int chunk) {
     constexpr int TILE = 64 * T;
     constexpr int VW = vec_width<T>::value;
@@ -436,7 +436,7 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
             const io_t* __restrict__ d_row2 = reinterpret_cast<const io_t*>(ke->f.delta) + (long)b * ke->f.dt_bs + (long)r * ke->f.dt_ds;
             if (lane < N) {
                 sRv[rl * N + lane] = rvout_v;
-                atomicAdd(ke->dA + (long)pr * ke->dA_ds + (long)lane * ke->dA_ns, dA_v);
+                row_result<DET>(ke, ke->dA + (long)pr * ke->dA_ds + (long)lane * ke->dA_ns, b, pr, lane, j == ntiles - 1, dA_v);
             }
             float duv[T], ddv[T];
             float dD_acc = 0.0f, dbias_acc = 0.0f;
@@ -465,38 +465,57 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
             io_t* __restrict__ dd_row = reinterpret_cast<io_t*>(ke->ddelta) + (long)b * ke->dd_bs + (long)r * ke->dd_ds;
             store_items<io_t, T, REV>(du_row, lbase, L, vec, duv);
             store_items<io_t, T, REV>(dd_row, lbase, L, vec, ddv);
-            if (ke->dD) { dD_acc = wave_sum(dD_acc); if (lane0) atomicAdd(ke->dD + pr, dD_acc); }
-            if (ke->dbias) { dbias_acc = wave_sum(dbias_acc); if (lane0) atomicAdd(ke->dbias + pr, dbias_acc); }
+            if (ke->dD) { dD_acc = wave_sum(dD_acc); if (lane0) row_result<DET>(ke, ke->dD + pr, b, pr, N, j == ntiles - 1, dD_acc); }
+            if (ke->dbias) { dbias_acc = wave_sum(dbias_acc); if (lane0) row_result<DET>(ke, ke->dbias + pr, b, pr, N + 1, j == ntiles - 1, dbias_acc); }
             PROF(8)                                            // row epilogue
         }
     }
     PROF_FLUSH
 }
 
-template <typename io_t, int T, bool GLDS, int MAXW>
-__global__ void __launch_bounds__(64 * MAXW)
-scan_bwd2_kernel(const BwdArgs q) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
+template <typename io_t, int T, bool GLDS, bool DET>
+__device__ __forceinline__ void scan_bwd2_entry(const BwdArgs& q, float* smem) {
     const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
     const int per_b = q.f.G * q.P;                    // workgroups per batch entry
     const int b = lb / per_b;
     const int rem = lb - b * per_b;
     const int g = rem / q.P;
     const int chunk = rem - g * q.P;
-    if ((q.f.rev_mask >> g) & 1u) scan_bwd2_body<io_t, T, GLDS, true>(q, smem, b, g, chunk);
-    else scan_bwd2_body<io_t, T, GLDS, false>(q, smem, b, g, chunk);
+    if ((q.f.rev_mask >> g) & 1u) scan_bwd2_body<io_t, T, GLDS, true, DET>(q, smem, b, g, chunk);
+    else scan_bwd2_body<io_t, T, GLDS, false, DET>(q, smem, b, g, chunk);
+}
+
+template <typename io_t, int T, bool GLDS, int MAXW>
+__global__ void __launch_bounds__(64 * MAXW)
+scan_bwd2_kernel(const BwdArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    scan_bwd2_entry<io_t, T, GLDS, false>(q, smem);
+}
+
+// deterministic mode (SIGMA_SCAN_BWD_DETERMINISTIC): the per-row results go to the workgroup's slot of q.rpart
+template <typename io_t, int T, bool GLDS, int MAXW>
+__global__ void __launch_bounds__(64 * MAXW)
+scan_bwd2_det_kernel(const BwdArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    scan_bwd2_entry<io_t, T, GLDS, true>(q, smem);
 }
 
 template <typename io_t, int T, bool GLDS, int MAXW>
 static hipError_t launch_bwd2_t(const BwdArgs& a, hipStream_t stream) {
     const size_t lds = bwd2_lds_bytes(T, a.f.R, a.f.NB, a.f.N, a.slab2 != 0, a.RB);
     const int grid = a.f.batch * a.f.G * a.P;
-    constexpr auto kern = scan_bwd2_kernel<io_t, T, GLDS, MAXW>;
-    if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
+    if (a.rpart) {
+        constexpr auto kern = scan_bwd2_det_kernel<io_t, T, GLDS, MAXW>;
+        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
+    } else {
+        constexpr auto kern = scan_bwd2_kernel<io_t, T, GLDS, MAXW>;
+        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
+    }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess || a.P == 1) return e;
-    return launch_reduce_partials(a, stream);
+    if (e != hipSuccess) return e;
+    return launch_reduce_after(a, stream);
 }
 
 template <typename io_t, int T, bool GLDS>

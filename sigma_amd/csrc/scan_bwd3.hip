@@ -72,7 +72,7 @@ __device__ __forceinline__ void stage_tile3(float* __restrict__ dst, const io_t*
 
 }  // namespace
 
-template <typename io_t, bool GLDS, bool REV>
+template <typename io_t, bool GLDS, bool REV, bool DET>
 __device__ __forceinline__ void scan_bwd3_body(const BwdArgs& q, float* smem, int b, int g, int chunk) {
     constexpr int T = kT3;
     constexpr int TILE = kTile3;
@@ -240,7 +240,7 @@ __device__ __forceinline__ void scan_bwd3_body(const BwdArgs& q, float* smem, in
             cold_args3_t ke = cold_args3();
             if (lane < 4) {
                 sRv[rl * N + nq0 + lane] = rvout_v;
-                atomicAdd(ke->dA + (long)pr * ke->dA_ds + (long)(nq0 + lane) * ke->dA_ns, dA_v);
+                row_result<DET>(ke, ke->dA + (long)pr * ke->dA_ds + (long)(nq0 + lane) * ke->dA_ns, b, pr, nq0 + lane, j == ntiles - 1, dA_v);
             }
             // ---- sum over the row's Q waves, then one of them finishes the row
             bool duty = true;
@@ -249,7 +249,8 @@ __device__ __forceinline__ void scan_bwd3_body(const BwdArgs& q, float* smem, in
 #pragma unroll
                 for (int k = 0; k < T; ++k) { mine[k] = psx[k]; mine[TILE + k] = psa[k]; }
                 lds_barrier();
-                duty = quad == (step % Q);
+                // deterministic mode: the same wave finishes the row in every tile (it reads back its own slot)
+                duty = quad == (DET ? 0 : step % Q);
                 if (duty) {
                     // all reads of the Q partials in flight before the first add (Q <= 4)
                     const float* src0 = sPart + ((par * nw + slot * Q) * 2) * TILE + lane * T;
@@ -297,8 +298,8 @@ __device__ __forceinline__ void scan_bwd3_body(const BwdArgs& q, float* smem, in
                 io_t* __restrict__ dd_row = reinterpret_cast<io_t*>(ke->ddelta) + (long)b * ke->dd_bs + (long)r * ke->dd_ds;
                 store_items<io_t, T, REV>(du_row, lbase, L, vec, duv);
                 store_items<io_t, T, REV>(dd_row, lbase, L, vec, ddv);
-                if (ke->dD) { dD_acc = wave_sum(dD_acc); if (lane0) atomicAdd(ke->dD + pr, dD_acc); }
-                if (ke->dbias) { dbias_acc = wave_sum(dbias_acc); if (lane0) atomicAdd(ke->dbias + pr, dbias_acc); }
+                if (ke->dD) { dD_acc = wave_sum(dD_acc); if (lane0) row_result<DET>(ke, ke->dD + pr, b, pr, N, j == ntiles - 1, dD_acc); }
+                if (ke->dbias) { dbias_acc = wave_sum(dbias_acc); if (lane0) row_result<DET>(ke, ke->dbias + pr, b, pr, N + 1, j == ntiles - 1, dbias_acc); }
             }
         }
 
@@ -344,18 +345,31 @@ __device__ __forceinline__ void scan_bwd3_body(const BwdArgs& q, float* smem, in
 }
 
 // MAXW = 16: 128-VGPR budget (4 waves per SIMD); MAXW = 12: 168 VGPRs (3 waves per SIMD, no spills)
-template <typename io_t, bool GLDS, int MAXW>
-__global__ void __launch_bounds__(64 * MAXW)
-scan_bwd3_kernel(const BwdArgs q) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
+template <typename io_t, bool GLDS, bool DET>
+__device__ __forceinline__ void scan_bwd3_entry(const BwdArgs& q, float* smem) {
     const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
     const int per_b = q.f.G * q.P;
     const int b = lb / per_b;
     const int rem = lb - b * per_b;
     const int g = rem / q.P;
     const int chunk = rem - g * q.P;
-    if ((q.f.rev_mask >> g) & 1u) scan_bwd3_body<io_t, GLDS, true>(q, smem, b, g, chunk);
-    else scan_bwd3_body<io_t, GLDS, false>(q, smem, b, g, chunk);
+    if ((q.f.rev_mask >> g) & 1u) scan_bwd3_body<io_t, GLDS, true, DET>(q, smem, b, g, chunk);
+    else scan_bwd3_body<io_t, GLDS, false, DET>(q, smem, b, g, chunk);
+}
+
+template <typename io_t, bool GLDS, int MAXW>
+__global__ void __launch_bounds__(64 * MAXW)
+scan_bwd3_kernel(const BwdArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    scan_bwd3_entry<io_t, GLDS, false>(q, smem);
+}
+
+// deterministic mode (SIGMA_SCAN_BWD_DETERMINISTIC): the per-row results go to the workgroup's slot of q.rpart
+template <typename io_t, bool GLDS, int MAXW>
+__global__ void __launch_bounds__(64 * MAXW)
+scan_bwd3_det_kernel(const BwdArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    scan_bwd3_entry<io_t, GLDS, true>(q, smem);
 }
 
 template <typename io_t, bool GLDS, int MAXW>
@@ -363,12 +377,18 @@ static hipError_t launch_bwd3_w(const BwdArgs& a, hipStream_t stream) {
     const int nw = a.f.R;                                  // waves per workgroup = slots * Q
     const size_t lds = bwd3_lds_bytes(nw, a.f.N, a.RB);
     const int grid = a.f.batch * a.f.G * a.P;
-    constexpr auto kern = scan_bwd3_kernel<io_t, GLDS, MAXW>;
-    if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(nw * 64), lds, stream, a);
+    if (a.rpart) {
+        constexpr auto kern = scan_bwd3_det_kernel<io_t, GLDS, MAXW>;
+        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(nw * 64), lds, stream, a);
+    } else {
+        constexpr auto kern = scan_bwd3_kernel<io_t, GLDS, MAXW>;
+        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(nw * 64), lds, stream, a);
+    }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess || a.P == 1) return e;
-    return launch_reduce_partials(a, stream);
+    if (e != hipSuccess) return e;
+    return launch_reduce_after(a, stream);
 }
 
 template <typename io_t, bool GLDS>

@@ -95,7 +95,7 @@ __device__ __forceinline__ float colsum1(const float* __restrict__ colp, int str
 
 }  // namespace
 
-template <bool REV>
+template <bool REV, bool DET>
 __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, int b, int g, int chunk, int seg) {
     constexpr int T = kT4;
     const FwdArgs& p = q.f;
@@ -255,7 +255,8 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
             // dA / dD / ddelta_bias leave through one atomicAdd per (row, tile) and state.  Summing them over the
             // tiles in LDS first (measured: WRITE_SIZE -6 %) costs the second B/C image its LDS and 3 % run time.
 #if !(SIGMA_BWD4_ABL & 2)
-            if (kq->dD) { dD_acc = row_sum_to_lane0(dD_acc); if (li0) atomicAdd(kq->dD + pr, dD_acc); }
+            // (deterministic mode: a plain store to the workgroup's slot, slot k = b * S + seg, added to over the tiles)
+            if (kq->dD) { dD_acc = row_sum_to_lane0(dD_acc); if (li0) row_result<DET>(kq, kq->dD + pr, b * kq->S + seg, pr, N, j == t_hi - 1, dD_acc); }
 #endif
 
             PROF(1)                                            // row prologue: loads, softplus
@@ -430,7 +431,7 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
                 const int st = li_e - vshift;
                 sRv[rl_e * N + st] = rvout_v;
 #if !(SIGMA_BWD4_ABL & 2)
-                atomicAdd(ke->dA + (long)pr_e * ke->dA_ds + (long)st * ke->dA_ns, dA_v);
+                row_result<DET>(ke, ke->dA + (long)pr_e * ke->dA_ds + (long)st * ke->dA_ns, b * ke->S + seg, pr_e, st, j == t_hi - 1, dA_v);
 #endif
             }
             float dbias_acc = 0.0f;
@@ -491,7 +492,7 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
                 }
             }
 #if !(SIGMA_BWD4_ABL & 2)
-            if (ke->dbias) { dbias_acc = row_sum_to_lane0(dbias_acc); if (li_e == 0) atomicAdd(ke->dbias + pr_e, dbias_acc); }
+            if (ke->dbias) { dbias_acc = row_sum_to_lane0(dbias_acc); if (li_e == 0) row_result<DET>(ke, ke->dbias + pr_e, b * ke->S + seg, pr_e, N + 1, j == t_hi - 1, dbias_acc); }
 #else
             asm volatile("" :: "v"(dbias_acc), "v"(dA_v));
 #endif
@@ -503,10 +504,8 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
     PROF_FLUSH
 }
 
-template <int MAXW>
-__global__ void __launch_bounds__(64 * MAXW)
-scan_bwd4_kernel(const BwdArgs q) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
+template <bool DET>
+__device__ __forceinline__ void scan_bwd4_entry(const BwdArgs& q, float* smem) {
     const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
     const int PS = q.P * q.S;                         // workgroups per (batch, group): row chunks x sequence segments
     const int per_b = q.f.G * PS;
@@ -516,8 +515,23 @@ scan_bwd4_kernel(const BwdArgs q) {
     const int rem2 = rem - g * PS;
     const int chunk = rem2 / q.S;
     const int seg = rem2 - chunk * q.S;
-    if ((q.f.rev_mask >> g) & 1u) scan_bwd4_body<true>(q, smem, b, g, chunk, seg);
-    else scan_bwd4_body<false>(q, smem, b, g, chunk, seg);
+    if ((q.f.rev_mask >> g) & 1u) scan_bwd4_body<true, DET>(q, smem, b, g, chunk, seg);
+    else scan_bwd4_body<false, DET>(q, smem, b, g, chunk, seg);
+}
+
+template <int MAXW>
+__global__ void __launch_bounds__(64 * MAXW)
+scan_bwd4_kernel(const BwdArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    scan_bwd4_entry<false>(q, smem);
+}
+
+// deterministic mode (SIGMA_SCAN_BWD_DETERMINISTIC): the per-row results go to the workgroup's slot of q.rpart
+template <int MAXW>
+__global__ void __launch_bounds__(64 * MAXW)
+scan_bwd4_det_kernel(const BwdArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    scan_bwd4_entry<true>(q, smem);
 }
 
 // ---- reverse summaries of the sequence segments (S > 1) ----------------------------------------------------------
@@ -643,12 +657,18 @@ template <int MAXW>
 static hipError_t launch_bwd4_t(const BwdArgs& a, hipStream_t stream) {
     const size_t lds = bwd4_lds_bytes(a.f.R, a.f.N, a.slab2, a.RB, a.f.NB);
     const int grid = a.f.batch * a.f.G * a.P * a.S;
-    constexpr auto kern = scan_bwd4_kernel<MAXW>;
-    if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
+    if (a.rpart) {
+        constexpr auto kern = scan_bwd4_det_kernel<MAXW>;
+        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
+    } else {
+        constexpr auto kern = scan_bwd4_kernel<MAXW>;
+        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
+    }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess || a.P == 1) return e;
-    return launch_reduce_partials(a, stream);
+    if (e != hipSuccess) return e;
+    return launch_reduce_after(a, stream);
 }
 
 // the pre-pass of the sequence split: W4 = waves per workgroup (<= 8) over the same rows, one workgroup per segment 1..S-1

@@ -182,7 +182,7 @@ __device__ __forceinline__ v4f rl_load4u(const float* __restrict__ row, int off,
 // over by the workgroup that walked the steps above (cin 2: chained walk); cout: this piece hands its carry on.
 struct RlPiece { int b, g, rbg, st_lo, st_hi, cin, cout, seg; };
 
-template <int NS, bool REV>
+template <int NS, bool REV, bool DET = false>
 __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, const RlPiece pc) {
     constexpr int T = kRT, H = kRT / 2;
     // wave-uniform by construction (block index arithmetic); said explicitly, because integer divisions are expanded on
@@ -781,17 +781,19 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
     }
     if (touch_acc == 1.2345678e-30f) du_blk[0] = touch_acc;        // keeps the touches alive (never true in practice)
 
-    // per-row results: one atomicAdd per (row, state) / row and workgroup (several workgroups only with segments)
+    // per-row results: one atomicAdd per (row, state) / row and workgroup (several workgroups only with segments);
+    // deterministic mode (MODE 3): one store each into slot b * S + seg of the row partials
+    const int rk = b * q.S + seg;
 #pragma unroll
-    for (int s = 0; s < NS; ++s) atomicAdd(q.dA + (long)pr_ln * q.dA_ds + (long)(n0 + s) * q.dA_ns, dAacc[s]);
+    for (int s = 0; s < NS; ++s) row_result<DET>(&q, q.dA + (long)pr_ln * q.dA_ds + (long)(n0 + s) * q.dA_ns, rk, pr_ln, n0 + s, true, dAacc[s]);
     // the four chunk threads of a row are neighbouring lanes
     dD_acc += dpp_take<0xB1, 0xF>(0.0f, dD_acc);                    // quad_perm [1,0,3,2]
     dD_acc += dpp_take<0x4E, 0xF>(0.0f, dD_acc);                    // quad_perm [2,3,0,1]
     dbias_acc += dpp_take<0xB1, 0xF>(0.0f, dbias_acc);
     dbias_acc += dpp_take<0x4E, 0xF>(0.0f, dbias_acc);
     if (cc == 0) {
-        if (q.dD) atomicAdd(q.dD + pr_rc, dD_acc);
-        if (q.dbias) atomicAdd(q.dbias + pr_rc, dbias_acc);
+        if (q.dD) row_result<DET>(&q, q.dD + pr_rc, rk, pr_rc, N, true, dD_acc);
+        if (q.dbias) row_result<DET>(&q, q.dbias + pr_rc, rk, pr_rc, N + 1, true, dbias_acc);
     }
 }
 
@@ -889,7 +891,8 @@ __device__ __forceinline__ void scan_bwdr_summary_body(const BwdArgs& q, float* 
         sm[(((long)(seg - 1) * p.batch * (p.dim >> 6) + rowblock) * N + n0 + s) * 64 + lane] = make_float2(fast_exp2(Pacc[s]), ecar[s]);
 }
 
-// MODE 0: the backward proper; MODE 1: the summaries of segments 1 .. S-1; MODE 2: the backward as a chained walk.
+// MODE 0: the backward proper; MODE 1: the summaries of segments 1 .. S-1; MODE 2: the backward as a chained walk;
+// MODE 3: the backward proper in deterministic mode (per-row results stored to the slots of q.rpart, no atomics).
 // Waves per SIMD the register allocation is sized for: the 64 KB of LDS of the backward proper (bwdr_lds_bytes) admit two
 // workgroups per CU = 2 waves per SIMD = 256 VGPRs; asking for 3 (round 4) capped the 16-state build at 168 VGPRs with 81
 // spilled to scratch for an occupancy the LDS never allowed.
@@ -958,8 +961,8 @@ scan_bwdr_kernel(const BwdArgs q) {
         pc.st_lo = q.S > 1 ? seg * q.seg_tiles : 0;
         pc.st_hi = q.S > 1 ? (pc.st_lo + q.seg_tiles < ntiles ? pc.st_lo + q.seg_tiles : ntiles) : ntiles;
         pc.cin = q.S > 1 ? 1 : 0; pc.cout = 0;
-        if (rev) scan_bwdr_body<NS, true>(q, smem, pc);
-        else scan_bwdr_body<NS, false>(q, smem, pc);
+        if (rev) scan_bwdr_body<NS, true, MODE == 3>(q, smem, pc);
+        else scan_bwdr_body<NS, false, MODE == 3>(q, smem, pc);
     }
 }
 
@@ -1022,10 +1025,10 @@ hipError_t launch_scan_bwdr(const BwdArgs& a, hipStream_t stream) {
             e = launch_bwdr_ns<1>(a, stream);
             if (e != hipSuccess) return e;
         }
-        e = launch_bwdr_ns<0>(a, stream);
+        e = a.rpart ? launch_bwdr_ns<3>(a, stream) : launch_bwdr_ns<0>(a, stream);
     }
-    if (e != hipSuccess || a.P == 1) return e;
-    return launch_reduce_partials(a, stream);
+    if (e != hipSuccess) return e;
+    return launch_reduce_after(a, stream);
 }
 
 }  // namespace sigma

@@ -527,6 +527,26 @@ struct BwdArgs {
     int* chain_flag;
     long g_bs, g_ds, du_bs, du_ds, dd_bs, dd_ds, dA_ds, dA_ns;
     long dB_bs, dB_gs, dB_ns, dC_bs, dC_gs, dC_ns;
+    // deterministic backward (SIGMA_SCAN_BWD_DETERMINISTIC): per-row partials [rpart_K][dim][N + 2] (columns: dA[0..N), dD,
+    // ddelta_bias), slot k = b * S + seg owned by the one workgroup that covers (batch b, sequence segment seg) of a row
+    float* rpart;
+    int rpart_K;
 };
+
+// A per-row result (one dA[n], dD or ddelta_bias term) leaving a backward workgroup.  DET = false: one atomicAdd into the
+// gradient, in whatever order the workgroups finish.  DET = true: a plain store into the workgroup's own slot of
+// q.rpart -- `first` = the first time the workgroup reaches this row, later tiles add to the slot (read-add-write by the
+// same lane: program order) -- which reduce_rows_kernel then adds in a fixed order.
+// `q` points to the BwdArgs (generic or constant address space).
+template <bool DET, class QP>
+__device__ __forceinline__ void row_result(QP q, float* grad, int k, int pr, int col, bool first, float v) {
+    if constexpr (DET) {
+        float* slot = q->rpart + ((long)k * q->f.dim + pr) * (q->f.N + 2) + col;
+        *slot = first ? v : *slot + v;
+    } else {
+        (void)q; (void)k; (void)pr; (void)col; (void)first;
+        atomicAdd(grad, v);
+    }
+}
 
 }  // namespace sigma

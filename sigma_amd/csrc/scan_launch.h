@@ -93,6 +93,7 @@ hipError_t launch_scan_fwdr(const FwdArgs& a, hipStream_t stream);   // a.rowblo
 hipError_t launch_scan_bwdr(const BwdArgs& a, hipStream_t stream);
 int bwdr_resident_per_cu(int N);                                     // workgroups of scan_bwdr_kernel a CU holds (occupancy query, cached)   // a.P = 64-row blocks per (batch, group); a.S / a.seg_tiles / a.summ
 hipError_t launch_reduce_partials(const BwdArgs& a, hipStream_t stream);
+hipError_t launch_reduce_after(const BwdArgs& a, hipStream_t stream);   // the reduce pass a backward needs (none, dB/dC, + rows)
 hipError_t bwd4_prof_read(unsigned long long* out16);
 hipError_t fwdr_prof_read(unsigned long long* out16);     // development builds (SIGMA_RL_PROF), zeros otherwise
 hipError_t bwdr_prof_read(unsigned long long* out16);

@@ -90,6 +90,11 @@ _FORMS = {"sigma_gemm_nt_split3": 0, "sigma_gemm_nn_split3": 1, "sigma_gemm_tn_s
 _TWO_STAGE = os.environ.get("SIGMA_GEMM_TWO_STAGE", "1") != "0"
 
 
+def _two_stage() -> bool:
+    """the two-stage sum, always in deterministic mode (sigma_amd/deterministic.py), whatever SIGMA_GEMM_TWO_STAGE says"""
+    return _TWO_STAGE or torch.are_deterministic_algorithms_enabled()
+
+
 def _atomic_path(out: torch.Tensor, accumulate: bool) -> bool:
     """A/B path only: the output of a possibly sliced launch is zero-filled here and then added into"""
     if not accumulate:
@@ -105,7 +110,11 @@ def _run(name, p, dev):
     # dword atomics per thread and item (half of such a launch, round 6) -- and the output needs no zero fill.  The
     # buffer comes from torch's caching allocator and goes back when this call returns: stream-ordered, so the kernels
     # enqueued here finish with it before a later allocation on this stream can reuse it.
-    need = int(lib.sigma_gemm_workspace_bytes(ctypes.byref(p), _FORMS[name])) if _TWO_STAGE else 0   # < 0: bad arguments -- the call below says so
+    need = int(lib.sigma_gemm_workspace_bytes(ctypes.byref(p), _FORMS[name])) if _two_stage() else 0   # < 0: bad arguments -- the call below says so
+    if need == 0 and p.c_mod > 0 and p.batch > p.c_mod and torch.are_deterministic_algorithms_enabled():
+        # problems share an output but the query offers no scratch (ragged c_mod): the kernel would add with fp32 atomics
+        from .deterministic import no_deterministic_implementation
+        no_deterministic_implementation(f"{name} with {p.batch} problems on {p.c_mod} shared outputs")
     ws = None
     if need > 0:
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -193,7 +202,7 @@ def gemm_nn(a: torch.Tensor, b: torch.Tensor, out=None, accumulate=False, pieces
     elif out.stride(1) != 1 or tuple(out.shape) != (M, N):
         raise RuntimeError("gemm_nn: out must be (M, N) with contiguous rows")
     if M and N:
-        if k_slices and not _TWO_STAGE:
+        if k_slices and not _two_stage():
             accumulate = _atomic_path(out, accumulate)
         _run("sigma_gemm_nn_split3", _params(M, N, K, a, b, out, None, a.stride(0), b.stride(0), out.stride(0),
                                              accumulate, pieces=pieces, k_slices=1 if k_slices else 0), a.device)
@@ -223,7 +232,7 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, out=None, accumulate=False, pieces
     elif out.stride(1) != 1 or tuple(out.shape) != (N, K):
         raise RuntimeError("gemm_tn: out must be (N, K) with contiguous rows")
     if N and K:
-        if not _TWO_STAGE:
+        if not _two_stage():
             accumulate = _atomic_path(out, accumulate)
         _run("sigma_gemm_tn_split3", _params(M, N, K, a, b, out, None, a.stride(0), b.stride(0), out.stride(0), accumulate, pieces=pieces), a.device)
     return out
@@ -282,7 +291,7 @@ def bgemm_nt_sum(a: torch.Tensor, bt: torch.Tensor, out: torch.Tensor, pieces: i
     if Zb != Z or Kb != K or tuple(out.shape[1:]) != (M, N) or Z % max(Zc, 1) != 0 or K % 4 != 0:
         raise RuntimeError(f"bgemm_nt_sum: shapes a {tuple(a.shape)} bt {tuple(bt.shape)} out {tuple(out.shape)}")
     if Z and M and N:
-        if not _TWO_STAGE:
+        if not _two_stage():
             accumulate = _atomic_path(out, accumulate)
         _run("sigma_gemm_nt_split3", _params(M, N, K, a, bt, out, None, a.stride(1), bt.stride(1), out.stride(1), accumulate, batch=Z,
                                              sA=a.stride(0), sB=bt.stride(0), sC=out.stride(0), c_mod=Zc, pieces=pieces), a.device)

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import logging
 
+import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
@@ -107,7 +108,10 @@ class EncoderDecoder(nn.Module):
         if label is not None:
             # mean cross entropy straight from the channels-last logits of the classifier GEMM (csrc/pointwise.hip); any
             # other criterion / layout: the criterion itself on the (B, nc, H, W) view
-            from ..pointwise import cross_entropy
+            from ..pointwise import cross_entropy, cross_entropy_deterministic
             loss = cross_entropy(self.criterion, out, label) if out.is_cuda else None
+            if loss is None and torch.are_deterministic_algorithms_enabled():
+                # deterministic mode: torch's nll_loss2d has no deterministic form (sigma_amd/deterministic.py)
+                loss = cross_entropy_deterministic(self.criterion, out, label)
             return loss if loss is not None else self.criterion(out, label.long())
         return out if out.is_contiguous() else out.contiguous()     # callers get the reference's (B, nc, H, W) layout

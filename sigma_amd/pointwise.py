@@ -116,9 +116,20 @@ class ScaleResidualFn(torch.autograd.Function):
         g = dy.contiguous()
         xc = x.contiguous()
         dx = torch.empty_like(xc)
+        lib = _capi.load()
+        if torch.are_deterministic_algorithms_enabled():
+            # deterministic mode (sigma_amd/deterministic.py): per-block column sums, added in a fixed order; ds is written
+            rows = xc.numel() // C
+            ws_bytes = int(lib.sigma_colscale_bwd_workspace_bytes(rows, C))
+            ws = torch.empty(max(ws_bytes, 16), device=x.device, dtype=torch.uint8)
+            ds = torch.empty(C, device=x.device, dtype=torch.float32)
+            with torch.cuda.device(x.device):
+                _capi.check(lib.sigma_colscale_bwd_ws(_p(g), _p(xc), _p(scale), _p(dx), _p(ds), rows, C, _p(ws), ws_bytes,
+                                                      _stream()), "colscale_bwd_ws")
+            return dy, dx, ds
         ds = torch.zeros(C, device=x.device, dtype=torch.float32)
         with torch.cuda.device(x.device):
-            _capi.check(_capi.load().sigma_colscale_bwd(_p(g), _p(xc), _p(scale), _p(dx), _p(ds), xc.numel() // C, C, _stream()),
+            _capi.check(lib.sigma_colscale_bwd(_p(g), _p(xc), _p(scale), _p(dx), _p(ds), xc.numel() // C, C, _stream()),
                         "colscale_bwd")
         return dy, dx, ds
 
@@ -184,3 +195,20 @@ def cross_entropy(criterion, logits: torch.Tensor, label: torch.Tensor):
         return None
     lab = label.long().contiguous()
     return SoftmaxCEFn.apply(nhwc.reshape(-1, nc), lab.view(-1), criterion.ignore_index)
+
+
+def cross_entropy_deterministic(criterion, logits: torch.Tensor, label: torch.Tensor):
+    """Deterministic mode only (sigma_amd/deterministic.py): criterion(logits, label) for a plain mean-reduced
+    nn.CrossEntropyLoss where ``cross_entropy`` above does not apply (a class count that is not a multiple of 4, as in
+    the small test models), or None.  torch's nll_loss2d raises under the deterministic flag; this formulation uses only
+    element-wise ops and fixed-order reductions: -sum(log_softmax * one_hot) over the non-ignored pixels / their count."""
+    if not (type(criterion) is nn.CrossEntropyLoss and criterion.reduction == "mean" and criterion.weight is None
+            and getattr(criterion, "label_smoothing", 0.0) == 0.0 and logits.dim() == 4 and label.dim() == 3):
+        return None
+    nc = logits.shape[1]
+    lab = label.long()
+    valid = (lab != criterion.ignore_index) & (lab >= 0) & (lab < nc)
+    onehot = F.one_hot(torch.where(valid, lab, torch.zeros_like(lab)), nc).permute(0, 3, 1, 2).to(logits.dtype)
+    per_pixel = -(F.log_softmax(logits, dim=1) * onehot).sum(dim=1)
+    validf = valid.to(logits.dtype)
+    return (per_pixel * validf).sum() / validf.sum()

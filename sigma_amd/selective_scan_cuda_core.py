@@ -298,8 +298,13 @@ def bwd_ext(u, delta, A, B, C, D_, delta_bias_, dout, x_, delta_softplus, nrows:
                    "x must have shape (batch_size, dim, n_chunks, 2 * dstate)")
     du = torch.empty_like(delta)                                     # :329-337 (== empty_like(u) in the reference)
     ddelta = torch.empty_like(delta)
-    # dA, dD, ddelta_bias are accumulated into (atomicAdd per row and tile): ONE zero fill for all three
-    zeros = torch.zeros(dim * dstate + 2 * dim, dtype=torch.float32, device=A.device)
+    # dA, dD, ddelta_bias are accumulated into (atomicAdd per row and tile): ONE zero fill for all three; deterministic
+    # mode (sigma_amd/deterministic.py) has the library write them (fixed-order sum), so no fill is needed
+    det = torch.are_deterministic_algorithms_enabled()
+    if det and batch > 0 and seqlen > 0:
+        zeros = torch.empty(dim * dstate + 2 * dim, dtype=torch.float32, device=A.device)
+    else:
+        zeros = torch.zeros(dim * dstate + 2 * dim, dtype=torch.float32, device=A.device)
     dA = zeros[:dim * dstate].view(dim, dstate)
     # fully written by the library (deterministic two-stage sum), so no zero fill is needed
     if dB_out is not None:
@@ -319,6 +324,7 @@ def bwd_ext(u, delta, A, B, C, D_, delta_bias_, dout, x_, delta_softplus, nrows:
         _fill_fwd(bp.fwd, u, delta, A, B, C, D_, delta_bias_, None, x_, delta_softplus, sizes, rev_mask, u_gshift,
                   ckpt_pitch, param_swap)
         bp.dout_group_shift = int(dout_gshift)
+        bp.flags = _capi.SIGMA_SCAN_BWD_DETERMINISTIC if det else 0
         bp.dout, bp.du, bp.ddelta = _ptr(dout), _ptr(du), _ptr(ddelta)
         bp.dA, bp.dB, bp.dC, bp.dD, bp.ddelta_bias = _ptr(dA), _ptr(dB), _ptr(dC), _ptr(dD), _ptr(ddelta_bias)
         bp.dout_batch_stride, bp.dout_d_stride = dout.stride(0), dout.stride(1)
@@ -330,7 +336,7 @@ def bwd_ext(u, delta, A, B, C, D_, delta_bias_, dout, x_, delta_softplus, nrows:
         ws_bytes = int(lib.sigma_scan_bwd_workspace_bytes(ctypes.byref(bp)))
         _check(ws_bytes >= 0, "selective_scan_bwd: " + _capi.last_error())
         workspace = None
-        if ws_bytes > 0:                                 # per-workgroup dB/dC partials (caching allocator)
+        if ws_bytes > 0:                                 # per-workgroup dB/dC (and deterministic dA/dD/ddelta_bias) partials
             workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=u.device)
             bp.workspace, bp.workspace_bytes = _ptr(workspace), ws_bytes
         with torch.cuda.device(u.device):

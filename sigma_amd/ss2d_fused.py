@@ -187,14 +187,25 @@ class DwConvSiLUTwoOrdersFn(torch.autograd.Function):
         # dx in the layout of x: the channel-major (d, B, H, W) buffer of the in_proj hand-over stays channel-major, so that
         # LinearXZFn.backward reads it in place (gemm.py)
         dx = torch.empty_strided(x.shape, x.stride(), device=x.device, dtype=torch.float32)
-        dw = torch.zeros_like(w)
-        db = torch.zeros(d, device=x.device, dtype=torch.float32) if ctx.has_bias else None
+        # deterministic mode (sigma_amd/deterministic.py): dweight / dbias are written through a fixed-order two-stage sum
+        det = torch.are_deterministic_algorithms_enabled()
+        alloc = torch.empty if det else torch.zeros
+        dw = alloc(w.shape, device=w.device, dtype=w.dtype)
+        db = alloc(d, device=x.device, dtype=torch.float32) if ctx.has_bias else None
         p = _capi.DwConvParams()
         p.batch, p.channels, p.height, p.width, p.n_orders = B, d, H, W, ctx.n_orders
+        p.flags = _capi.SIGMA_DWCONV_DETERMINISTIC if det else 0
         p.x, p.weight, p.bias = x.data_ptr(), w.data_ptr(), (b.data_ptr() if ctx.has_bias else None)
         p.g2, p.gpre, p.dweight, p.dx = g2.data_ptr(), gpre.data_ptr(), dw.data_ptr(), dx.data_ptr()
         p.x_batch_stride, p.x_channel_stride = x.stride(0), x.stride(1)
         p.dbias = db.data_ptr() if db is not None else None
+        workspace = None
+        if det:
+            ws_bytes = int(lib.sigma_dwconv3x3_silu_bwd_workspace_bytes(ctypes.byref(p)))
+            if ws_bytes < 0:
+                raise RuntimeError("dwconv3x3_silu_bwd: invalid sizes")
+            workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+            p.workspace, p.workspace_bytes = workspace.data_ptr(), ws_bytes
         with torch.cuda.device(x.device):
             _capi.check(lib.sigma_dwconv3x3_silu_bwd(ctypes.byref(p), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
                         "dwconv3x3_silu_bwd")
