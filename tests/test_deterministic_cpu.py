@@ -70,6 +70,44 @@ def family_of(plan):
     return "Bwd"
 
 
+def fwd_family_of(plan):
+    """the forward family a plan report describes (sigma_scan_fwd_plan: states_per_block slot -200 row-lane, -100 quad-row)"""
+    return {-200: "Fwdr", -100: "Fwd4"}.get(plan[5], "Fwd")
+
+
+def segments_of(plan):
+    """sequence segments of a backward plan report: quad-row items = 10 + 1000 S, row-lane tiles slot = S, else one"""
+    family = family_of(plan)
+    if family == "Bwd4":
+        return max(plan[0] // 1000, 1)
+    return max(plan[4], 1) if family == "Bwdr" else 1
+
+
+def row_sum_depth(plan, batch, L):
+    """Summation depth K of the per-row sums dD = sum dout u and ddelta_bias = sum ddelta over (batch, L), for the two
+    forms of the backward: (K default, K deterministic).  Per family, from the kernel:
+    * Bwdr (scan_bwdr.hip): four lanes per row, each adds 4 positions of every 16-tile of its segment serially
+      (seg_tiles = ceil(ceil(L / 16) / S) tiles), 2 DPP levels, one result per workgroup;
+    * Bwd4 (scan_bwd4.hip): 16 lanes per row, 10 positions each per 160-tile, 4 levels (row_sum_to_lane0), one result per
+      tile of the segment;
+    * Bwd2 (scan_bwd2.hip): 64 lanes, T = items positions each per 64 T tile, 6 levels (wave_sum), one result per tile.
+    Default: every result is an atomicAdd into the zero-filled row, batch x S x (results per workgroup) of them.
+    Deterministic: the results of a workgroup are added into its slot (read-add-write), then reduce_partials_det_kernel adds
+    the rpart_K = batch x S slots in order."""
+    family, S = family_of(plan), segments_of(plan)
+    if family == "Bwdr":
+        seg_tiles = -(-(-(-L // 16)) // S)
+        lane, levels, per_wg = 4 * seg_tiles, 2, 1
+    elif family == "Bwd4":
+        seg_tiles = -(-(-(-L // 160)) // S)
+        lane, levels, per_wg = 10, 4, seg_tiles
+    elif family == "Bwd2":
+        lane, levels, per_wg = plan[0], 6, -(-L // (64 * plan[0]))
+    else:
+        raise ValueError(f"no row-sum depth written out for {family}")
+    return lane + levels + batch * S * per_wg, lane + levels + per_wg + batch * S
+
+
 def test_abi_version_and_struct_fields(tmp_path):
     lib = _capi.load()
     assert _capi.SIGMA_SCAN_ABI_VERSION == 11 and lib.sigma_scan_abi_version() == 11
@@ -104,8 +142,8 @@ def test_scan_workspace_and_plan_with_the_flag(shape):
     assert list(p0) == list(p1), "determinism must not move the kernel choice"
     assert family_of(list(p0)) == family
     assert lib.sigma_scan_bwd_workspace_bytes(ctypes.byref(plain)) == base
-    segments = (p0[0] // 1000) if family == "Bwd4" and p0[0] > 1000 else (p0[4] if family == "Bwdr" else 1)
-    rows = B * max(segments, 1) * KD * (N + 2) * 4              # one slot of dA[N], dD, ddelta_bias per (batch, segment)
+    segments = segments_of(list(p0))
+    rows = B * segments * KD * (N + 2) * 4             # one slot of dA[N], dD, ddelta_bias per (batch, segment)
     assert lib.sigma_scan_bwd_workspace_bytes(ctypes.byref(det)) >= base + rows
 
 

@@ -1,8 +1,9 @@
 """Deterministic mode on the MI355X (sigma_amd/deterministic.py): every backward family through the C ABI with the
 deterministic bit (all of dA / dD / ddelta_bias written, same values as the atomic path to summation order), bitwise
 repeats at the real launch sizes of the step (GPU against GPU: no CPU oracle at full size), the depthwise conv and the
-residual scale, and the whole training step (eager and graph-replayed) in a child process.  Every test that sets
-torch's flag restores it."""
+residual scale, and the whole training step (eager and graph-replayed) in a child process.  Values: the per-workgroup
+slots of the workspace against the written dA / dD / ddelta_bias (fp64), and the fixture models against the reference's
+own model under the flag (child process).  Every test that sets torch's flag restores it."""
 import contextlib
 import ctypes
 import os
@@ -51,8 +52,9 @@ def _problem(batch, KD, L, N, G, ush, dtype=torch.float32, seed=0):
     return u, delta, A, B, C, D, bias, dout
 
 
-def _bwd_capi(args, dout, x, pitch, mask, ush, flags, fill):
-    """sigma_selective_scan_bwd called directly: dA / dD / ddelta_bias pre-filled with `fill`; returns the seven gradients"""
+def _bwd_capi(args, dout, x, pitch, mask, ush, flags, fill, ws_fill=None):
+    """sigma_selective_scan_bwd called directly: dA / dD / ddelta_bias pre-filled with `fill`, the workspace with `ws_fill`
+    (None: left as allocated); returns the seven gradients, the plan report and the workspace (fp32 view)"""
     core = _core()
     lib = _capi.load()
     u, delta, A, B, C, D, bias = args
@@ -78,11 +80,13 @@ def _bwd_capi(args, dout, x, pitch, mask, ush, flags, fill):
     assert lib.sigma_scan_bwd_plan(ctypes.byref(bp), ctypes.byref(plan)) == 0, _capi.last_error()
     ws_bytes = lib.sigma_scan_bwd_workspace_bytes(ctypes.byref(bp))
     assert ws_bytes >= 0, _capi.last_error()
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=DEV)
+    ws = torch.empty(max(ws_bytes, 16) // 4, dtype=torch.float32, device=DEV)
+    if ws_fill is not None:
+        ws.fill_(ws_fill)
     bp.workspace, bp.workspace_bytes = ws.data_ptr(), ws_bytes
     _capi.check(lib.sigma_selective_scan_bwd(ctypes.byref(bp), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "bwd")
     torch.cuda.synchronize()
-    return [du, ddelta, dA, dB, dC, dD, dbias], list(plan)
+    return [du, ddelta, dA, dB, dC, dD, dbias], list(plan), ws[:ws_bytes // 4]
 
 
 # (batch, KD, L, N, G, rev_mask, u_gshift, pitch, dtype, family) -- small launches that force each backward family
@@ -106,9 +110,12 @@ def test_every_family_writes_all_row_gradients(shape):
     u, delta, A, B, C, D, bias, dout = _problem(batch, KD, L, N, G, ush, dtype, seed=3)
     core = _core()
     args = (u, delta, A, B, C, D, bias)
-    _, x = core.fwd_ext(*args, True, rev_mask=mask, u_gshift=ush, ckpt_pitch=pitch)
-    ref, plan = _bwd_capi(args, dout, x, pitch, mask, ush, 0, 0.0)                  # the accumulating contract, zeroed
-    det, plan_d = _bwd_capi(args, dout, x, pitch, mask, ush, _capi.SIGMA_SCAN_BWD_DETERMINISTIC, float("nan"))
+    from tests.test_stream_fp64_gpu import IO_DTYPES, recording, scan_case_keys
+    with recording() as launched:
+        _, x = core.fwd_ext(*args, True, rev_mask=mask, u_gshift=ush, ckpt_pitch=pitch)
+        ref, plan, _ = _bwd_capi(args, dout, x, pitch, mask, ush, 0, 0.0)           # the accumulating contract, zeroed
+        det, plan_d, _ = _bwd_capi(args, dout, x, pitch, mask, ush, _capi.SIGMA_SCAN_BWD_DETERMINISTIC, float("nan"), float("nan"))
+    assert launched == scan_case_keys(*shape[:8], IO_DTYPES[dtype], det=(False, True))    # the census keys of this case
     assert plan == plan_d and family_of(plan) == family
     names = ["du", "ddelta", "dA", "dB", "dC", "dD", "ddelta_bias"]
     for name, a, b in zip(names, det, ref):
@@ -117,7 +124,7 @@ def test_every_family_writes_all_row_gradients(shape):
         err = (a - b).abs().max().item()
         assert err <= 1e-5 * b.abs().max().item(), f"{name}: {err:.3e} vs max {b.abs().max().item():.3e}"
     # the flag-clear contract is kept: dA / dD / ddelta_bias are ADDED to what the caller passes
-    acc, _ = _bwd_capi(args, dout, x, pitch, mask, ush, 0, 1.0)
+    acc, _, _ = _bwd_capi(args, dout, x, pitch, mask, ush, 0, 1.0)
     for name, a, b in zip(names[5:] + names[2:3], acc[5:] + acc[2:3], ref[5:] + ref[2:3]):
         torch.testing.assert_close(a, b + 1.0, rtol=1e-5, atol=1e-5 * (1 + b.abs().max().item()), msg=name)
 
@@ -146,6 +153,40 @@ def test_bitwise_repeat_at_real_sizes(shape):
             for i, (a, b) in enumerate(zip(first, again)):
                 assert torch.equal(a, b), f"gradient {i} differs between two deterministic backwards"
             del again
+
+
+SLOTS = REPEAT + [(1, 768, 19200, 16, 4, 0b1010, 1, 160)]       # + quad-row with sequence segments
+
+
+@pytest.mark.parametrize("shape", SLOTS, ids=["x".join(map(str, s[:3])) + f"xN{s[3]}-p{s[7]}" for s in SLOTS])
+def test_slots_add_up_to_the_written_row_gradients(shape):
+    """The per-workgroup slots of a deterministic backward through the C ABI, workspace NaN-filled: the slot region is the
+    tail of the workspace, [rpart_K][dim][N + 2] floats (columns dA[0..N), dD, ddelta_bias; rpart_K = batch x segments),
+    exactly what the flag adds to the workspace query; every slot is written (finite), and the written dA / dD /
+    ddelta_bias equal the fp64 sum of their rpart_K slots within (rpart_K + 1) u sum_k |slot[k]|
+    (reduce_partials_det_kernel: rpart_K serial fp32 adds).  Negative control: the sum without the last slot."""
+    from tests.test_deterministic_cpu import bwd_params, segments_of
+    from tests.test_stream_fp64_gpu import check, rejects
+    batch, KD, L, N, G, mask, ush, pitch = shape
+    lib = _capi.load()
+    flag = _capi.SIGMA_SCAN_BWD_DETERMINISTIC
+    u, delta, A, B, C, D, bias, dout = _problem(batch, KD, L, N, G, ush, seed=5)
+    args = (u, delta, A, B, C, D, bias)
+    _, x = _core().fwd_ext(*args, True, rev_mask=mask, u_gshift=ush, ckpt_pitch=pitch)
+    det, plan, ws = _bwd_capi(args, dout, x, pitch, mask, ush, flag, float("nan"), float("nan"))
+    K = batch * segments_of(plan)
+    assert K > 1, "one slot per row: nothing to check"
+    with_flag = lib.sigma_scan_bwd_workspace_bytes(ctypes.byref(bwd_params(batch, KD, L, N, G, mask, ush, pitch, 0, flag)))
+    without = lib.sigma_scan_bwd_workspace_bytes(ctypes.byref(bwd_params(batch, KD, L, N, G, mask, ush, pitch, 0)))
+    assert with_flag - without == K * KD * (N + 2) * 4, "the slot region is not [batch x segments][dim][N + 2] floats"
+    assert ws.numel() * 4 == with_flag
+    slots = ws[ws.numel() - K * KD * (N + 2):].view(K, KD, N + 2)
+    assert torch.isfinite(slots).all(), f"{int((~torch.isfinite(slots)).sum())} slot entries not written"
+    s64 = slots.double()
+    ref, S = s64.sum(0), s64.abs().sum(0)
+    got = torch.cat([det[2], det[5][:, None], det[6][:, None]], 1)
+    check("det slots", got, ref, S, K + 1, "dA | dD | ddelta_bias against the sum of the slots")
+    rejects(got, s64[:-1].sum(0), S, K + 1, "the sum without the last slot")
 
 
 def _dw_capi(x, w, b, g2, flags, fill):
@@ -225,3 +266,15 @@ def test_whole_training_step_is_bitwise_reproducible():
                        text=True, timeout=600)
     assert r.returncode == 0, f"worker exit {r.returncode}\n--- stdout\n{r.stdout[-4000:]}\n--- stderr\n{r.stderr[-6000:]}"
     assert "[deterministic_step_worker] done" in r.stdout
+
+
+def test_fixture_models_match_the_reference_under_the_flag():
+    """The model-level VALUES of deterministic mode: tests/deterministic_model_worker.py runs the fixture comparison of
+    tests/test_model_gpu.py (both fixtures, split3 GEMMs, automatic pitch, the same tolerances) under torch's flag, in a
+    child process."""
+    env = dict(os.environ, CUBLAS_WORKSPACE_CONFIG=":4096:8", SIGMA_GEMM="split3")
+    env.pop("SIGMA_CKPT_PITCH", None)                                # automatic pitch
+    r = subprocess.run([sys.executable, "-m", "tests.deterministic_model_worker"], cwd=ROOT, env=env, capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, f"worker exit {r.returncode}\n--- stdout\n{r.stdout[-4000:]}\n--- stderr\n{r.stderr[-6000:]}"
+    assert "[deterministic_model_worker] done" in r.stdout

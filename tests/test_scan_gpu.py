@@ -9,6 +9,7 @@ Tolerances are the reference's (models/encoders/selective_scan/test_selective_sc
 weights 1e-3 / 1e-3, with the same 2x / 5x-10x multipliers on the gradients.
 """
 import ast
+import ctypes
 import glob
 import itertools
 import os
@@ -304,8 +305,11 @@ def test_long_sequences_of_the_720x1280_configuration(shape, pitch):
     core = _core()
     dev = "cuda"
     args = [t.to(dev) for t in (u_h, delta, A, B, C, D, bias)]
-    out, x = core.fwd_ext(*args, True, rev_mask=mask, u_gshift=ush, ckpt_pitch=pitch)
-    grads = core.bwd_ext(*args, g_h.to(dev), x, True, rev_mask=mask, u_gshift=ush, dout_gshift=ush, ckpt_pitch=pitch)
+    from tests.test_stream_fp64_gpu import recording, scan_case_keys
+    with recording() as launched:
+        out, x = core.fwd_ext(*args, True, rev_mask=mask, u_gshift=ush, ckpt_pitch=pitch)
+        grads = core.bwd_ext(*args, g_h.to(dev), x, True, rev_mask=mask, u_gshift=ush, dout_gshift=ush, ckpt_pitch=pitch)
+    assert launched == scan_case_keys(*shape, pitch)                                # the census keys of this case
     revs = [(mask >> g) & 1 for g in range(G)]
     fr = lambda t: torch.cat([t[:, g * rpg:(g + 1) * rpg].flip(-1) if revs[g] else t[:, g * rpg:(g + 1) * rpg] for g in range(G)], 1)
     fg = lambda t: torch.stack([t[:, g].flip(-1) if revs[g] else t[:, g] for g in range(G)], 1)
@@ -556,8 +560,10 @@ def test_full_size_step_launches_against_oracle(shape):
     pitch = ckpt_pitch_for(L, N, batch * KD, core.quad_backward_ok(args[0], args[1], args[3], args[4]),
                            core.rowlane_ok(args[0], args[1], args[3], args[4], g_dev), G)
     assert pitch == want_pitch
-    out, x = core.fwd_ext(*args, True, rev_mask=mask, u_gshift=ush, ckpt_pitch=pitch)
-    grads = core.bwd_ext(*args, g_dev, x, True, rev_mask=mask, u_gshift=ush, dout_gshift=ush, ckpt_pitch=pitch)
+    from tests.test_stream_fp64_gpu import recording, scan_case_keys
+    with recording() as launched:
+        out, x = core.fwd_ext(*args, True, rev_mask=mask, u_gshift=ush, ckpt_pitch=pitch)
+        grads = core.bwd_ext(*args, g_dev, x, True, rev_mask=mask, u_gshift=ush, dout_gshift=ush, ckpt_pitch=pitch)
     revs = [(mask >> g) & 1 for g in range(G)]
     fr = lambda t: torch.cat([t[:, g * rpg:(g + 1) * rpg].flip(-1) if revs[g] else t[:, g * rpg:(g + 1) * rpg] for g in range(G)], 1)
     fg = lambda t: torch.stack([t[:, g].flip(-1) if revs[g] else t[:, g] for g in range(G)], 1)
@@ -567,6 +573,47 @@ def test_full_size_step_launches_against_oracle(shape):
     rg = list(so.selective_scan_oracle_bwd(fr(u_f), fr(delta), A, fg(B), fg(C), D, bias, fr(g_f), True))
     rg[0], rg[1], rg[3], rg[4] = fr(rg[0]), fr(rg[1]), fg(rg[3]), fg(rg[4])
     assert_grads_close(grads, rg)
+
+    # the same backward in deterministic mode (torch's flag; fill_uninitialized_memory stays on, so the binding's
+    # dA / dD / ddelta_bias and workspace start as NaN): the same oracle, the per-element gradients bitwise equal
+    from tests.test_deterministic_gpu import deterministic
+    with deterministic(), recording() as launched_det:
+        det = core.bwd_ext(*args, g_dev, x, True, rev_mask=mask, u_gshift=ush, dout_gshift=ush, ckpt_pitch=pitch)
+    assert launched + launched_det == scan_case_keys(*shape, det=(False, True))     # the census keys of this case
+    assert_grads_close(det, rg)
+    for i, name in ((0, "du"), (1, "ddelta"), (3, "dB"), (4, "dC")):
+        assert torch.equal(det[i], grads[i]), f"{name}: deterministic mode changed a per-element gradient"
+    _check_row_sums(shape, pitch, u_f.to(dev), g_f.to(dev), grads, det)
+
+
+def _check_row_sums(shape, pitch, u_f, g_f, grads, det):
+    """Exact identities of the per-row sums, in fp64 on the GPU over the kernel's own operands / outputs, in both modes:
+    ddelta_bias[d] = sum_{b,l} ddelta[b,d,l] (the bias is added before the softplus) and dD[d] = sum_{b,l} dout u (a
+    reversed group flips both factors).  K = row_sum_depth (tests/test_deterministic_cpu.py: serial adds per lane + reduce
+    levels + results per row, atomics or slot adds + rpart_K), S = sum |terms|.  Negative control: the same sum without the
+    last batch image (batch > 1) or the last ceil(L / S) positions (one image, S sequence segments)."""
+    from tests.test_deterministic_cpu import bwd_params, family_of, row_sum_depth, segments_of
+    from tests.test_stream_fp64_gpu import check, rejects
+    from sigma_amd import _capi
+    batch, KD, L, N, G, mask, ush, _ = shape
+    plan = (ctypes.c_int32 * 6)()
+    assert _capi.load().sigma_scan_bwd_plan(ctypes.byref(bwd_params(batch, KD, L, N, G, mask, ush, pitch, 0)),
+                                            ctypes.byref(plan)) == 0, _capi.last_error()
+    plan = list(plan)
+    family, segs = family_of(plan), segments_of(plan)
+    k_default, k_det = row_sum_depth(plan, batch, L)
+    if batch > 1:
+        drop = lambda t: t[:-1]
+    else:
+        assert segs > 1, "one image and one segment: no negative control"
+        drop = lambda t: t[..., :L - -(-L // segs)]
+    dD_terms = g_f.double() * u_f.double()
+    for mode, gr, K in (("default", grads, k_default), ("deterministic", det, k_det)):
+        fam = f"scan {family} {mode[:3]}"
+        for name, got, terms in (("ddelta_bias", gr[6], gr[1].double()), ("dD", gr[5], dD_terms)):
+            ref, S = terms.sum((0, 2)), terms.abs().sum((0, 2))
+            check(fam, got, ref, S, K, f"{name} ({mode}, {family}, K = {K})")
+            rejects(got, drop(terms).sum((0, 2)), S, K, f"{name} ({mode}) without the last image / segment")
 
 
 def test_quad_row_backward_refuses_what_it_cannot_take():

@@ -26,6 +26,7 @@ memory is detected without a fault.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 
@@ -73,7 +74,8 @@ def launch_key(lib, name, args):
         p = args[0]._obj
         L = p.height * p.width
         strided = (p.x_batch_stride, p.x_channel_stride) not in ((0, 0), (p.channels * L, L))     # dwconv.hip plane_strides
-        return ("dw_" + name[-3:], "plane" if dw_plane(p.height, p.width) else "tiled", p.n_orders, strided)
+        k = ("dw_" + name[-3:], "plane" if dw_plane(p.height, p.width) else "tiled", p.n_orders, strided)
+        return k + ((bool(p.flags & 1),) if name.endswith("bwd") else ())                         # SIGMA_DWCONV_DETERMINISTIC
     if name in ("sigma_softmax_ce_fwd", "sigma_softmax_ce_bwd"):
         nc = int(a[3] if name.endswith("fwd") else a[5])
         return ("ce_" + name[-3:], "reg" if nc // 4 <= 16 else "generic")                        # pointwise.hip:274 dispatch_nc4
@@ -90,6 +92,10 @@ def launch_key(lib, name, args):
         return ("pair_sum_add", "vec" if a[3] % 4 == 0 and _al16(a[0]) and _al16(a[1]) else "scalar")
     if name == "sigma_colscale_bwd":                                                              # pointwise.hip:370
         return ("colscale_bwd", 256 // (int(a[6]) // 4))
+    if name == "sigma_colscale_bwd_ws":                                                           # pointwise.hip:423
+        return ("colscale_bwd_ws", 256 // (int(a[6]) // 4))
+    if name in SCAN_SYMBOLS:
+        return scan_key(lib, name, args[0]._obj)
     if name == "sigma_cross_merge_nhwc":
         return ("merge",)
     if name == "sigma_cross_split_nhwc":
@@ -109,6 +115,37 @@ def launch_key(lib, name, args):
     return None
 
 
+SCAN_SYMBOLS = ("sigma_selective_scan_fwd", "sigma_selective_scan_bwd")
+
+
+def scan_key(lib, name, p):
+    """the kernel family a scan launch takes (the planner's report, decoded as tests/test_deterministic_cpu.py does), the
+    deterministic bit (backward), the IO dtype (0 f32, 1 f16, 2 bf16) and whether the sequence is cut into segments"""
+    from tests.test_deterministic_cpu import family_of, fwd_family_of, segments_of
+    plan = (ctypes.c_int32 * 6)()
+    if name.endswith("fwd"):
+        if lib.sigma_scan_fwd_plan(ctypes.byref(p), ctypes.byref(plan)) != 0:
+            return ("scan_fwd", "refused")
+        fam = fwd_family_of(list(plan))
+        return ("scan_fwd", fam, int(p.io_dtype), fam == "Fwdr" and plan[4] > 1)
+    if lib.sigma_scan_bwd_plan(ctypes.byref(p), ctypes.byref(plan)) != 0:
+        return ("scan_bwd", "refused")
+    return ("scan_bwd", family_of(list(plan)), bool(p.flags & 1), int(p.fwd.io_dtype), segments_of(list(plan)) > 1)
+
+
+def scan_case_keys(batch, KD, L, N, G, mask, ush, pitch, io=0, det=(False,)):
+    """the scan keys of a test case's forward and backward(s), planned for its (contiguous) operands -- no GPU needed"""
+    from tests.test_deterministic_cpu import bwd_params
+    from sigma_amd import _capi
+    lib = _capi.load()
+    bp = bwd_params(batch, KD, L, N, G, mask, ush, pitch, io)
+    keys = [scan_key(lib, "sigma_selective_scan_fwd", bp.fwd)]
+    for d in det:
+        keys.append(scan_key(lib, "sigma_selective_scan_bwd",
+                             bwd_params(batch, KD, L, N, G, mask, ush, pitch, io, _capi.SIGMA_SCAN_BWD_DETERMINISTIC if d else 0)))
+    return keys
+
+
 class _Recorder:
     """stands in for the ctypes library: records (symbol, key) of every keyed call, then forwards it"""
 
@@ -117,7 +154,8 @@ class _Recorder:
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if not (name.startswith("sigma_") and (name in _OPS or name.startswith("sigma_gemm_") and name.endswith("split3"))):
+        if not (name.startswith("sigma_") and (name in _OPS or name in SCAN_SYMBOLS or
+                                               name.startswith("sigma_gemm_") and name.endswith("split3"))):
             return fn
 
         def call(*args):
@@ -134,17 +172,27 @@ def _ops():
 _OPS = set()
 
 
-@pytest.fixture
-def record(monkeypatch):
-    """monkeypatches sigma_amd._capi.load; yields the list the keys are appended to"""
+@contextlib.contextmanager
+def recording():
+    """sigma_amd._capi.load replaced by a recorder for the block; yields the list the keys are appended to"""
     from sigma_amd import _capi
     global _OPS
     _OPS = _ops()
-    real = _capi.load()
+    real = _capi.load
     log: list = []
-    rec = _Recorder(real, log)
-    monkeypatch.setattr(_capi, "load", lambda: rec)
-    yield log
+    rec = _Recorder(real(), log)
+    _capi.load = lambda: rec
+    try:
+        yield log
+    finally:
+        _capi.load = real
+
+
+@pytest.fixture
+def record():
+    """the recorder of ``recording`` around one test"""
+    with recording() as log:
+        yield log
 
 
 # Every path the two models take -> the real shape it is tested at (cases below; GEMM keys: tests/test_gemm_gpu.py)
@@ -400,8 +448,8 @@ DW_CASES = [
 for _B, _d, _H, _W, _l, _path, _w in DW_CASES:
     assert ("plane" if dw_plane(_H, _W) else "tiled") == _path, (_H, _W, _path)
     for _o in (1, 2):
-        for _ph in ("fwd", "bwd"):
-            covers(("dw_" + _ph, _path, _o, _l == "cmajor"), f"test_dwconv_silu_against_fp64[{_B}x{_d}x{_H}x{_W}-{_l}-o{_o}] ({_w})")
+        for _k in (("dw_fwd",), ("dw_bwd", False), ("dw_bwd", True)):      # backward: both values of the deterministic bit
+            covers((_k[0], _path, _o, _l == "cmajor") + _k[1:], f"test_dwconv_silu_against_fp64[{_B}x{_d}x{_H}x{_W}-{_l}-o{_o}] ({_w})")
 
 
 @pytest.mark.parametrize("orders", [2, 1], ids=["o2", "o1"])
@@ -446,7 +494,7 @@ def test_dwconv_silu_against_fp64(case, orders, record):
     _capi.check(lib.sigma_dwconv3x3_silu_bwd(ctypes.byref(p), _stream()), "dwconv bwd")
     torch.cuda.synchronize()
     plane = "plane" if dw_plane(H, W) else "tiled"
-    assert record == [("dw_fwd", plane, orders, layout == "cmajor"), ("dw_bwd", plane, orders, layout == "cmajor")], record
+    assert record == [("dw_fwd", plane, orders, layout == "cmajor"), ("dw_bwd", plane, orders, layout == "cmajor", False)], record
     _intact(gout, "out2")
     _intact(gdx, "dx")
     _intact(ggp, "gpre scratch")
@@ -489,6 +537,36 @@ def test_dwconv_silu_against_fp64(case, orders, record):
             gp = (g2.double()[:, 0].view(B, d, H, W) + (g2.double()[:, 1].view(B, d, W, H).transpose(2, 3) if orders == 2 else 0.0)) \
                 * sg * (1 + pre.detach() * (1 - sg))
             rejects(dbb, gp[:-1].sum((0, 2, 3)), S_gpre.sum((0, 2, 3)), Kr, "dbias missing the last image")
+
+    # deterministic mode (SIGMA_DWCONV_DETERMINISTIC): the same workgroup sums stored to one slot per (batch, tile), then
+    # dwconv_reduce_kernel adds the slots of a channel in order -- the atomics' count of serial adds becomes the slot count:
+    # K = the workgroup's depth + slots.  dweight / dbias / workspace stay NaN-filled: written, not added to
+    p.flags = _capi.SIGMA_DWCONV_DETERMINISTIC
+    slots = B * (1 if plane == "plane" else -(-H // 32) * -(-W // 32))
+    nws = int(lib.sigma_dwconv3x3_silu_bwd_workspace_bytes(ctypes.byref(p)))
+    assert nws == slots * d * 10 * 4
+    gws = _guarded((nws // 4,), 64)
+    gdx2 = _guarded(tuple(gdx[1].shape), L)
+    ggp2 = _guarded((B, d, H, W), L)
+    gdw2, gdb2 = _guarded((d, 9), 64), _guarded((d,), 64)
+    p.gpre, p.dweight, p.dbias, p.dx = ggp2[1].data_ptr(), gdw2[1].data_ptr(), gdb2[1].data_ptr(), gdx2[1].data_ptr()
+    p.workspace, p.workspace_bytes = gws[1].data_ptr(), nws
+    _capi.check(lib.sigma_dwconv3x3_silu_bwd(ctypes.byref(p), _stream()), "dwconv bwd (deterministic)")
+    torch.cuda.synchronize()
+    assert record[2:] == [("dw_bwd", plane, orders, layout == "cmajor", True)], record
+    for g_, w_ in ((gws, "workspace"), (gdx2, "dx"), (ggp2, "gpre scratch"), (gdw2, "dweight"), (gdb2, "dbias")):
+        _intact(g_, w_ + " (deterministic)")
+    assert torch.equal(gdx2[1], gdx[1]), "dx: deterministic mode changed it"
+    if plane == "tiled":
+        assert torch.equal(ggp2[1], ggp[1]), "gpre: deterministic mode changed it"
+    else:                                                     # the whole-plane kernel keeps gpre in LDS
+        assert bool(torch.isnan(ggp2[1]).all()) and bool(torch.isnan(ggp[1]).all())
+    Kd = (4 + 6 + 3 if plane == "tiled" else -(-L // 256) + 6 + 3) + 24 + slots
+    with torch.no_grad():
+        check("dwconv det", gdw2[1], w64.grad.view(d, 9), S_dw, Kd, "dweight (deterministic)")
+        check("dwconv det", gdb2[1], b64.grad, S_gpre.sum((0, 2, 3)), Kd, "dbias (deterministic)")
+        if B > 1:
+            rejects(gdb2[1], gp[:-1].sum((0, 2, 3)), S_gpre.sum((0, 2, 3)), Kd, "deterministic dbias missing the last image")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -724,7 +802,8 @@ def test_plane_ops_against_fp64(case, record):
 CS_CASES = [(8 * 19200, 96, "s decoder 120x160x96"), (8 * 4800, 192, "s decoder 60x80x192"), (8 * 1200, 384, "s decoder 30x40x384"),
             (8 * 300, 768, "s decoder 15x20x768"), (57600, 128, "b decoder 180x320x128"), (14400, 256, "b decoder 90x160x256"), (1001, 1024, "C = 1024"), (37, 4, "C = 4")]
 for _c in CS_CASES:
-    covers(("colscale_bwd", 256 // (_c[1] // 4)), f"test_colscale_bwd_against_fp64[{_c[0]}x{_c[1]}] ({_c[2]})")
+    for _k in ("colscale_bwd", "colscale_bwd_ws"):
+        covers((_k, 256 // (_c[1] // 4)), f"test_colscale_bwd_against_fp64[{_c[0]}x{_c[1]}] ({_c[2]})")
 
 
 @pytest.mark.parametrize("case", CS_CASES, ids=[f"{c[0]}x{c[1]}" for c in CS_CASES])
@@ -758,6 +837,25 @@ def test_colscale_bwd_against_fp64(case, record):
     if rows > G * slots:
         tail = rows % (G * slots) or G * slots
         rejects(gds[1], (dd * xd)[:rows - tail].sum(0), S, K, "ds missing the last row block")
+
+    # deterministic form (sigma_colscale_bwd_ws): the G block sums are stored to workspace rows, then colscale_reduce_kernel
+    # adds them in a fixed order (thread y of 16 adds rows y, y + 16, ..., then the 16 partials in order):
+    # K = ceil(rows / (G slots)) + slots + ceil(G / 16) + 16 + 2.  ds and the workspace stay NaN-filled: ds is written
+    n = int(_capi.load().sigma_colscale_bwd_workspace_bytes(rows, C))
+    assert n == G * C * 4
+    gws, gdx2, gds2 = _guarded((n // 4,), C), _guarded((rows, C), C), _guarded((C,), C)
+    _capi.check(_capi.load().sigma_colscale_bwd_ws(ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(s.data_ptr()),
+                                                   ctypes.c_void_p(gdx2[1].data_ptr()), ctypes.c_void_p(gds2[1].data_ptr()), rows, C,
+                                                   ctypes.c_void_p(gws[1].data_ptr()), n, _stream()), "colscale_bwd_ws")
+    torch.cuda.synchronize()
+    assert record == [("colscale_bwd", slots), ("colscale_bwd_ws", slots)], record
+    for g_, w_ in ((gws, "workspace"), (gdx2, "dx"), (gds2, "ds")):
+        _intact(g_, w_ + " (deterministic)")
+    assert torch.equal(gdx2[1], gdx[1]), "dx: the deterministic form changed it"
+    Kd = -(-rows // (G * slots)) + slots + -(-G // 16) + 16 + 2
+    check("colscale det", gds2[1], (dd * xd).sum(0), S, Kd, "ds (deterministic)")
+    cut = rows - (rows % (G * slots) or G * slots) if rows > G * slots else rows - 1
+    rejects(gds2[1], (dd * xd)[:cut].sum(0), S, Kd, "deterministic ds missing the last row block (or row)")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -873,6 +971,29 @@ def test_gemm_cases_launch_their_census_keys(run, record):
 COVERED.update(GEMM_COVERED)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# scan launches: key -> the oracle / C-ABI case that runs it; each case asserts at run time that it launches its keys
+# (scan_case_keys), so registering them here re-runs nothing
+def _scan_covered():
+    from tests.test_deterministic_gpu import FAMILIES
+    from tests.test_scan_gpu import FULL_LAUNCHES, LONG_SHAPES
+    for c in FULL_LAUNCHES:
+        for k in scan_case_keys(*c, det=(False, True)):
+            covers(k, f"tests/test_scan_gpu.py::test_full_size_step_launches_against_oracle[{c}]")
+    for c in LONG_SHAPES:
+        for pitch in LONG_PITCHES:
+            for k in scan_case_keys(*c, pitch):
+                covers(k, f"tests/test_scan_gpu.py::test_long_sequences_of_the_720x1280_configuration[{c}-{pitch}]")
+    for c in FAMILIES:
+        for k in scan_case_keys(*c[:8], IO_DTYPES[c[8]], det=(False, True)):
+            covers(k, f"tests/test_deterministic_gpu.py::test_every_family_writes_all_row_gradients[{c}]")
+
+
+IO_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+LONG_PITCHES = (0, 640, 320, 160)
+_scan_covered()
+
+
 def _census(model_name, H, W, batch, classes, record):
     from tests.model_utils import build_model, fill
     model = build_model(model_name, classes, H, W).cuda().train()
@@ -887,11 +1008,14 @@ def _census(model_name, H, W, batch, classes, record):
     return keys
 
 
+CENSUS_MODELS = (("sigma_small", 480, 640, 2, 40), ("sigma_base", 720, 1280, 1, 5))
+
+
 def test_census_of_both_models_is_covered(record):
     """one forward + backward of sigma_small 480x640 (batch 2) and sigma_base 720x1280 (batch 1): every stream-kernel /
-    GEMM path they take must be a key of COVERED"""
+    GEMM / scan path they take must be a key of COVERED"""
     seen = {}
-    for name, H, W, batch, classes in (("sigma_small", 480, 640, 2, 40), ("sigma_base", 720, 1280, 1, 5)):
+    for name, H, W, batch, classes in CENSUS_MODELS:
         seen[name] = _census(name, H, W, batch, classes, record)
     missing = []
     for name, keys in seen.items():
@@ -901,6 +1025,53 @@ def test_census_of_both_models_is_covered(record):
             if k not in COVERED:
                 missing.append((name, k))
     assert not missing, f"paths without an fp64 case: {missing}"
+
+
+# project paths of the deterministic step that keep a float atomic on purpose: key -> the documented reason (none)
+NONDETERMINISTIC_ALLOWED: dict = {}
+
+
+def nondeterministic(key) -> bool:
+    """a key whose launch sums with float atomics: a GEMM stage "atomic", a scan / dwconv backward without the
+    deterministic bit, the atomic colscale backward"""
+    if key[0] == "gemm":
+        return key[-1] == "atomic"
+    if key[0] in ("scan_bwd", "dw_bwd"):
+        return key[-1] is not True if key[0] == "dw_bwd" else len(key) < 3 or key[2] is not True
+    return key[0] == "colscale_bwd"
+
+
+def test_census_of_the_deterministic_step():
+    """the census of test_census_of_both_models_is_covered under torch's flag (warn_only: torch's own refusals warn), in a
+    child process (tests/deterministic_census_worker.py; the flag and CUBLAS_WORKSPACE_CONFIG stay out of this one):
+    (a) every key is in COVERED, (b) no project path sums with float atomics unless NONDETERMINISTIC_ALLOWED says why"""
+    import ast
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, CUBLAS_WORKSPACE_CONFIG=":4096:8")
+    r = subprocess.run([sys.executable, "-m", "tests.deterministic_census_worker"], cwd=root, env=env, capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, f"worker exit {r.returncode}\n--- stdout\n{r.stdout[-4000:]}\n--- stderr\n{r.stderr[-6000:]}"
+    assert "[deterministic_census_worker] done" in r.stdout
+    seen = {}
+    for line in r.stdout.splitlines():
+        if line.startswith("[census] "):
+            name, keys = line[9:].split(" ", 1)
+            seen[name] = ast.literal_eval(keys)
+    assert sorted(seen) == sorted(m[0] for m in CENSUS_MODELS), r.stdout[-4000:]
+    missing, atomic = [], []
+    for name, keys in seen.items():
+        print(f"\ndeterministic census {name}: {len(keys)} keys")
+        for k in keys:
+            print("  ", k, "->", COVERED.get(k, "NOT COVERED"), "(NON-DETERMINISTIC)" if nondeterministic(k) else "")
+            if k not in COVERED:
+                missing.append((name, k))
+            if nondeterministic(k) and k not in NONDETERMINISTIC_ALLOWED:
+                atomic.append((name, k))
+    assert not missing, f"paths without an fp64 case: {missing}"
+    assert not atomic, f"float-atomic paths in the deterministic step: {atomic}"
 
 
 def test_zz_report_worst_ratios():
