@@ -230,6 +230,53 @@ int sigma_layernorm_bwd(const sigma_layernorm_params *params, void *stream);
  * meet in LDS), added up in a fixed order by a second small kernel */
 int sigma_layernorm_bwd_partial_rows(int64_t rows, int32_t channels);
 
+/* ---- evaluation: multi-scale score sum, arg-max and confusion matrix (csrc/segmetric.hip) ----
+ *
+ * The reference's evaluator (engine/evaluator.py:433-450, utils/metric.py:8-15) adds the (H, W, C) float32 scores of
+ * every scale into a float64 array, takes argmax(2) and counts hist[gt * n_cl + pred] over the pixels with
+ * 0 <= gt < n_cl.  Scores are held class-planar here, (C, pixels): the layout the evaluator's device score already
+ * has before its permute to (H, W, C), and the one in which a lane per pixel reads every class plane coalesced.
+ * Both entry points reproduce the host result exactly: the same IEEE float64 adds in the same (scale) order, numpy's
+ * arg-max rules, integer counts. */
+typedef struct sigma_seg_accumulate_params {
+    int64_t pixels;                /* pixels per class plane (H * W)                                         */
+    int32_t classes;               /* C >= 1                                                                 */
+    int32_t first;                 /* 1: acc = 0.0 + (double)score -- numpy's np.zeros(...) += score, so no
+                                      zero fill is needed (and -0.0 becomes +0.0 as it does there);
+                                      0: acc += (double)score                                               */
+    const float *score;            /* class plane c at score + c * score_plane_stride, pixels contiguous     */
+    double *acc;                   /* class plane c at acc + c * acc_plane_stride                            */
+    int64_t score_plane_stride;    /* elements; >= pixels                                                    */
+    int64_t acc_plane_stride;      /* elements; >= pixels                                                    */
+} sigma_seg_accumulate_params;
+
+int sigma_seg_accumulate(const sigma_seg_accumulate_params *params, void *stream);
+
+typedef struct sigma_seg_confusion_params {
+    int64_t pixels;                /* pixels of the image (H * W), < 2^31                                    */
+    int32_t classes;               /* C planes of `acc` (1..65535), or 0 when `acc` is NULL                  */
+    int32_t n_cl;                  /* 1..256: hist is n_cl x n_cl                                            */
+    int32_t gt_elem_size;          /* 1: uint8 labels, 8: int64 labels                                       */
+    int32_t pred_elem_size;        /* 1: uint8, 8: int64 (numpy's argmax dtype); 1 needs classes <= 256      */
+    const double *acc;             /* the summed scores, class plane c at acc + c * acc_plane_stride; NULL:
+                                      `pred` is an INPUT (hist_info of a given prediction)                   */
+    int64_t acc_plane_stride;      /* elements; >= pixels                                                    */
+    void *pred;                    /* (pixels,) arg-max over the classes, first maximum / first NaN wins
+                                      (numpy's argmax); written when acc != NULL (NULL = not written),
+                                      read when acc == NULL                                                  */
+    const void *gt;                /* (pixels,) labels; a pixel counts when 0 <= gt < n_cl (255 = ignore);
+                                      NULL = arg-max only (pred required, hist / counts unused)              */
+    int64_t *hist;                 /* (n_cl, n_cl) row gt, column pred; counts are ADDED (zero it first)     */
+    int64_t *counts;               /* [labeled, correct, invalid], ADDED; invalid = counted pixels whose pred
+                                      is outside [0, n_cl) -- they are not binned                           */
+} sigma_seg_confusion_params;
+
+/* per-workgroup uint32 histograms in LDS when n_cl * n_cl * 4 <= SIGMA_SEG_LDS_HIST_BYTES (n_cl <= 90), flushed into
+ * the int64 global histogram; above that, int64 atomics straight into the global histogram.  Integer adds only: the
+ * result is exact and the same in any order. */
+#define SIGMA_SEG_LDS_HIST_BYTES 32768
+int sigma_seg_argmax_confusion(const sigma_seg_confusion_params *params, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

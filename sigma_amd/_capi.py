@@ -142,7 +142,27 @@ class GateBwdParams(ctypes.Structure):
     ]
 
 
+class SegAccumulateParams(ctypes.Structure):
+    """mirror of sigma_seg_accumulate_params (include/sigma_ops.h)"""
+    _fields_ = [
+        ("pixels", ctypes.c_int64), ("classes", ctypes.c_int32), ("first", ctypes.c_int32),
+        ("score", ctypes.c_void_p), ("acc", ctypes.c_void_p),
+        ("score_plane_stride", ctypes.c_int64), ("acc_plane_stride", ctypes.c_int64),
+    ]
+
+
+class SegConfusionParams(ctypes.Structure):
+    """mirror of sigma_seg_confusion_params (include/sigma_ops.h)"""
+    _fields_ = [
+        ("pixels", ctypes.c_int64), ("classes", ctypes.c_int32), ("n_cl", ctypes.c_int32),
+        ("gt_elem_size", ctypes.c_int32), ("pred_elem_size", ctypes.c_int32),
+        ("acc", ctypes.c_void_p), ("acc_plane_stride", ctypes.c_int64),
+        ("pred", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("hist", ctypes.c_void_p), ("counts", ctypes.c_void_p),
+    ]
+
+
 SIGMA_CE_BLOCKS = 1024      # include/sigma_ops.h
+SIGMA_SEG_LDS_HIST_BYTES = 32768    # include/sigma_ops.h
 
 # every symbol include/sigma_gemm.h declares
 GEMM_SYMBOLS = ("sigma_gemm_nt_split3", "sigma_gemm_nn_split3", "sigma_gemm_tn_split3")
@@ -153,7 +173,7 @@ OPS_SYMBOLS = ("sigma_dwconv3x3_silu_fwd", "sigma_dwconv3x3_silu_bwd", "sigma_cr
                "sigma_layernorm_fwd", "sigma_layernorm_bwd", "sigma_layernorm_bwd_partial_rows", "sigma_transpose2d",
                "sigma_pair_sum_add", "sigma_upsample2x_nhwc", "sigma_plane_pool", "sigma_plane_scale",
                "sigma_plane_dot", "sigma_plane_gate_bwd", "sigma_softmax_ce_fwd", "sigma_softmax_ce_bwd", "sigma_colscale_bwd",
-               "sigma_colscale_bwd_ws")
+               "sigma_colscale_bwd_ws", "sigma_seg_accumulate", "sigma_seg_argmax_confusion")
 # the size queries include/sigma_ops.h declares (int64_t results)
 OPS_AUX_SYMBOLS = ("sigma_dwconv3x3_silu_bwd_workspace_bytes", "sigma_colscale_bwd_workspace_bytes")
 
@@ -244,6 +264,10 @@ def load() -> ctypes.CDLL:
         elif name == "sigma_softmax_ce_bwd":
             fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                            ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+        elif name == "sigma_seg_accumulate":
+            fn.argtypes = [P(SegAccumulateParams), ctypes.c_void_p]
+        elif name == "sigma_seg_argmax_confusion":
+            fn.argtypes = [P(SegConfusionParams), ctypes.c_void_p]
         else:
             st = (MergeParams if "cross_" in name else LayerNormParams if "layernorm" in name else
                   TransposeParams if "transpose" in name else DwConvParams)

@@ -20,6 +20,12 @@ Drop-in for the reference's ``Evaluator`` (same method names, arguments and retu
     evaluator.val_func_process_rgbX = types.MethodType(evaluator_ops.val_func_process_rgbX, evaluator)
     evaluator.scale_process_rgbX = types.MethodType(evaluator_ops.scale_process_rgbX, evaluator)
     evaluator.sliding_eval_rgbX = types.MethodType(evaluator_ops.sliding_eval_rgbX, evaluator)
+    evaluator.func_per_iteration = types.MethodType(evaluator_ops.func_per_iteration, evaluator)   # SegEvaluator
+
+``func_per_iteration`` keeps the per-image bookkeeping on the device as well (csrc/segmetric.hip): the float64 sum of
+the scales (``summed_scores_device``), numpy's arg-max and hist_info's confusion counts in one pass; only the
+n_cl x n_cl matrix and two counts come back to the host.  ``sliding_eval_rgbX_device`` returns the device prediction,
+``hist_info_device`` is hist_info of a given prediction.
 
 The window grid reproduces the reference's arithmetic literally, including its mixed use of ``crop_size[0]`` /
 ``stride[0]`` for the column direction (evaluator.py:472-478): a drop-in must score the same pixels.  With a crop that
@@ -34,6 +40,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 import torch.nn.functional as F
+
+from .. import segmetric
 
 
 def flip_pair_scores(model, rgb: torch.Tensor, modal_x: torch.Tensor, is_flip: bool) -> torch.Tensor:
@@ -112,6 +120,13 @@ def window_grid(pad_rows: int, pad_cols: int, crop, stride_rate: float):
 
 def scale_process_rgbX(self, img, modal_x, ori_shape, crop_size, stride_rate, device=None, max_windows: int = 4):
     """Mirror of engine/evaluator.py:452-499 for one scale; returns the (ori_rows, ori_cols, classes) float32 array."""
+    score = scale_scores_device(self, img, modal_x, ori_shape, crop_size, stride_rate, device, max_windows)
+    return score.permute(1, 2, 0).contiguous().cpu().numpy()
+
+
+def scale_scores_device(self, img, modal_x, ori_shape, crop_size, stride_rate, device=None, max_windows: int = 4):
+    """The device part of ``scale_process_rgbX``: the (classes, ori_rows, ori_cols) float32 score of one scale, left on
+    the device in the class-planar layout the network produces (the host path permutes it to (H, W, C))."""
     crop = (int(crop_size[0]), int(crop_size[1]))
     new_rows, new_cols = img.shape[0], img.shape[1]
     self.val_func.eval()
@@ -164,7 +179,7 @@ def scale_process_rgbX(self, img, modal_x, ori_shape, crop_size, stride_rate, de
             score = data_scale[:, top:data_scale.shape[1] - bottom, left:data_scale.shape[2] - right]
         if tuple(score.shape[1:]) != (int(ori_shape[0]), int(ori_shape[1])):
             score = F.interpolate(score[None], size=(int(ori_shape[0]), int(ori_shape[1])), mode="bilinear", align_corners=False)[0]
-        return score.permute(1, 2, 0).contiguous().cpu().numpy()
+        return score
 
 
 _COEF_ONE = 1 << 11         # cv2's INTER_RESIZE_COEF_SCALE: bilinear weights of 8-bit images are 11-bit fixed point
@@ -258,3 +273,68 @@ def sliding_eval_rgbX(self, img, modal_x, crop_size, stride_rate, device=None):
         mx_scale = resize_like_cv2(modal_x, s, modal_x.ndim == 2, dev)
         processed += scale_process_rgbX(self, img_scale, mx_scale, (ori_rows, ori_cols), crop, stride_rate, device)
     return processed.argmax(2)
+
+
+def summed_scores_device(self, img, modal_x, crop_size, stride_rate, device=None) -> torch.Tensor:
+    """The scales and resizes of ``sliding_eval_rgbX`` with the float64 sum kept on the device: (classes, H, W) float64,
+    the same IEEE adds in the same scale order as the reference's np.zeros(...) += score (csrc/segmetric.hip)."""
+    crop = (crop_size, crop_size) if isinstance(crop_size, int) else tuple(crop_size)
+    ori_rows, ori_cols, _ = img.shape
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    acc = None
+    for s in self.multi_scales:
+        img_scale = resize_like_cv2(img, s, False, dev)
+        mx_scale = resize_like_cv2(modal_x, s, modal_x.ndim == 2, dev)
+        score = scale_scores_device(self, img_scale, mx_scale, (ori_rows, ori_cols), crop, stride_rate, device)
+        first = acc is None
+        if first:
+            acc = torch.empty((self.class_num, ori_rows, ori_cols), dtype=torch.float64, device=score.device)
+        segmetric.accumulate_scores(acc, score, first)
+    if acc is None:                     # no scales: the reference's arg-max of its zero array
+        acc = torch.zeros((self.class_num, ori_rows, ori_cols), dtype=torch.float64, device=dev)
+    return acc
+
+
+def sliding_eval_rgbX_device(self, img, modal_x, crop_size, stride_rate, device=None) -> torch.Tensor:
+    """``sliding_eval_rgbX`` with the sum over the scales and the arg-max on the device: the (H, W) int64 prediction as
+    a device tensor, equal to the host path's numpy array element for element."""
+    return segmetric.argmax(summed_scores_device(self, img, modal_x, crop_size, stride_rate, device))
+
+
+def hist_info_device(n_cl, pred, gt):
+    """utils/metric.py:8-15 (hist_info) on the device: pred / gt are tensors (any device) or numpy arrays; returns
+    (hist: int64 ndarray (n_cl, n_cl), labeled: int, correct: int).  A labeled pixel whose prediction lies outside
+    [0, n_cl) raises ValueError (numpy's bincount would fail on a negative one and misplace a large one)."""
+    return segmetric.confusion(pred, gt, int(n_cl))
+
+
+def func_per_iteration(self, data, device, config):
+    """Drop-in for SegEvaluator.func_per_iteration (eval.py:22-30): the same results_dict ({'hist', 'labeled',
+    'correct'}, values of hist_info), with the scale sum, the arg-max and the confusion counts on the device -- what
+    leaves the device per image is the n_cl x n_cl matrix and two counts.
+
+    The (H, W) prediction is copied to the host only when ``self.save_path`` or ``self.show_image`` asks for it; it is
+    then handed to the evaluator class's own func_per_iteration (its saving and display code), in place of the
+    prediction its sliding_eval_rgbX would have returned.  That needs the method patched on the INSTANCE (the recipe
+    in INTEGRATION.md), so that the class still holds the original."""
+    n_cl = int(config.num_classes)
+    acc = summed_scores_device(self, data['data'], data['modal_x'], config.eval_crop_size, config.eval_stride_rate, device)
+    need_pred = getattr(self, "save_path", None) is not None or bool(getattr(self, "show_image", False))
+    pred, (hist, labeled, correct) = segmetric.argmax_confusion(acc, data['label'], n_cl, want_pred=need_pred)
+    results_dict = {'hist': hist, 'labeled': labeled, 'correct': correct}
+    if need_pred:
+        own = getattr(type(self), "func_per_iteration", None)
+        if own is None or getattr(own, "__func__", own) is func_per_iteration:
+            raise RuntimeError("func_per_iteration: saving or showing the prediction needs the evaluator class's own "
+                               "func_per_iteration; patch the instance (types.MethodType), not the class")
+        host_pred = pred.cpu().numpy()
+        patched = self.__dict__.get("sliding_eval_rgbX")
+        self.sliding_eval_rgbX = lambda *args, **kwargs: host_pred
+        try:
+            own(self, data, device, config)
+        finally:
+            if patched is None:
+                del self.sliding_eval_rgbX
+            else:
+                self.sliding_eval_rgbX = patched
+    return results_dict
