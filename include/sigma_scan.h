@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-#define SIGMA_SCAN_ABI_VERSION 11
+/* ABI 12 removed the cycle-counter read-out of the phase-profiling builds, along with those builds. */
+#define SIGMA_SCAN_ABI_VERSION 12
 
 /* dtype of u, delta, B, C, out, dout, du, ddelta  (input_t of the reference,
  * selective_scan.cpp:174: float / half / bfloat16).  A, D, delta_bias, x, dA,
@@ -244,10 +245,6 @@ int sigma_scan_get_option(const char *name);
  * ones (ckpt_pitch 16 / 160) or pick another kernel variant, never another workspace size. */
 int sigma_scan_fwd_plan(const sigma_scan_fwd_params *params, int32_t plan[6]);
 int sigma_scan_bwd_plan(const sigma_scan_bwd_params *params, int32_t plan[6]);
-
-/* Development aid: per-phase cycle totals of the second-generation backward since the last call
- * (all zero unless the library was built with -DSIGMA_BWD2_PROF=1); synchronises the device. */
-int sigma_scan_debug_read(uint64_t out16[16]);
 
 /* On-device self test of the wave64 DPP scan primitives against a serial loop.
  * Returns 0 when every lane matches; enqueues on `stream` and synchronises it. */

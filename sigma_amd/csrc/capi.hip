@@ -920,18 +920,6 @@ int sigma_selective_scan_bwd(const sigma_scan_bwd_params* q, void* stream) {
     return SIGMA_OK;
 }
 
-int sigma_scan_debug_read(uint64_t out16[16]) {
-    if (!out16) return fail(SIGMA_ERR_NULL_ARG, "out16 is NULL");
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = sigma::bwd2_prof_read(reinterpret_cast<unsigned long long*>(out16));
-    if (e == hipSuccess && out16[15] == 0) e = sigma::bwd4_prof_read(reinterpret_cast<unsigned long long*>(out16));   // quad-row kernel ran
-    if (e == hipSuccess && out16[15] == 0) e = sigma::bwdr_prof_read(reinterpret_cast<unsigned long long*>(out16));   // row-lane backward ran
-    if (e == hipSuccess && out16[15] == 0) e = sigma::fwdr_prof_read(reinterpret_cast<unsigned long long*>(out16));   // row-lane forward ran
-    if (e == hipSuccess && out16[15] == 0) e = sigma::gemm_prof_read(reinterpret_cast<unsigned long long*>(out16));   // split-operand GEMM ran
-    if (e != hipSuccess) return fail(SIGMA_ERR_LAUNCH, "debug read failed: %s", hipGetErrorString(e));
-    return SIGMA_OK;
-}
-
 int sigma_scan_selftest(void* stream) {
     float* d = nullptr;
     hipError_t e = hipMalloc(&d, 8 * sizeof(float));

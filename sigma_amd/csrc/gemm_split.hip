@@ -22,45 +22,12 @@
 //     re-read from that XCD's L2).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/sigma_gemm.h"
 #include "../../include/sigma_ops.h"
 #include "scan_device.h"
 
-// Ablation builds (-DSIGMA_GEMM_ABL=<bits>; WRONG results, timing only): 1 no MFMA / fragment reads, 2 no global operand
-// loads, 4 no C stores, 8 no fp32 -> bf16 split arithmetic (raw bits are stored), 16 no LDS stores and no barriers
-#ifndef SIGMA_GEMM_ABL
-#define SIGMA_GEMM_ABL 0
-#endif
-
-// Development builds (-DSIGMA_GEMM_PROF=1): clocks per phase of the k-step loop, summed over the waves (sigma_scan_debug_read;
-// tools/diag/gemm_prof.py): 0 wait for operand loads, 1 split + LDS stores, 2 barrier, 3 load issue, 4 fragment reads + MFMA
-// issue, 5 barrier, 6 epilogue + store drain, 7 item switch; 13 tiles, 14 all clocks of the loop, 15 k-steps.  The probes are
-// scheduling barriers and each costs an s_memtime round trip: the instrumented loop runs ~30 % longer.
-#ifndef SIGMA_GEMM_PROF
-#define SIGMA_GEMM_PROF 0
-#endif
-#if SIGMA_GEMM_PROF
-__device__ unsigned long long g_gemm_prof[16];
-#define GPROF(slot) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_readcyclecounter(); \
-                      prof_[slot] += t_ - tp_; tp_ = t_; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define GPROF(slot)
-#endif
-
 namespace sigma {
-
-#if SIGMA_GEMM_PROF
-hipError_t gemm_prof_read(unsigned long long* out16) {
-    hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_gemm_prof), 16 * sizeof(unsigned long long));
-    if (e != hipSuccess) return e;
-    unsigned long long z[16] = {0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_prof), z, sizeof(z));
-}
-#else
-hipError_t gemm_prof_read(unsigned long long* out16) { for (int i = 0; i < 16; ++i) out16[i] = 0; return hipSuccess; }
-#endif
 
 namespace {
 
@@ -101,11 +68,6 @@ struct GemmArgs {
 // next residual: 8 significant bits each, round to nearest even (v_cvt_pk_bf16_f32)
 template <int P>
 __device__ __forceinline__ void split_pair(float x0, float x1, unsigned (&piece)[P]) {
-#if SIGMA_GEMM_ABL & 8
-#pragma unroll
-    for (int q = 0; q < P; ++q) piece[q] = __builtin_bit_cast(unsigned, q & 1 ? x1 : x0);
-    return;
-#endif
 #pragma unroll
     for (int q = 0; q < P; ++q) {
         const f32x2_t f = {x0, x1};
@@ -161,11 +123,6 @@ struct TileLoader {
     // base: element (row0, k0) of the operand; rem = reduction elements left from k0 (>= 32: a full step)
     __device__ __forceinline__ void issue(f32x4_t (&v)[NV], const float* base, int rem, long ld) const {
         const int t = threadIdx.x;
-#if SIGMA_GEMM_ABL & 2
-#pragma unroll
-        for (int i = 0; i < NV; ++i) { v[i] = f32x4_t{0.5f + t, 0.25f, 1.0f + i, 2.0f}; asm volatile("" : "+v"(v[i])); }
-        return;
-#endif
         const unsigned ldb4 = (unsigned)(ld * 4);
         // the base is wave-uniform by construction; readfirstlane folds away when the compiler knows it and keeps the
         // "s" operand of the asm legal when it does not (it then holds the pointer in VGPRs)
@@ -248,20 +205,8 @@ __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" :
 // operands k-contiguous or one of them transposed, one step ahead is as fast as two (and leaves the registers to the
 // compiler's schedule); the weight-gradient form (both operands transposed on the way in, reduction over the tokens
 // straight from HBM) gains 10-20 % from two on the long-token shapes.
-#ifndef SIGMA_GEMM_DEPTH
-#define SIGMA_GEMM_DEPTH 0
-#endif
-#ifndef SIGMA_GEMM_SLICE_MAJOR
-#define SIGMA_GEMM_SLICE_MAJOR 1           // 0: A/B builds with the tile-major item order for sliced reductions
-#endif
-#ifndef SIGMA_GEMM_FRAG_PIN
-#define SIGMA_GEMM_FRAG_PIN 1              // 0: A/B builds that leave the placement of the fragment reads to the compiler
-#endif
-#ifndef SIGMA_GEMM_ROW_EPILOGUE
-#define SIGMA_GEMM_ROW_EPILOGUE 1          // 0: A/B builds with the direct (dword) epilogue
-#endif
 template <bool A_KS, bool B_KS>
-struct ring_depth { static constexpr int value = SIGMA_GEMM_DEPTH ? SIGMA_GEMM_DEPTH : ((A_KS && B_KS) ? 2 : 1); };
+struct ring_depth { static constexpr int value = (A_KS && B_KS) ? 2 : 1; };
 
 // one output tile (x one reduction slice) of one problem of the batch
 struct Item {
@@ -306,7 +251,7 @@ gemm_split3_kernel(const GemmArgs g) {
         // XCD runs at the same time stream the same k-range of both operands -- each slice of A and B then comes from HBM once
         // per XCD instead of once per row / column tile (the tile-major order shares only the A slice among the column
         // tiles).  One division chain for both orders (selects on wave-uniform values, no branch).
-        const bool slice_major = SIGMA_GEMM_SLICE_MAJOR && B_KS && g.slices > 1;
+        const bool slice_major = B_KS && g.slices > 1;
         const int d1 = slice_major ? g.ntm * g.ntn : g.ntn * g.slices;
         const int q1 = r0 / d1;
         const int rem = r0 - q1 * d1;
@@ -394,7 +339,7 @@ gemm_split3_kernel(const GemmArgs g) {
     // added to the epilogue.  Wave-uniform base + 32-bit element offsets (host: M * ldr < 2^31); rows / columns past the
     // matrix are clamped (their sums are never stored).
     const bool res_rows = RES && (g.N & 3) == 0 && (g.ldr & 3) == 0 && (g.sR & 3) == 0 && (reinterpret_cast<uintptr_t>(g.R) & 15) == 0 &&
-                          (g.R2 == nullptr || (reinterpret_cast<uintptr_t>(g.R2) & 15) == 0) && SIGMA_GEMM_ROW_EPILOGUE;
+                          (g.R2 == nullptr || (reinterpret_cast<uintptr_t>(g.R2) & 15) == 0);
     auto init_acc = [&](const Item& it) {
         if constexpr (!RES) { zero_acc(); return; }
         const float* __restrict__ r1 = g.R + it.r_off;
@@ -488,12 +433,8 @@ gemm_split3_kernel(const GemmArgs g) {
                 for (int r = 0; r < 16; ++r) {
                     const int dr = (r & 3) + ((r >> 2) << 3);
                     const float val = acc[i][j][r] + bv[j];
-#if SIGMA_GEMM_ABL & 4
-                    asm volatile("" :: "v"(val), "v"(p0));
-#else
                     if (inside) put(p0 + (long)dr * g.ldc, val);
                     else if (col < g.N && rbase + dr < g.M) put(p0 + (long)dr * g.ldc, val);
-#endif
                 }
             }
         }
@@ -580,19 +521,12 @@ gemm_split3_kernel(const GemmArgs g) {
             }
         }
     };
-    const bool rows_ok = (g.N & 3) == 0 && (g.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(g.C) & 15) == 0 && (g.sC & 3) == 0 &&
-                         !(SIGMA_GEMM_ABL & 4) && SIGMA_GEMM_ROW_EPILOGUE;
+    const bool rows_ok = (g.N & 3) == 0 && (g.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(g.C) & 15) == 0 && (g.sC & 3) == 0;
 
-#if SIGMA_GEMM_PROF
-    unsigned long long prof_[16] = {0};
-    unsigned long long tp_ = __builtin_readcyclecounter();
-    const unsigned long long t_begin_ = tp_;
-#endif
     while (c_on) {
 #pragma unroll
         for (int u = 0; u < kDepth; ++u) {
             if (!c_on) break;
-            GPROF(7)
             // the loads of slot u are complete when at most the loads of the NEWER stages are outstanding (in-order return)
             {
                 int newer = 0;
@@ -606,30 +540,19 @@ gemm_split3_kernel(const GemmArgs g) {
 #pragma unroll
                 for (int i = 0; i < LoaderB::NV; ++i) asm volatile("" : "+v"(vb[u][i]));
             }
-            GPROF(0)
             const int rem_u = rem_[u];
-#if SIGMA_GEMM_ABL & 16
-            asm volatile("" :: "v"(va[u][0]), "v"(vb[u][0]));
-#else
             la.template store<P>(va[u], rem_u, sA, BM * kPitch);
             lb_.template store<P>(vb[u], rem_u, sB, BN * kPitch);
-#if SIGMA_GEMM_PROF
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            GPROF(1)
-#endif
             lds_barrier();
-            GPROF(2)
-#endif
             produce(u, va[u], vb[u]);                  // refill the slot just written to LDS: step s + kDepth
-            GPROF(3)
             // ALL fragments of the k-step are requested up front (16 ds_read_b128 at 128 x 128, 64 VGPRs), pinned in front of
             // the MFMAs: left to its register heuristics hipcc re-used eight fragment registers and put s_waitcnt
             // lgkmcnt(0) straight after a read three times per k-block -- the MFMA phase ran at ~55 clocks per MFMA
             // against 32 (round 6, ISA + the no-memory ablation build).  LDS returns in order, so the compiler's counted
             // waits release each MFMA as soon as its own two fragments are there.
             // (three pieces per operand: one k-block at a time -- 24 fragments would not fit beside the accumulators)
-            constexpr int KSN = (SIGMA_GEMM_ABL & 1) ? 0 : kBK / 16;
-            constexpr int KH = P == 2 ? (KSN > 0 ? KSN : 1) : 1;          // k-blocks whose fragments are in registers at once
+            constexpr int KSN = kBK / 16;
+            constexpr int KH = P == 2 ? KSN : 1;          // k-blocks whose fragments are in registers at once
 #pragma unroll
             for (int k0 = 0; k0 < KSN; k0 += KH) {
                 bf16x8_t fa[KH][P][TM], fb[KH][P][TN];
@@ -645,9 +568,7 @@ gemm_split3_kernel(const GemmArgs g) {
                             fb[kh][q][j] = *reinterpret_cast<const bf16x8_t*>(fB + q * BN * kPitch + j * 32 * kPitch + (k0 + kh) * 16);
                     }
                 }
-#if SIGMA_GEMM_FRAG_PIN
                 if (P == 2) __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
                 for (int kh = 0; kh < KH; ++kh) {
                     // piece products with qa + qb < P, smallest first: P = 2: lo*hi, hi*lo, hi*hi (dropped lo*lo ~ 2^-16);
@@ -663,14 +584,7 @@ gemm_split3_kernel(const GemmArgs g) {
                                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kh][qa][i], fb[kh][sum - qa][j], acc[i][j], 0, 0, 0);
                 }
             }
-            GPROF(4)
-#if !(SIGMA_GEMM_ABL & 16)
             lds_barrier();
-#endif
-            GPROF(5)
-#if SIGMA_GEMM_PROF
-            prof_[15] += 1;
-#endif
             ck += kBK;
             if (ck >= cit.kend) {                      // tile (slice) complete
                 // a transposed column range ALWAYS takes the row epilogue (the direct one below knows no t_cols and would
@@ -682,24 +596,12 @@ gemm_split3_kernel(const GemmArgs g) {
                 } else if (g.mode == 0) epilogue(cit, [](float* dst, float v) { *dst = v; });
                 else if (g.mode == 1) epilogue(cit, [](float* dst, float v) { *dst += v; });
                 else epilogue(cit, [](float* dst, float v) { atomicAdd(dst, v); });
-#if SIGMA_GEMM_PROF
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // charge the store drain to the epilogue
-                prof_[13] += 1;
-#endif
-                GPROF(6)
                 c_id += gridDim.x;
                 c_on = c_id < total;
                 if (c_on) { decode(c_id, cit); ck = cit.kbeg; init_acc(cit); }
             }
         }
     }
-#if SIGMA_GEMM_PROF
-    prof_[14] = __builtin_readcyclecounter() - t_begin_;
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) atomicAdd(&g_gemm_prof[i], prof_[i]);
-    }
-#endif
 }
 
 template <int BM, int BN, int WM, int WN, bool A_KS, bool B_KS, int P, bool RES>
@@ -715,9 +617,6 @@ hipError_t launch_cfg(const GemmArgs& g, int batch, hipStream_t stream) {
         int n = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_split3_kernel<BM, BN, WM, WN, A_KS, B_KS, P, RES>, 256, 0) != hipSuccess || n < 1) n = 2;
         per_cu = n > 4 ? 4 : n;
-#ifdef SIGMA_GEMM_MAX_PER_CU
-        if (per_cu > SIGMA_GEMM_MAX_PER_CU) per_cu = SIGMA_GEMM_MAX_PER_CU;     // A/B builds: resident workgroups per CU capped
-#endif
     }
     long grid = 256L * per_cu;
     if (grid > items) grid = items;
@@ -727,9 +626,6 @@ hipError_t launch_cfg(const GemmArgs& g, int batch, hipStream_t stream) {
 
 // tile width for N columns: 128 unless a narrower tile wastes less ((N = 96, 192: 96-wide tiles are exact)
 int pick_bn(int N) {
-#ifdef SIGMA_GEMM_FORCE_BN
-    return SIGMA_GEMM_FORCE_BN;                         // A/B builds: one tile width for every problem
-#endif
     if (N % 128 == 0) return 128;
     if (N % 96 == 0) return 96;
     if (N <= 64) return 64;
@@ -916,7 +812,7 @@ int plan_nt(const sigma_gemm_params* p, Planned& pl) {
     if (p->t_cols != 0) {                                // transposed column range: row-contiguous epilogue, plain stores only
         if (p->t_cols < 0 || p->t_cols > p->N || p->t_cols % 32 != 0 || !p->Ct || !aligned16(p->Ct) || p->ldct % 4 != 0 ||
             p->ldct < p->M || p->M % 4 != 0 || p->N % 4 != 0 || p->ldc % 4 != 0 || !aligned16(p->C) || pl.batch != 1 ||
-            p->accumulate || p->residual || pl.summed || !SIGMA_GEMM_ROW_EPILOGUE || (SIGMA_GEMM_ABL & 4))
+            p->accumulate || p->residual || pl.summed)
             return SIGMA_OPS_ERR_ARG;
         g.Ct = p->Ct; g.ldct = p->ldct; g.t_cols = p->t_cols;
     }
@@ -979,7 +875,7 @@ int plan_tn(const sigma_gemm_params* p, Planned& pl) {
     const int bn = pick_bn(g.N);
     const long tiles = (long)pl.batch * ((g.M + 127) / 128) * ((g.N + bn - 1) / bn);
     const long steps = (p->M + 31) / 32;
-    static const long target_items = [] { const char* e = getenv("SIGMA_GEMM_TN_ITEMS"); const long v = e ? atol(e) : 0; return v > 0 ? v : 512L; }();
+    constexpr long target_items = 512;
     long want = target_items / tiles;
     if (want > steps / 8) want = steps / 8;
     if (want < 1) want = 1;

@@ -30,35 +30,7 @@
 
 #include <atomic>
 
-// Phase timing for development builds (python -m sigma_amd.build --variant prof --flags=-DSIGMA_BWD2_PROF=1):
-// every wave accumulates s_memtime deltas per phase and adds them to g_bwd2_prof at the end
-// (sigma_scan_debug_read in capi.hip).  Costs ~10 % run time; compiled out of the product build.
-#ifndef SIGMA_BWD2_PROF
-#define SIGMA_BWD2_PROF 0
-#endif
-#if SIGMA_BWD2_PROF
-__device__ unsigned long long g_bwd2_prof[16];
-#define PROF_DECL long long prof_t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long prof_last = __builtin_readcyclecounter();
-#define PROF(i) { const long long t_ = __builtin_readcyclecounter(); prof_t[i] += t_ - prof_last; prof_last = t_; }
-#define PROF_FLUSH if ((threadIdx.x & 63) == 0) { for (int i_ = 0; i_ < 10; ++i_) atomicAdd(&g_bwd2_prof[i_], (unsigned long long)prof_t[i_]); atomicAdd(&g_bwd2_prof[15], 1ull); }
-#else
-#define PROF_DECL
-#define PROF(i)
-#define PROF_FLUSH
-#endif
-
 namespace sigma {
-
-#if SIGMA_BWD2_PROF
-hipError_t bwd2_prof_read(unsigned long long* out16) {
-    hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_bwd2_prof), 16 * sizeof(unsigned long long));
-    if (e != hipSuccess) return e;
-    unsigned long long z[16] = {0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_bwd2_prof), z, sizeof(z));
-}
-#else
-hipError_t bwd2_prof_read(unsigned long long* out16) { for (int i = 0; i < 16; ++i) out16[i] = 0; return hipSuccess; }
-#endif
 
 namespace {
 
@@ -247,12 +219,10 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
 
     int step = 0;                                      // staging buffer parity
     int cnt = 0;                                       // states processed (slab parity)
-    PROF_DECL
     stage(0, ntiles - 1, 0);
     if constexpr (GLDS) lds_dma_wait();
     __syncthreads();
 
-    PROF(0)
     for (int j = ntiles - 1; j >= 0; --j) {
         const int l0 = j * TILE;
         const int lbase = l0 + lane * T;
@@ -315,13 +285,11 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
                     touch_lines(reinterpret_cast<const io_t*>(kq->dout) + (long)b * kq->g_bs + (long)grn * kq->g_ds + m0, nb, lane, touch_sink);
                 }
             }
-            PROF(1)                                            // row prologue: loads, softplus
             for (int sb = 0; sb < nsb; ++sb) {
                 const float* cur = sBC + (step & 1) * bufsz;
                 if (sb + 1 < nsb) stage(step + 1, j, sb + 1);
                 else if (rb + 1 < RB) stage(step + 1, j, 0);
                 else if (j > 0) stage(step + 1, j - 1, 0);
-                PROF(2)                                        // B/C stage issue
                 const int n0 = sb * NB;
                 const int nend = (N - n0 < NB) ? (N - n0) : NB;
 #pragma unroll 1
@@ -359,7 +327,6 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
 #pragma unroll
                         for (int k = 0; k < T; ++k) { x = fmaf(a[k], x, xs[k]); xs[k] = x; }
                     }
-                    PROF(3)                                    // forward: LDS reads, fold, scan, replay
                     // ---- reverse: e_k = a_k * dx_k, dx_k = g_k C_k + e_{k+1}; lane 63 starts from the carry
                     float e = lane63 ? carry : 0.0f;
 #pragma unroll
@@ -369,7 +336,6 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
                     e = wave_next_lane(e, carry);                  // e entering the lane from the right
                     float dAp = 0.0f;
                     float* sRedN = sRed + ((cnt & (nslab - 1)) ? R * 2 * TILE : 0);
-                    PROF(4)                                    // reverse fold + scan
                     if (nslab == 1) lds_barrier();                 // slab free (previous state summed)
                     {
                         float* __restrict__ slab = sRedN + wave * 2 * TILE + lane * T;
@@ -403,10 +369,8 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
                     }
                     rvout_v = lane_put(e, n, rvout_v);             // lane 0: a*dx of the tile's first element
                     dA_v = lane_put(wave_sum(dAp), n, dA_v);
-                    PROF(5)                                    // reverse replay, slab writes, dA sum
                     // slabs complete; at the end of a staging block also "next B/C block landed"
                     if (nn == nend - 1) { if constexpr (GLDS) lds_dma_wait(); __syncthreads(); } else lds_barrier();
-                    PROF(6)                                    // barrier wait
                     if (col_on) {
                         const float2 s = colsum(sRedN + col_c * TILE + col_pp, 2 * TILE, R);
                         if (RB > 1) {
@@ -423,7 +387,6 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
                         }
                     }
                     ++cnt;
-                    PROF(7)                                    // column sums
                 }
                 ++step;
             }
@@ -467,10 +430,8 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
             store_items<io_t, T, REV>(dd_row, lbase, L, vec, ddv);
             if (ke->dD) { dD_acc = wave_sum(dD_acc); if (lane0) row_result<DET>(ke, ke->dD + pr, b, pr, N, j == ntiles - 1, dD_acc); }
             if (ke->dbias) { dbias_acc = wave_sum(dbias_acc); if (lane0) row_result<DET>(ke, ke->dbias + pr, b, pr, N + 1, j == ntiles - 1, dbias_acc); }
-            PROF(8)                                            // row epilogue
         }
     }
-    PROF_FLUSH
 }
 
 template <typename io_t, int T, bool GLDS, bool DET>

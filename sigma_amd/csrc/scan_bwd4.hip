@@ -28,40 +28,7 @@
 
 #include <atomic>
 
-// phase timing of development builds, as in scan_bwd2.hip (-DSIGMA_BWD2_PROF=1; tools/bwd2_prof.py)
-#ifndef SIGMA_BWD2_PROF
-#define SIGMA_BWD2_PROF 0
-#endif
-#if SIGMA_BWD2_PROF
-__device__ unsigned long long g_bwd4_prof[16];
-#define PROF_DECL long long prof_t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long prof_last = __builtin_readcyclecounter();
-#define PROF(i) { const long long t_ = __builtin_readcyclecounter(); prof_t[i] += t_ - prof_last; prof_last = t_; }
-#define PROF_FLUSH if ((threadIdx.x & 63) == 0) { for (int i_ = 0; i_ < 10; ++i_) atomicAdd(&g_bwd4_prof[i_], (unsigned long long)prof_t[i_]); atomicAdd(&g_bwd4_prof[15], 1ull); }
-#else
-#define PROF_DECL
-#define PROF(i)
-#define PROF_FLUSH
-#endif
-
-// Ablation builds (-DSIGMA_BWD4_ABL=<bits>; results are WRONG, timing only; profiles/r03_bwd4_ablation.txt):
-//   1 no du / ddelta stores   2 no dA / dD / ddelta_bias atomics   4 no column sums (barriers stay)
-//   8 no barriers and no column sums   16 no four-row folds / slab writes   32 no row prologue loads (constants)
-#ifndef SIGMA_BWD4_ABL
-#define SIGMA_BWD4_ABL 0
-#endif
-
 namespace sigma {
-
-#if SIGMA_BWD2_PROF
-hipError_t bwd4_prof_read(unsigned long long* out16) {
-    hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_bwd4_prof), 16 * sizeof(unsigned long long));
-    if (e != hipSuccess) return e;
-    unsigned long long z[16] = {0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_bwd4_prof), z, sizeof(z));
-}
-#else
-hipError_t bwd4_prof_read(unsigned long long* out16) { for (int i = 0; i < 16; ++i) out16[i] = 0; return hipSuccess; }
-#endif
 
 namespace {
 
@@ -189,11 +156,9 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
 
     int buf = 0;
     int grp = 0;                                       // state groups processed (slab set parity)
-    PROF_DECL
     stage(0, t_hi - 1);
     lds_dma_wait();
     __syncthreads();
-    PROF(0)
 
     for (int j = t_hi - 1; j >= t_lo; --j) {
         const int l0 = j * kTile4;
@@ -228,15 +193,9 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
             float dD_acc = 0.0f;                       // sum of dout * u over the lane's positions (zero past the end)
             {
                 float dv[T], uu[T];
-#if SIGMA_BWD4_ABL & 32
-#pragma unroll
-                for (int k = 0; k < T; ++k) { uu[k] = 0.5f + 0.01f * (lane + k); dv[k] = 0.1f * k; gg[k] = 1.0f - 0.02f * k; }
-                asm volatile("" : "+v"(uu[0]), "+v"(dv[0]), "+v"(gg[0]));
-#else
                 load_items<float, T, REV>(u_row, lbase, L, vec, uu);
                 load_items<float, T, REV>(d_row, lbase, L, vec, dv);
                 load_items<float, T, REV>(g_row, lbase, L, vec, gg);
-#endif
 #pragma unroll
                 for (int k = 0; k < T; ++k) {
                     float d = dv[k] + bias;
@@ -254,12 +213,9 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
             for (int k = 0; k < T; ++k) dsum += dl[k];
             // dA / dD / ddelta_bias leave through one atomicAdd per (row, tile) and state.  Summing them over the
             // tiles in LDS first (measured: WRITE_SIZE -6 %) costs the second B/C image its LDS and 3 % run time.
-#if !(SIGMA_BWD4_ABL & 2)
             // (deterministic mode: a plain store to the workgroup's slot, slot k = b * S + seg, added to over the tiles)
             if (kq->dD) { dD_acc = row_sum_to_lane0(dD_acc); if (li0) row_result<DET>(kq, kq->dD + pr, b * kq->S + seg, pr, N, j == t_hi - 1, dD_acc); }
-#endif
 
-            PROF(1)                                            // row prologue: loads, softplus
             // row scalars of state 0; those of state n + 1 are fetched while state n is computed
             float An_nx = row_pick(Av, rowbase4), x0_nx = row_pick(X0v, rowbase4), cy_nx = row_pick(Rvv, rowbase4);
 #pragma unroll 1
@@ -313,7 +269,6 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
                 }
                 const float plane = fast_exp2(A2 * dsum);       // this lane's decay product
                 float pf = plane;
-                PROF(2)                                        // B/C reads, exp, forward fold
                 row_mscan_inclusive(pf, xa);
                 const float xstart = dpp_take<DPP_ROW_SHR1, 0xF>(x0, xa);    // state entering the lane
                 {
@@ -321,7 +276,6 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
 #pragma unroll
                     for (int k = 0; k < T; ++k) { x = fmaf(a[k], x, xs[k]); xs[k] = x; }
                 }
-                PROF(3)                                        // forward scan + replay
                 // ---- reverse: e_k = a_k * dx_k, dx_k = g_k C_k + e_{k+1}; lane 15 of the row starts from the carry
                 float e = li15 ? carry : 0.0f;
 #pragma unroll
@@ -330,7 +284,6 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
                 row_mscan_inclusive_rev(prv, e);
                 e = dpp_take<DPP_ROW_SHL1, 0xF>(carry, e);       // e entering the lane from the right
                 float dAp = 0.0f;
-                PROF(4)                                        // reverse fold + scan
                 const int sidx = ((grp & 1) * SB + (n % SB)) * W + wave;
                 float* __restrict__ slab = sRed + sidx * kCols4 + slab_c0;
 #pragma unroll
@@ -350,27 +303,14 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
                         vc[jj] = gg[k] * xs[k];                  // this row's term of dC[n, l]
                     }
                     // four-row sums: rows of the result = {dB pos 2qq, dB pos 2qq+1, dC pos 2qq, dC pos 2qq+1}
-#if SIGMA_BWD4_ABL & 16
-                    asm volatile("" :: "v"(vb[0]), "v"(vc[0]), "v"(vb[1]), "v"(vc[1]));
-#else
                     slab[2 * qq] = fold16(fold32(vb[0], vc[0]), fold32(vb[1], vc[1]));
-#endif
                 }
                 // collect: lane 0 of each row holds the result of this state; select + rotate, so that after
                 // N states the value of state n sits in lane 16 - N + n
                 rvout_v = row_rotate_left(li0 ? e : rvout_v);
                 const float dA_row = row_sum_to_lane0(dAp);      // all lanes take part: outside the select
                 dA_v = row_rotate_left(li0 ? dA_row : dA_v);
-                PROF(5)                                        // reverse replay, four-row sums, slab writes, collect
-#if SIGMA_BWD4_ABL & 8
-                if (n == N - 1 && rb == RB - 1) {
-                    if (nbuf == 2) { lds_dma_wait(); __syncthreads(); }
-                    else { lds_barrier(); if (j > t_lo) stage(0, j - 1); }
-                }
-                if (false) {
-#else
                 if ((n % SB) == SB - 1) {
-#endif
                     // slabs of this state group complete; at the end of the tile also "next B/C image landed"
                     if (n == N - 1 && rb == RB - 1) {
                         if (nbuf == 2) { lds_dma_wait(); __syncthreads(); }
@@ -378,11 +318,6 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
                     } else {
                         lds_barrier();
                     }
-#if SIGMA_BWD4_ABL & 4
-                    ++grp;
-                    continue;
-#endif
-                    PROF(6)                                    // barrier wait
                     const float* sset = sRed + ((grp & 1) * SB) * W * kCols4;
                     auto column = [&](int s, int c, int pos, bool is_c) {
                         const int ns = n - (SB - 1) + s;
@@ -412,7 +347,6 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
                         }
                     }
                     ++grp;
-                    PROF(7)                                    // column sums
                 }
             }
 
@@ -430,9 +364,7 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
             if (li_e >= vshift) {
                 const int st = li_e - vshift;
                 sRv[rl_e * N + st] = rvout_v;
-#if !(SIGMA_BWD4_ABL & 2)
                 row_result<DET>(ke, ke->dA + (long)pr_e * ke->dA_ds + (long)st * ke->dA_ns, b * ke->S + seg, pr_e, st, j == t_hi - 1, dA_v);
-#endif
             }
             float dbias_acc = 0.0f;
             float* __restrict__ du_row = reinterpret_cast<float*>(ke->du) + (long)b * ke->du_bs + (long)r_e * ke->du_ds;
@@ -467,13 +399,8 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
                         ddv[k] = dd_of(k);
                         dbias_acc += ddv[k];           // zero past the end (dl = 0 there)
                     }
-#if SIGMA_BWD4_ABL & 1
-#pragma unroll
-                    for (int k = 0; k < T; ++k) asm volatile("" :: "v"(duv[k]), "v"(ddv[k]));
-#else
                     store_items<float, T, REV>(du_row, lbase_e, L, vec, duv);
                     store_items<float, T, REV>(dd_row, lbase_e, L, vec, ddv);
-#endif
                 } else {
                     const int rpg2 = ke->f.rows_per_group;
                     const int ur2 = r_e - ((g - (g >> ke->f.u_gshift)) * rpg2);
@@ -491,17 +418,11 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
                     store_items<float, T, REV>(dd_row, lbase_e, L, vec, ddv);
                 }
             }
-#if !(SIGMA_BWD4_ABL & 2)
             if (ke->dbias) { dbias_acc = row_sum_to_lane0(dbias_acc); if (li_e == 0) row_result<DET>(ke, ke->dbias + pr_e, b * ke->S + seg, pr_e, N + 1, j == t_hi - 1, dbias_acc); }
-#else
-            asm volatile("" :: "v"(dbias_acc), "v"(dA_v));
-#endif
-            PROF(8)                                            // row epilogue
         }
         if (nbuf == 2) buf ^= 1;
         else if (j > t_lo) { lds_dma_wait(); __syncthreads(); }
     }
-    PROF_FLUSH
 }
 
 template <bool DET>

@@ -24,33 +24,13 @@
 #include <atomic>
 #include <type_traits>
 
-// 1: u / delta / dout of the next tile travel by LDS-DMA (12 KB of LDS more: two workgroups per CU); 0: in registers
-#ifndef SIGMA_RL_DMA
-#define SIGMA_RL_DMA 1
-#endif
-
-// A/B build knob (round 5, measured and NOT taken: profiles/r05_bwdr_mfma_reduce_ab.txt).  1: the dB / dC terms of a
-// (position, state) are summed over the 64 lanes (= rows) of a wave on the MATRIX pipe -- v_mfma_f32_16x16x4_f32 with the
-// term as the A operand (A[i = lane & 15][k = lane >> 4]) and a one-hot B (column c = the position) adds the 4-lane sums
-// sum_k term[i + 16 k] into column c of a 16 x 16 accumulator (exact fp32), 128 MFMAs per tile and wave instead of 96 lane
-// swaps + 60 DPP adds.  Results identical to the oracle's tolerance, but (16,3072,1200,N16) runs in 1083 us against 748:
-// the f32 MFMA holds its SIMD for ~80 clocks next to dependent VALU work, not the 32 of a bare MFMA stream.
-// 0 (default): the transpose-reduce network on the vector ALU.
-// 1: B / C of the next tile are pulled into L2 a tile ahead by one vector load per wave (round 4); 0: A/B builds without
-// development only: a deliberately mis-counted wait (tests/test_isa_waits_cpu.py must refuse such a build)
+// The one build switch of the kernels: a wait that keeps SIGMA_BWDR_WAIT_SKEW vector-memory operations too many in flight.
+// It exists only for the negative case of tests/test_isa_waits_cpu.py, which compiles a mis-counted build to prove that its
+// ISA check refuses one.  The product build leaves it at 0.
 #ifndef SIGMA_BWDR_WAIT_SKEW
 #define SIGMA_BWDR_WAIT_SKEW 0
 #endif
-#ifndef SIGMA_BWDR_TOUCH
-#define SIGMA_BWDR_TOUCH 1
-#endif
-#ifndef SIGMA_RL_MFMA
-#define SIGMA_RL_MFMA 0
-#endif
 
-#if SIGMA_RL_PROF
-__device__ unsigned long long g_bwdr_prof[16];
-#endif
 __device__ unsigned int g_bwdr_chain_timeouts;     // chained walk: hand-over waits that ran out (their row blocks were poisoned)
 
 namespace sigma {
@@ -62,17 +42,6 @@ hipError_t bwdr_chain_timeouts_read(unsigned int* out) {
     const unsigned int z = 0;
     return hipMemcpyToSymbol(HIP_SYMBOL(g_bwdr_chain_timeouts), &z, sizeof(z));
 }
-
-#if SIGMA_RL_PROF
-hipError_t bwdr_prof_read(unsigned long long* out16) {
-    hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_bwdr_prof), 16 * sizeof(unsigned long long));
-    if (e != hipSuccess) return e;
-    unsigned long long z[16] = {0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_bwdr_prof), z, sizeof(z));
-}
-#else
-hipError_t bwdr_prof_read(unsigned long long* out16) { for (int i = 0; i < 16; ++i) out16[i] = 0; return hipSuccess; }
-#endif
 
 namespace {
 
@@ -131,39 +100,10 @@ __device__ __forceinline__ float rl_reduce_finish(float p0, float p1) {
     return o;
 }
 
-typedef float v8f_a16 __attribute__((ext_vector_type(8), aligned(16)));
-typedef const __attribute__((address_space(4))) v8f_a16* cv8p_t;
-
-// B or C of one (state, half tile): 8 consecutive floats at a wave-uniform address -> SGPRs; nch = valid 16-byte chunks
-// of the half (2 except in a partial last tile), missing ones read as zero
-__device__ __forceinline__ void rl_load_bc8(const float* base, int nch, float (&v)[8]) {
-#if SIGMA_RL_ABL & 1
-    float c = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane((int)(reinterpret_cast<uintptr_t>(base) & 0xffff) | 0x3f000000));
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { v[k] = c; asm volatile("" : "+s"(c)); }
-    return;
-#endif
-    if (nch >= 2) {
-        const auto t = *reinterpret_cast<cv8p_t>(reinterpret_cast<uintptr_t>(base));
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = t[k];
-    } else {
-        const v4f z = {0.0f, 0.0f, 0.0f, 0.0f};
-        const v4f c0 = nch > 0 ? *reinterpret_cast<cv4p_t>(reinterpret_cast<uintptr_t>(base)) : z;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { v[j] = c0[j]; v[4 + j] = 0.0f; }
-    }
-}
-
 // 16 bytes of a row; `ok` false: zeros (the load itself always runs, from the row start, so that the VMEM operations of a
 // tile are the same on every path and the compiler's vmcnt bookkeeping stays exact instead of falling back to vmcnt(0))
 __device__ __forceinline__ v4f rl_load4u(const float* __restrict__ row, int off, bool ok) {
     const v4f z = {0.0f, 0.0f, 0.0f, 0.0f};
-#if SIGMA_RL_ABL & 4
-    const float c = 0.001f * (float)((reinterpret_cast<uintptr_t>(row) + off) & 0xff);
-    const v4f tc = {c, 0.5f * c, 0.25f * c, -c};
-    return ok ? tc : z;
-#endif
     const v4f t = *reinterpret_cast<const v4f*>(row + (ok ? off : 0));
     return ok ? t : z;
 }
@@ -173,10 +113,9 @@ __device__ __forceinline__ v4f rl_load4u(const float* __restrict__ row, int off,
 // ---------------------------------------------------------------------------------------------------------------------
 // The backward proper.  A workgroup is one block of 64 rows x 4 state waves (NS = dstate / 4 states each).  Per tile of 16
 // positions: the (row, chunk) threads pre-process u / delta / dout once (softplus, delta * u, softplus') into LDS; then
-// the tile is walked as TWO halves of 8 positions, second half in scan order first.  Per half every wave runs, for each of
-// its states: forward replay of the half from the forward's checkpoint (pitch 8), the reverse recurrence, the sums over
-// the states of dx B and A2 dx a x_prev in 16 registers, and the lane-reduce of the dB / dC terms.  Halves rather than
-// whole tiles keep the per-lane arrays at 8 entries (~120 VGPRs, 3-4 waves per SIMD) where whole tiles need > 200.
+// every wave runs, for each of its states: forward replay of the tile from the forward's checkpoint (one per tile,
+// scan_rowlane.h), the reverse recurrence, the sums over the states of dx B and A2 dx a x_prev in 16 registers, and the
+// lane-reduce of the dB / dC terms.
 // One piece of work: scan steps [st_lo, st_hi) of one row block, walked from the last to the first.  The reverse carry
 // entering at st_hi is zero (cin 0: the end of the sequence), the composition of the segment summaries (cin 1), or handed
 // over by the workgroup that walked the steps above (cin 2: chained walk); cout: this piece hands its carry on.
@@ -197,11 +136,7 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
     const int ntiles = (L + T - 1) / T;
     v4f* sProc = reinterpret_cast<v4f*>(smem);                    // [5][4][64] float4: delta, delta * u, dout; u, softplus' (epilogue)
     v4f* sEx = sProc + 5 * 256;                                   // [4 waves][2][4][64] float4: sum dx B, sum A2 dx a x_prev
-#if SIGMA_RL_ABL & 128
-    v4f* sRaw = sEx + 4 * 256;
-#else
     v4f* sRaw = sEx + 8 * 256;                                    // [3][256 threads] float4: u, delta, dout of the NEXT tile (LDS-DMA)
-#endif
     const unsigned raw_base = (unsigned)(uintptr_t)(lptr_t)(sRaw + sw * 64);   // this wave's 1 KB of array 0
 
     // thread as (row, chunk)
@@ -241,13 +176,8 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
     const float* Cw = reinterpret_cast<const float*>(p.C) + (long)b * p.C_bs + (long)g * p.C_gs + (long)n0 * p.C_ns;
     const int B_ns = (int)p.B_ns, C_ns = (int)p.C_ns;               // host: (N - 1) * stride + L fits 31 bits
     const long rowblock = (long)b * (p.dim >> 6) + (row0 >> 6);
-    // checkpoints: x[((rowblock * ntiles + tile) * 2 + h) * N + n) * 64 + lane], h = 0 after the first scan half of the tile
-#if SIGMA_BWDR_FULL
-    // checkpoints (one per tile): x[((rowblock * ntiles + tile) * N + n) * 64 + lane] = state after memory tile `tile` in scan order
+    // checkpoints (one per tile): x[(rowblock * ntiles + tile) * N * 64 + rl_ck_slot(n, lane)] = state after memory tile `tile` in scan order
     const float* ck = p.x + rowblock * ntiles * N * 64;                         // wave-uniform; rl_load_ck adds the wave's slot
-#else
-    const float* ck = p.x + rowblock * ntiles * 2 * N * 64 + (long)n0 * 64;     // wave-uniform; + lane at the use
-#endif
 
     // dB / dC of this row block: the caller's tensors when the block is the whole group, else its slab of the workspace
     float* __restrict__ oB;
@@ -260,17 +190,8 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
         const long slab = (((long)rbg * p.batch + b) * p.G + g) * (long)N * L;
         oB = q.ws_dB + slab; oC = q.ws_dC + slab; o_nsB = L; o_nsC = L;
     }
-#if SIGMA_RL_MFMA
-    // after the folds of the accumulators (below) lane l holds the total of array l >> 5 at memory position l & 15 (lanes l
-    // and l ^ 16 hold the same total and store it twice)
-    const int o_pos = lane & 15;
-    float oh[T];                                                    // B operand of the reducing MFMA: one-hot column c
-#pragma unroll
-    for (int c = 0; c < T; ++c) oh[c] = (lane & 15) == c ? 1.0f : 0.0f;
-#else
     // lane l of rl_reduce_finish: array l >> 5, memory position below (lanes l and l ^ 1 hold the same total and store it twice)
     const int o_pos = ((lane >> 1) & 1) * 8 + ((lane >> 2) & 1) * 2 + ((lane >> 3) & 1) + ((lane >> 4) & 1) * 4;
-#endif
     float* __restrict__ o_lane = (lane < 32 ? oB + (long)n0 * o_nsB : oC + (long)n0 * o_nsC) + o_pos;
     const int o_ns_lane = (int)(lane < 32 ? o_nsB : o_nsC);
 
@@ -327,22 +248,6 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
         }
     }
     auto tile_of = [&](int st) { return REV ? (ntiles - 1 - st) : st; };   // memory tile of scan step st
-    // state entering scan half hs of scan step st: after the first half of the same tile / after the previous tile
-    // (before the first scan step there is no checkpoint: the load is clamped to a valid one and the caller scales by zero
-    // at the point of USE -- a select next to the load would make the compiler wait for it there)
-    [[maybe_unused]] auto ck_in = [&](int st, int hs, int s) {
-#if SIGMA_RL_ABL & 2
-        return 0.001f * st;
-#endif
-#if SIGMA_BWDR_FULL
-        (void)hs; (void)s;
-        return 0.0f;                                                // (the whole-tile walk loads its NS states at once: ck_load)
-#else
-        const int tl = hs == 1 ? tile_of(st) : tile_of(st > 0 ? st - 1 : 0);
-        return ck[(unsigned)(((tl * 2 + (hs == 1 ? 0 : 1)) * N + s) * 64 + lane)];      // host: floats per row block < 2^31
-#endif
-    };
-
     // u / delta / dout of a tile travel by LDS-DMA one tile ahead (with register targets the compiler, short of
     // registers, moved the requests next to their use: three exposed memory latencies per tile).  Chunks past the end of
     // the row are requested at the row start (finite values) and masked when they are read back.
@@ -354,33 +259,18 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
     };
     int st = st_hi - 1;
     int m = tile_of(st);
-#if SIGMA_RL_DMA
     request(m);
-#else
-    v4f u_nx = rl_load4u(u_blk + u_off - 4 * cc, T * m + 4 * cc, T * m + 4 * cc < L);
-    v4f d_nx = rl_load4u(d_blk + d_off - 4 * cc, T * m + 4 * cc, T * m + 4 * cc < L);
-    v4f g_nx = rl_load4u(g_blk + g_off - 4 * cc, T * m + 4 * cc, T * m + 4 * cc < L);
-#endif
-    float x1_nx[NS];                                                // entering the second scan half of the next step (FULL: entering the next step)
-#if SIGMA_BWDR_FULL
+    float x1_nx[NS];                                                // the states entering the next step
     // the NS states entering scan step st_ = those after the previous step's tile: one access per lane (before the first
-    // step there is none: the load is clamped to a valid block and the value scaled by zero where it is used)
+    // step there is none: the load is clamped to a valid block and the value scaled by zero where it is used -- a select
+    // next to the load would make the compiler wait for it there)
     auto ck_load = [&](int st_, float (&xo)[NS]) {
-#if SIGMA_RL_ABL & 2
-        for (int s = 0; s < NS; ++s) xo[s] = 0.001f * st_;
-        return;
-#endif
         rl_load_ck<NS, NS>(ck + (unsigned)(tile_of(st_ > 0 ? st_ - 1 : 0) * N * 64), n0, lane, xo);      // host: floats per row block < 2^31
     };
     ck_load(st, x1_nx);
-#else
-#pragma unroll
-    for (int s = 0; s < NS; ++s) x1_nx[s] = ck_in(st, 1, s);
-#endif
     // B / C of the NEXT tile are pulled into L2 a tile ahead (see scan_fwdr.hip)
     const float* __restrict__ bc_touch = ((lane & 1) ? Cw : Bw) + (long)((lane >> 1) & (NS - 1)) * ((lane & 1) ? C_ns : B_ns);
     float touch_nx = 0.0f, touch_acc = 0.0f;
-    RLPROF_DECL
 
     auto step = [&](int it, auto tail_tag) {
         constexpr bool TAIL = decltype(tail_tag)::value;
@@ -388,70 +278,36 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
         m = tile_of(st);
         const bool valid = !TAIL || T * m + 4 * cc < L;
         const int nch = TAIL ? (L - T * m) >> 2 : 4;                // valid 16-byte chunks of this tile
-        const int hm_first = REV ? 0 : 1;                           // memory half of the second scan half (walked first)
-#if SIGMA_BWDR_FULL
-        (void)hm_first;
         float Bn[T], Cn[T];
         rl_load_bc(Bw + T * m, nch, Bn);                            // first state's B / C: requested before anything waits
         rl_load_bc(Cw + T * m, nch, Cn);
-#else
-        float Bn[H], Cn[H];
-        rl_load_bc8(Bw + T * m + H * hm_first, nch - 2 * hm_first, Bn);      // first step's B / C: requested before anything waits
-        rl_load_bc8(Cw + T * m + H * hm_first, nch - 2 * hm_first, Cn);
-#endif
         __builtin_amdgcn_sched_barrier(0);
-#if SIGMA_RL_DMA
-        // This tile's u / delta / dout have landed.  A full step of the loop issues 3 + 2 NS vector-memory operations
-        // after its requests (the touch, NS checkpoint loads, NS dB/dC stores, du, ddelta), which stay in
+        // This tile's u / delta / dout have landed.  A full step of the loop issues 4 + NS vector-memory operations
+        // after its requests (the touch, ONE checkpoint load, NS dB/dC stores, du, ddelta), which stay in
         // flight; the partial tile may skip some of them, so it (and the step after it: the caller waits) drains the counter.
-        // (whole-tile walk: the touch, ONE checkpoint load, NS dB/dC stores, du, ddelta)
-        if (TAIL) rl_dma_wait(); else rl_dma_wait_keep<(SIGMA_BWDR_FULL ? 3 + NS : 2 + 2 * NS) + (SIGMA_BWDR_TOUCH ? 1 : 0) + SIGMA_BWDR_WAIT_SKEW>();
-        RLPROF(8)                                                   // wait for this tile's u / delta / dout (LDS-DMA)
+        if (TAIL) rl_dma_wait(); else rl_dma_wait_keep<4 + NS + SIGMA_BWDR_WAIT_SKEW>();
         const v4f uu = sRaw[tid], dd = sRaw[256 + tid];
         v4f g4 = sRaw[512 + tid];
         const v4f zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
         g4 = valid ? g4 : zero4;                                    // dout reads as zero past the end
-#else
-        const v4f uu = u_nx, dd = d_nx, g4 = g_nx;
-#endif
-        float x1[NS], x0[NS];
-        const float x0_scale = st > 0 ? 1.0f : 0.0f; (void)x0_scale;
+        float x1[NS];
         touch_acc += touch_nx;
-#if SIGMA_BWDR_FULL
 #pragma unroll
-        for (int s = 0; s < NS; ++s) { x1[s] = x1_nx[s]; x0[s] = 0.0f; }               // x1: the state entering this tile
-#else
-#pragma unroll
-        for (int s = 0; s < NS; ++s) { x1[s] = x1_nx[s]; x0[s] = ck_in(st, 0, s); }     // x0: used half a tile from now
-#endif
+        for (int s = 0; s < NS; ++s) x1[s] = x1_nx[s];                                   // x1: the state entering this tile
         {                                                           // next tile's operands fly during this tile
             const bool more = it + 1 < nst;
             const int mn = tile_of(more ? st - 1 : st);
-#if SIGMA_RL_DMA
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the reads of this tile's bytes are done
-            RLPROF(9)                                               // raw operand reads back from LDS (+ B / C of the first state)
             request(mn);
-#else
-            u_nx = rl_load4u(u_blk + u_off - 4 * cc, T * mn + 4 * cc, more && T * mn + 4 * cc < L);
-            d_nx = rl_load4u(d_blk + d_off - 4 * cc, T * mn + 4 * cc, more && T * mn + 4 * cc < L);
-            g_nx = rl_load4u(g_blk + g_off - 4 * cc, T * mn + 4 * cc, more && T * mn + 4 * cc < L);
-#endif
-#if SIGMA_BWDR_TOUCH
             touch_nx = bc_touch[T * mn];
-#endif
         }
-        RLPROF(10)                                                  // requests of the next tile
         {
             v4f dl4, dlu4, sg4;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float raw = dd[j] + bias;
                 float sig;
-#if SIGMA_RL_ABL & 32
-                const float sp = raw * raw; sig = 1.0f;
-#else
                 const float sp = softplus_ref(raw, sig);
-#endif
                 float d = p.softplus ? sp : raw;
                 sg4[j] = p.softplus ? sig : 1.0f;
                 d = valid ? d : 0.0f;                               // identity element past the end (a = 1, b = 0)
@@ -466,11 +322,8 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
             sProc[768 + rl_unit(cc, rr)] = uu;
             sProc[1024 + rl_unit(cc, rr)] = sg4;
         }
-        RLPROF(0)                                                   // operand wait, softplus, LDS writes
-        rl_barrier();
-        RLPROF(1)                                                   // barrier 1
+        lds_barrier();
 
-#if SIGMA_BWDR_FULL
         {
             float dl[T], dlu[T], gg[T], sdxB[T], sAx[T];
 #pragma unroll
@@ -486,7 +339,6 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
             asm volatile("" : "+v"(dl[0]), "+v"(dlu[0]), "+v"(gg[0]), "+v"(dl[4]), "+v"(dlu[4]), "+v"(gg[4]),
                               "+v"(dl[8]), "+v"(dlu[8]), "+v"(gg[8]), "+v"(dl[12]), "+v"(dlu[12]), "+v"(gg[12]));
             __builtin_amdgcn_sched_barrier(0);
-            RLPROF(2)                                               // LDS reads
             const float xin_scale = st > 0 ? 1.0f : 0.0f;
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
@@ -496,7 +348,6 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
                 // scalar loads return out of order: wait for THIS state's operands (lgkmcnt(0)), then request the next state's
                 asm volatile("" : "+s"(Bt[0]), "+s"(Ct[0]));
                 __builtin_amdgcn_sched_barrier(0);
-                RLPROF(3)                                           // scalar operand wait
                 if (s + 1 < NS) {
                     rl_load_bc(Bw + (s + 1) * B_ns + T * m, nch, Bn);
                     rl_load_bc(Cw + (s + 1) * C_ns + T * m, nch, Cn);
@@ -529,34 +380,18 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
                     const float t = e * xprev;                      // dx * a_k * x_{k-1}
                     sAx[k] = fmaf(A2[s], t, sAx[k]);                // x ln 2 in the epilogue
                     dAacc[s] = fmaf(dl[k], t, dAacc[s]);
-#if SIGMA_RL_ABL & 64
-                    w[k & 7] = dx * dlu[k] + gg[k] * xs[k];
-#else
                     w[k & 7] = rl_fold32(dx * dlu[k], gg[k] * xs[k]);  // this row's terms of dB[n, l] and dC[n, l], wave halves summed
-#endif
                     if (kk == H) {                                  // the half walked first is complete: memory half REV ? 0 : 1
-#if SIGMA_RL_ABL & 64
-                        ph_first = ((w[0] + w[1]) + (w[2] + w[3])) + ((w[4] + w[5]) + (w[6] + w[7]));
-#else
                         ph_first = rl_reduce_half(w);
-#endif
                     }
                 }
                 ecar[s] = e;
-#if SIGMA_RL_ABL & 64
-                const float tot = ph_first + (((w[0] + w[1]) + (w[2] + w[3])) + ((w[4] + w[5]) + (w[6] + w[7])));
-#else
                 const float ph_second = rl_reduce_half(w);          // memory half REV ? 1 : 0
                 const float tot = REV ? rl_reduce_finish(ph_first, ph_second) : rl_reduce_finish(ph_second, ph_first);
-#endif
                 if (!TAIL || T * m + o_pos < L) o_lane[s * o_ns_lane + T * m] = tot;
                 __builtin_amdgcn_sched_barrier(0);
-                RLPROF(4)                                           // state loop
             }
             // ---- the sums over the states of the four waves meet in LDS
-#if SIGMA_RL_ABL & 16
-            asm volatile("" :: "v"(sdxB[0]), "v"(sdxB[5]), "v"(sAx[2]), "v"(sAx[7]), "v"(sdxB[9]), "v"(sAx[14]));
-#else
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const v4f t1 = {sdxB[4 * c], sdxB[4 * c + 1], sdxB[4 * c + 2], sdxB[4 * c + 3]};
@@ -564,176 +399,15 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
                 sEx[(sw * 2) * 256 + rl_unit(c, lane)] = t1;
                 sEx[(sw * 2 + 1) * 256 + rl_unit(c, lane)] = t2;
             }
-#endif
             ck_load(it + 1 < nst ? st - 1 : st, x1_nx);              // the states entering the NEXT step
-            RLPROF(5)                                               // exchange writes
         }
-#else
-#if SIGMA_RL_MFMA
-        float psB[NS], psC[NS];                                     // 4-lane sums of the half walked first, per state
-#else
-        float psave[NS];
-#endif
-#pragma unroll
-        for (int hs = 1; hs >= 0; --hs) {
-            const int hm = REV ? 1 - hs : hs;                       // memory half
-            float dl[H], dlu[H], gg[H], sdxB[H], sAx[H];
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const v4f a4 = sProc[rl_unit(2 * hm + c, lane)], b4 = sProc[256 + rl_unit(2 * hm + c, lane)];
-                const v4f g4r = sProc[512 + rl_unit(2 * hm + c, lane)];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    dl[4 * c + j] = a4[j]; dlu[4 * c + j] = b4[j]; gg[4 * c + j] = g4r[j];
-                    sdxB[4 * c + j] = 0.0f; sAx[4 * c + j] = 0.0f;
-                }
-            }
-            // LDS reads and scalar loads share one counter: retire the reads before the first scalar request of the state
-            // loop, or its wait for them (lgkmcnt(0)) would also sit out that request
-            asm volatile("" : "+v"(dl[0]), "+v"(dlu[0]), "+v"(gg[0]), "+v"(dl[4]), "+v"(dlu[4]), "+v"(gg[4]));
-            __builtin_amdgcn_sched_barrier(0);
-            RLPROF(2)                                               // LDS reads
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                float Bt[H], Ct[H];
-#pragma unroll
-                for (int k = 0; k < H; ++k) { Bt[k] = Bn[k]; Ct[k] = Cn[k]; }
-                // Scalar loads return out of order, so every wait on them is lgkmcnt(0): the operands of THIS step are
-                // waited for here, BEFORE the requests of the next step are issued -- which then have a whole step to arrive.
-                asm volatile("" : "+s"(Bt[0]), "+s"(Ct[0]));
-                __builtin_amdgcn_sched_barrier(0);
-                RLPROF(3)                                           // scalar operand wait
-                if (s + 1 < NS) {
-                    rl_load_bc8(Bw + (s + 1) * B_ns + T * m + H * hm, nch - 2 * hm, Bn);
-                    rl_load_bc8(Cw + (s + 1) * C_ns + T * m + H * hm, nch - 2 * hm, Cn);
-                } else if (hs == 1) {                               // first state of the other half
-                    rl_load_bc8(Bw + T * m + H * (1 - hm), nch - 2 * (1 - hm), Bn);
-                    rl_load_bc8(Cw + T * m + H * (1 - hm), nch - 2 * (1 - hm), Cn);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const float xin = hs == 1 ? x1[s] : x0[s] * x0_scale;
-                float a[H], xs[H];
-                // ---- forward replay from the checkpoint
-                {
-                    float x = xin;
-#pragma unroll
-                    for (int kk = 0; kk < H; ++kk) {
-                        const int k = REV ? H - 1 - kk : kk;
-                        a[k] = fast_exp2(dl[k] * A2[s]);
-                        x = fmaf(a[k], x, dlu[k] * Bt[k]);
-                        xs[k] = x;
-                    }
-                }
-                // ---- reverse: dx_k = g_k C_k + e_{k+1}, e_k = a_k dx_k
-                float e = ecar[s];
-#if SIGMA_RL_MFMA
-                v4f accB = {0.0f, 0.0f, 0.0f, 0.0f}, accC = {0.0f, 0.0f, 0.0f, 0.0f};
-#else
-                float w[H];
-#endif
-#pragma unroll
-                for (int kk = H - 1; kk >= 0; --kk) {
-                    const int k = REV ? H - 1 - kk : kk;
-                    const float dx = fmaf(gg[k], Ct[k], e);
-                    e = a[k] * dx;
-                    const int kp = REV ? k + 1 : k - 1;             // previous position in scan order
-                    const float xprev = kk > 0 ? xs[kk > 0 ? kp : k] : xin;
-                    sdxB[k] = fmaf(dx, Bt[k], sdxB[k]);
-                    const float t = e * xprev;                      // dx * a_k * x_{k-1}
-                    sAx[k] = fmaf(A2[s], t, sAx[k]);                // x ln 2 in the epilogue
-                    dAacc[s] = fmaf(dl[k], t, dAacc[s]);
-                    // this row's terms of dB[n, l] and dC[n, l]
-#if SIGMA_RL_MFMA
-#if SIGMA_RL_ABL & 64
-                    accB[0] += dx * dlu[k]; accC[0] += gg[k] * xs[k];
-#else
-                    accB = __builtin_amdgcn_mfma_f32_16x16x4f32(dx * dlu[k], oh[H * hm + k], accB, 0, 0, 0);
-                    accC = __builtin_amdgcn_mfma_f32_16x16x4f32(gg[k] * xs[k], oh[H * hm + k], accC, 0, 0, 0);
-#endif
-                }
-                ecar[s] = e;
-                // accumulator of lane l: column l & 15 (position), rows 4 (l >> 4) + r of the 16 four-lane sums
-                const float tB = (accB[0] + accB[1]) + (accB[2] + accB[3]), tC = (accC[0] + accC[1]) + (accC[2] + accC[3]);
-                if (hs == 1) {
-                    psB[s] = tB; psC[s] = tC;                       // columns of the other half are zero in these
-                } else {
-#if SIGMA_RL_ABL & 64
-                    const float tot = (tB + psB[s]) + (tC + psC[s]);
-#else
-                    // lanes l, l + 16, l + 32, l + 48 hold the four quarters of position l & 15: wave halves (dB to lanes
-                    // 0-31, dC to 32-63), then DPP row pairs
-                    const float f = rl_fold32(tB + psB[s], tC + psC[s]);
-                    const float tot = rl_fold16(f, f);
-#endif
-                    if (!TAIL || T * m + o_pos < L) o_lane[s * o_ns_lane + T * m] = tot;
-                }
-#else
-                    // ... the two wave halves summed at once
-#if SIGMA_RL_ABL & 64
-                    w[k] = dx * dlu[k] + gg[k] * xs[k];
-#else
-                    w[k] = rl_fold32(dx * dlu[k], gg[k] * xs[k]);
-#endif
-                }
-                ecar[s] = e;
-#if SIGMA_RL_ABL & 64
-                const float ph = ((w[0] + w[1]) + (w[2] + w[3])) + ((w[4] + w[5]) + (w[6] + w[7]));
-#else
-                const float ph = rl_reduce_half(w);
-#endif
-                if (hs == 1) {
-                    psave[s] = ph;
-                } else {
-#if SIGMA_RL_ABL & 64
-                    const float tot = ph + psave[s];
-#else
-                    const float tot = hm == 0 ? rl_reduce_finish(ph, psave[s]) : rl_reduce_finish(psave[s], ph);
-#endif
-                    if (!TAIL || T * m + o_pos < L) o_lane[s * o_ns_lane + T * m] = tot;
-                }
-#endif
-                __builtin_amdgcn_sched_barrier(0);
-                RLPROF(4)                                           // state loop
-            }
-            // ---- the sums over the states of the four waves meet in LDS
-#if SIGMA_RL_ABL & 16
-            asm volatile("" :: "v"(sdxB[0]), "v"(sdxB[5]), "v"(sAx[2]), "v"(sAx[7]));
-#else
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const v4f t1 = {sdxB[4 * c], sdxB[4 * c + 1], sdxB[4 * c + 2], sdxB[4 * c + 3]};
-                const v4f t2 = {sAx[4 * c], sAx[4 * c + 1], sAx[4 * c + 2], sAx[4 * c + 3]};
-#if SIGMA_RL_ABL & 128
-                sEx[((sw & 1) * 2) * 256 + rl_unit(2 * hm + c, lane)] = t1;
-                sEx[((sw & 1) * 2 + 1) * 256 + rl_unit(2 * hm + c, lane)] = t2;
-#else
-                sEx[(sw * 2) * 256 + rl_unit(2 * hm + c, lane)] = t1;
-                sEx[(sw * 2 + 1) * 256 + rl_unit(2 * hm + c, lane)] = t2;
-#endif
-            }
-#endif
-            if (hs == 1) {                                          // entering the second scan half of the NEXT step
-                const int stn = it + 1 < nst ? st - 1 : st;
-#pragma unroll
-                for (int s = 0; s < NS; ++s) x1_nx[s] = ck_in(stn, 1, s);
-            }
-            RLPROF(5)                                               // exchange writes
-        }
-#endif
-        rl_barrier();
-        RLPROF(6)                                                   // barrier 2
+        lds_barrier();
         {
             v4f S1 = {0.0f, 0.0f, 0.0f, 0.0f}, S2 = {0.0f, 0.0f, 0.0f, 0.0f};
-#if !(SIGMA_RL_ABL & 16)
 #pragma unroll
-            for (int w = 0; w < 4; ++w) { S1 += sEx[((w & (SIGMA_RL_ABL & 128 ? 1 : 3)) * 2) * 256 + rl_unit(cc, rr)]; S2 += sEx[((w & (SIGMA_RL_ABL & 128 ? 1 : 3)) * 2 + 1) * 256 + rl_unit(cc, rr)]; }
-#endif
+            for (int w = 0; w < 4; ++w) { S1 += sEx[(w * 2) * 256 + rl_unit(cc, rr)]; S2 += sEx[(w * 2 + 1) * 256 + rl_unit(cc, rr)]; }
             const v4f dle = sProc[rl_unit(cc, rr)], ge = sProc[512 + rl_unit(cc, rr)];
             const v4f ue = sProc[768 + rl_unit(cc, rr)], sge = sProc[1024 + rl_unit(cc, rr)];
-#if SIGMA_RL_PROF
-            asm volatile("" : "+v"(S1), "+v"(S2));
-#endif
-            RLPROF(11)                                              // epilogue: exchange reads
             v4f duv, ddv;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -746,27 +420,21 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
                 *reinterpret_cast<v4f*>(dd_blk + (unsigned)(dd_off + T * m)) = ddv;
             }
         }
-        RLPROF(7)                                                   // epilogue
     };
     // The partial tile (fewer than 16 positions: the memory-last one) is the first step of a forward group and the last
     // of a reversed one: it is peeled off the loop.  With both variants of the body inside ONE loop the register
     // allocation of the whole loop doubled (254 instead of 128 VGPRs at 16 states).
     const int tail_tile = (L % T) ? ntiles - 1 : -1;                // memory tile with fewer than 16 positions
     int it0 = 0, it1 = nst;
-#if SIGMA_RL_DMA
     rl_dma_wait();                                                  // the first requests: nothing younger behind them yet
-#endif
     if (!REV && nst > 0 && tile_of(st_hi - 1) == tail_tile) {
         step(0, std::true_type{});
         it0 = 1;
-#if SIGMA_RL_DMA
         rl_dma_wait();
-#endif
     }
     if (REV && nst > 0 && tile_of(st_lo) == tail_tile) it1 = nst - 1;
     for (int it = it0; it < it1; ++it) step(it, std::false_type{});
     if (it1 < nst) step(it1, std::true_type{});
-    RLPROF_FLUSH(g_bwdr_prof)
     if (pc.cout) {
         // hand the reverse carry to the workgroup that walks the steps below: plain stores, barrier, one lane releases
         // at agent scope, drains its stores (the compiler may drop the wait: asm) and raises the flag
@@ -861,7 +529,7 @@ __device__ __forceinline__ void scan_bwdr_summary_body(const BwdArgs& q, float* 
         }
         sProc[rl_unit(cc, rr)] = dl4;
         sProc[256 + rl_unit(cc, rr)] = g4;
-        rl_barrier();
+        lds_barrier();
         float dl[T], gg[T];
         float dsum = 0.0f;
 #pragma unroll
@@ -883,7 +551,7 @@ __device__ __forceinline__ void scan_bwdr_summary_body(const BwdArgs& q, float* 
             ecar[s] = e;
             Pacc[s] = fmaf(dsum, A2[s], Pacc[s]);
         }
-        rl_barrier();
+        lds_barrier();
     }
     float2* __restrict__ sm = reinterpret_cast<float2*>(q.summ);
 #pragma unroll
@@ -896,11 +564,8 @@ __device__ __forceinline__ void scan_bwdr_summary_body(const BwdArgs& q, float* 
 // Waves per SIMD the register allocation is sized for: the 64 KB of LDS of the backward proper (bwdr_lds_bytes) admit two
 // workgroups per CU = 2 waves per SIMD = 256 VGPRs; asking for 3 (round 4) capped the 16-state build at 168 VGPRs with 81
 // spilled to scratch for an occupancy the LDS never allowed.
-#ifndef SIGMA_BWDR_WPS
-#define SIGMA_BWDR_WPS 2
-#endif
 template <int NS, int MODE>
-__global__ void __launch_bounds__(256, MODE == 1 ? 4 : SIGMA_BWDR_WPS)
+__global__ void __launch_bounds__(256, MODE == 1 ? 4 : 2)
 scan_bwdr_kernel(const BwdArgs q) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int ntiles = (q.f.L + kRT - 1) / kRT;

@@ -18,22 +18,7 @@
 #include <atomic>
 #include <type_traits>
 
-#if SIGMA_RL_PROF
-__device__ unsigned long long g_fwdr_prof[16];
-#endif
-
 namespace sigma {
-
-#if SIGMA_RL_PROF
-hipError_t fwdr_prof_read(unsigned long long* out16) {
-    hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_fwdr_prof), 16 * sizeof(unsigned long long));
-    if (e != hipSuccess) return e;
-    unsigned long long z[16] = {0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_fwdr_prof), z, sizeof(z));
-}
-#else
-hipError_t fwdr_prof_read(unsigned long long* out16) { for (int i = 0; i < 16; ++i) out16[i] = 0; return hipSuccess; }
-#endif
 
 // MODE 0: out only (inference, x == NULL); 1: out + checkpoints; 2: the pre-pass of the sequence split -- recurrence only
 // (no C, no out, no checkpoints), the segment's (P, X) pairs to p.fsumm.  A template parameter rather than a run-time
@@ -80,13 +65,7 @@ __device__ __forceinline__ void scan_fwdr_body(const FwdArgs& p, float* smem, in
     const float* Bg = reinterpret_cast<const float*>(p.B) + (long)b * p.B_bs + (long)g * p.B_gs;
     const float* Cg = reinterpret_cast<const float*>(p.C) + (long)b * p.C_bs + (long)g * p.C_gs;
     const long rowblock = (long)b * (p.dim >> 6) + (row0 >> 6);
-    // checkpoints (pitch 8): x[(((rowblock * ntiles + tile) * 2 + h) * N + n) * 64 + lane], h = 0: state after the first
-    // scan half of the tile, h = 1: after the tile
-#if SIGMA_BWDR_FULL
     float* __restrict__ ck = CK ? p.x + rowblock * ntiles * N * 64 + lane : nullptr;      // one checkpoint per tile (scan_rowlane.h)
-#else
-    float* __restrict__ ck = CK ? p.x + rowblock * ntiles * 2 * N * 64 + lane : nullptr;
-#endif
 
     // tiles of this workgroup in scan order: steps it = 0 .. nst-1, memory tile m = REV ? hi - it : lo + it
     const int st_lo = p.segs > 1 ? seg * p.seg_tiles : 0;
@@ -143,7 +122,6 @@ __device__ __forceinline__ void scan_fwdr_body(const FwdArgs& p, float* smem, in
     const float* __restrict__ bc_touch = ((lane & 1) ? Cw : Bw) + (long)(lane >> 1) * ((lane & 1) ? C_ns : B_ns);
     const bool bc_touch_on = lane < 2 * NS;
     float touch_nx = 0.0f, touch_acc = 0.0f;
-    RLPROF_DECL
     auto step = [&](int it, auto tail_tag) {
         constexpr bool TAIL = decltype(tail_tag)::value;
         m = tile_of(it);
@@ -167,11 +145,7 @@ __device__ __forceinline__ void scan_fwdr_body(const FwdArgs& p, float* smem, in
             for (int j = 0; j < 4; ++j) {
                 const float raw = dd[j] + bias;
                 float sig;
-#if SIGMA_RL_ABL & 32
-                const float sp = raw * raw; sig = 1.0f;
-#else
                 const float sp = softplus_ref(raw, sig);
-#endif
                 float d = p.softplus ? sp : raw;
                 d = valid ? d : 0.0f;                               // identity element past the end (a = 1, b = 0)
                 dl4[j] = d;
@@ -181,9 +155,7 @@ __device__ __forceinline__ void scan_fwdr_body(const FwdArgs& p, float* smem, in
             sProc[rl_unit(cc, rr)] = dl4;
             sProc[256 + rl_unit(cc, rr)] = dlu4;
         }
-        RLPROF(0)                                                   // operand wait, softplus, LDS writes
-        rl_barrier();
-        RLPROF(1)                                                   // barrier 1
+        lds_barrier();
 
         float dl[T], dlu[T], y[T];
 #pragma unroll
@@ -196,7 +168,6 @@ __device__ __forceinline__ void scan_fwdr_body(const FwdArgs& p, float* smem, in
         // loop, or its wait for them (lgkmcnt(0)) would also sit out that request
         asm volatile("" : "+v"(dl[0]), "+v"(dlu[0]), "+v"(dl[4]), "+v"(dlu[4]), "+v"(dl[8]), "+v"(dlu[8]), "+v"(dl[12]), "+v"(dlu[12]));
         __builtin_amdgcn_sched_barrier(0);
-        RLPROF(2)                                                   // LDS reads
         float dsum = 0.0f;
         if (SUMMARY) {
 #pragma unroll
@@ -211,7 +182,6 @@ __device__ __forceinline__ void scan_fwdr_body(const FwdArgs& p, float* smem, in
             // for here, BEFORE the requests of the next state are issued -- which then have the whole state to arrive.
             asm volatile("" : "+s"(Bt[0]), "+s"(Ct[0]));
             __builtin_amdgcn_sched_barrier(0);
-            RLPROF(3)                                               // scalar operand wait
             if (s + 1 < NS) {
                 rl_load_bc(Bw + (s + 1) * B_ns + T * m, nch, Bn);
                 if (!SUMMARY) rl_load_bc(Cw + (s + 1) * C_ns + T * m, nch, Cn);
@@ -224,26 +194,12 @@ __device__ __forceinline__ void scan_fwdr_body(const FwdArgs& p, float* smem, in
                 const float a = fast_exp2(dl[k] * A2[s]);
                 x = fmaf(a, x, dlu[k] * Bt[k]);
                 if (!SUMMARY) y[k] = fmaf(Ct[k], x, y[k]);
-#if !(SIGMA_RL_ABL & 2) && !SIGMA_BWDR_FULL
-                if (CK && kk == T / 2 - 1) ck[((long)(m * 2) * N + n0 + s) * 64] = x;
-#endif
             }
             xst[s] = x;
             if (SUMMARY) Pacc[s] = fmaf(dsum, A2[s], Pacc[s]);
-#if !(SIGMA_RL_ABL & 2)
-#if !SIGMA_BWDR_FULL
-            if (CK) ck[((long)(m * 2 + 1) * N + n0 + s) * 64] = x;  // state after memory tile m (scan order)
-#endif
-#endif
             __builtin_amdgcn_sched_barrier(0);
-            RLPROF(4)                                               // state loop
         }
-#if SIGMA_BWDR_FULL && !(SIGMA_RL_ABL & 2)
         if (CK) rl_store_ck<NS, NS * NW / 4>(ck - lane + (long)m * N * 64, n0, lane, xst);     // the states after memory tile m (scan order)
-#endif
-#if SIGMA_RL_ABL & 16
-        asm volatile("" :: "v"(y[0]), "v"(y[5]), "v"(y[10]), "v"(y[15]));
-#else
         if (!SUMMARY) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -251,19 +207,13 @@ __device__ __forceinline__ void scan_fwdr_body(const FwdArgs& p, float* smem, in
                 sEx[sw * 256 + rl_unit(c, lane)] = t;
             }
         }
-#endif
-        RLPROF(5)                                                   // exchange writes
-        rl_barrier();
-        RLPROF(6)                                                   // barrier 2
+        lds_barrier();
         if (!SUMMARY && (NW == 4 || rcw)) {
             v4f acc = du4;
-#if !(SIGMA_RL_ABL & 16)
 #pragma unroll
             for (int w = 0; w < NW; ++w) acc += sEx[w * 256 + rl_unit(cc, rr)];
-#endif
             if (valid) *reinterpret_cast<v4f*>(o_row + T * m) = acc;
         }
-        RLPROF(7)                                                   // sum of the waves, store
     };
     // The partial tile (fewer than 16 positions: the memory-last one) is the last step of a forward group and the first
     // of a reversed one: it is peeled off the loop (two variants of the body inside one loop double its register need).
@@ -273,7 +223,6 @@ __device__ __forceinline__ void scan_fwdr_body(const FwdArgs& p, float* smem, in
     if (!REV && nst > 0 && tile_of(nst - 1) == tail_tile) it1 = nst - 1;
     for (int it = it0; it < it1; ++it) step(it, std::false_type{});
     if (it1 < nst) step(it1, std::true_type{});
-    RLPROF_FLUSH(g_fwdr_prof)
     if (touch_acc == 1.2345678e-30f) o_row[0] = touch_acc;          // keeps the touches alive (never true in practice)
     if (SUMMARY) {
         float2* __restrict__ sm = reinterpret_cast<float2*>(p.fsumm);
@@ -333,11 +282,7 @@ __device__ __forceinline__ void scan_fwdp_body(const FwdArgs& p, float* smem, in
     const float* Cw = reinterpret_cast<const float*>(p.C) + (long)b * p.C_bs + (long)g * p.C_gs + (long)n0 * p.C_ns;
     const int B_ns = (int)p.B_ns, C_ns = (int)p.C_ns;               // host: (N - 1) * stride + L fits 31 bits
     const long rowblock = (long)b * (p.dim >> 6) + (row0 >> 6);
-#if SIGMA_BWDR_FULL
     float* __restrict__ ck = CK ? p.x + rowblock * ntiles * N * 64 : nullptr;      // one checkpoint block per tile (rl_store_ck)
-#else
-    float* __restrict__ ck = CK ? p.x + rowblock * ntiles * 2 * N * 64 + (long)n0 * 64 + lane : nullptr;
-#endif
 
     const int st_lo = p.segs > 1 ? seg * p.seg_tiles : 0;
     const int st_hi = p.segs > 1 ? (st_lo + p.seg_tiles < ntiles ? st_lo + p.seg_tiles : ntiles) : ntiles;
@@ -378,11 +323,7 @@ __device__ __forceinline__ void scan_fwdp_body(const FwdArgs& p, float* smem, in
         for (int j = 0; j < 4; ++j) {
             const float raw = dd[j] + bias;
             float sig;
-#if SIGMA_RL_ABL & 32
-            const float sp = raw * raw; sig = 1.0f;
-#else
             const float sp = softplus_ref(raw, sig);
-#endif
             float d = use_softplus ? sp : raw;
             d = valid ? d : 0.0f;                                   // identity element past the end (a = 1, b = 0)
             dl4[j] = d;
@@ -409,31 +350,26 @@ __device__ __forceinline__ void scan_fwdp_body(const FwdArgs& p, float* smem, in
         const v4f u0 = load_rc(u_row, m, true), d0 = load_rc(d_row, m, true);
         du_cur = preprocess(u0, d0, T * m + 4 * cc < L, 0);
     }
-    // u / delta travel PF tiles ahead of the state loop in PF register sets (set it & (PF - 1) feeds step it): with PF = 2
-    // a set is consumed and refilled by every second step, so no copy ever touches a register with a load in flight
-    constexpr int PF = SIGMA_FWDR_PF;
-    v4f u_s0 = load_rc(u_row, tile_of(nst > 1 ? 1 : 0), nst > 1), d_s0 = load_rc(d_row, tile_of(nst > 1 ? 1 : 0), nst > 1);
-    v4f u_s1 = u_s0, d_s1 = d_s0;
-    if (PF == 2) { u_s1 = load_rc(u_row, tile_of(nst > 2 ? 2 : 0), nst > 2); d_s1 = load_rc(d_row, tile_of(nst > 2 ? 2 : 0), nst > 2); }
+    // u / delta travel one tile ahead of the state loop
+    v4f u_nx = load_rc(u_row, tile_of(nst > 1 ? 1 : 0), nst > 1), d_nx = load_rc(d_row, tile_of(nst > 1 ? 1 : 0), nst > 1);
     float Bn[T], Cn[T];
     {
         const int nch0 = (L - T * m) >> 2;
         rl_load_bc(Bw + T * m, nch0 < 4 ? nch0 : 4, Bn);
         rl_load_bc(Cw + T * m, nch0 < 4 ? nch0 : 4, Cn);
     }
-    rl_barrier();
+    lds_barrier();
 
     // One step.  FAST: the steady state -- a previous tile to finish (it > 0), two more tiles ahead (it + 2 < nst) and no
     // partial tile among tiles it - 1 .. it + 2: straight-line code, no masks, full-width scalar requests.  Otherwise every
     // condition is tested at run time (the first step, the last two, and the neighbours of the partial tile).
-    RLPROF_DECL
     auto step = [&](int it, auto fast_tag, v4f& u_set, v4f& d_set) {
         constexpr bool FAST = decltype(fast_tag)::value;
         m = tile_of(it);
         const int buf = it & 1;
         const bool first = FAST ? false : it == 0;
         const bool more = FAST ? true : it + 1 < nst;
-        const bool moreP = FAST ? true : it + 1 + PF < nst;
+        const bool moreP = FAST ? true : it + 2 < nst;
         const int mn = tile_of(more ? it + 1 : it);
         const int mp = tile_of(first ? it : it - 1);
         // ---- row lane: this tile's delta / delta * u
@@ -445,33 +381,19 @@ __device__ __forceinline__ void scan_fwdp_body(const FwdArgs& p, float* smem, in
             for (int j = 0; j < 4; ++j) { dl[4 * c + j] = a[j]; dlu[4 * c + j] = bq[j]; y[4 * c + j] = 0.0f; }
         }
         // ---- (row, chunk): the partial sums of the previous tile (garbage on the first step: not stored)
-#if SIGMA_RL_ABL & 16
-        v4f e0 = du_prev, e1 = du_prev, e2 = du_cur, e3 = du_cur;
-#else
         v4f e0 = sEx[((buf ^ 1) * 4 + 0) * 256 + unit_rc], e1 = sEx[((buf ^ 1) * 4 + 1) * 256 + unit_rc];
         v4f e2 = sEx[((buf ^ 1) * 4 + 2) * 256 + unit_rc], e3 = sEx[((buf ^ 1) * 4 + 3) * 256 + unit_rc];
-#endif
         // ---- (row, chunk): next tile's operands -> sProc[buf ^ 1]
         v4f uu = u_set, dd = d_set;
-#if SIGMA_RL_PROF
-        RLPROF(1)                                                   // LDS read requests, addresses
-        asm volatile("" : "+v"(uu), "+v"(dd));
-        RLPROF(0)                                                   // wait for the next tile's u / delta (vmcnt)
-#endif
         const v4f du_next = preprocess(uu, dd, FAST ? true : (more && T * mn + 4 * cc < L), buf ^ 1);
-        // ... and tile it + 1 + PF starts flying into the registers just read (after their last use: no copy, no early wait)
+        // ... and tile it + 2 starts flying into the registers just read (after their last use: no copy, no early wait)
         asm volatile("" :: "v"(du_next));
         __builtin_amdgcn_sched_barrier(0);
         {
-            const int m2 = tile_of(moreP ? it + 1 + PF : it);
+            const int m2 = tile_of(moreP ? it + 2 : it);
             if (FAST) {
-#if SIGMA_RL_ABL & 4
-                u_set = rl_load4(u_row + T * m2, true);
-                d_set = rl_load4(d_row + T * m2, true);
-#else
                 u_set = *reinterpret_cast<const v4f*>(u_row + T * m2);
                 d_set = *reinterpret_cast<const v4f*>(d_row + T * m2);
-#endif
             } else {
                 u_set = load_rc(u_row, m2, moreP);
                 d_set = load_rc(d_row, m2, moreP);
@@ -483,12 +405,10 @@ __device__ __forceinline__ void scan_fwdp_body(const FwdArgs& p, float* smem, in
         }
         du_prev = du_cur;
         du_cur = du_next;
-        RLPROF(7)                                                   // (row, chunk) duties: softplus, hand-off, sum, store
         // LDS reads and scalar loads share one counter: retire the reads before the first scalar request of the state loop,
         // or its wait for them (lgkmcnt(0)) would also sit out that request
         asm volatile("" : "+v"(dl[0]), "+v"(dlu[0]), "+v"(dl[4]), "+v"(dlu[4]), "+v"(dl[8]), "+v"(dlu[8]), "+v"(dl[12]), "+v"(dlu[12]));
         __builtin_amdgcn_sched_barrier(0);
-        RLPROF(2)                                                   // LDS reads of this tile's operands
         // ---- state loop
         const int nch = FAST ? 4 : ((L - T * m) >> 2 < 4 ? (L - T * m) >> 2 : 4);
 #pragma unroll
@@ -515,63 +435,32 @@ __device__ __forceinline__ void scan_fwdp_body(const FwdArgs& p, float* smem, in
                 const float a = fast_exp2(dl[k] * A2[s]);
                 x = fmaf(a, x, dlu[k] * Bt[k]);
                 y[k] = fmaf(Ct[k], x, y[k]);
-#if !(SIGMA_RL_ABL & 2) && !SIGMA_BWDR_FULL
-                if (CK && kk == T / 2 - 1) ck[((long)(m * 2) * N + s) * 64] = x;
-#endif
             }
             xst[s] = x;
-#if !(SIGMA_RL_ABL & 2)
-#if !SIGMA_BWDR_FULL
-            if (CK) ck[((long)(m * 2 + 1) * N + s) * 64] = x;       // state after memory tile m (scan order)
-#endif
-#endif
             // the sums are complete HERE: without this the instruction selector parks the C * x products of a state behind
             // the last one (its scheduling barriers bind the machine scheduler only) and keeps every x and C alive until then
             asm volatile("" : "+v"(y[0]), "+v"(y[1]), "+v"(y[2]), "+v"(y[3]), "+v"(y[4]), "+v"(y[5]), "+v"(y[6]), "+v"(y[7]),
                               "+v"(y[8]), "+v"(y[9]), "+v"(y[10]), "+v"(y[11]), "+v"(y[12]), "+v"(y[13]), "+v"(y[14]), "+v"(y[15]));
             __builtin_amdgcn_sched_barrier(0);
         }
-#if SIGMA_BWDR_FULL && !(SIGMA_RL_ABL & 2)
         if (CK) rl_store_ck<NS, NS>(ck + (long)m * N * 64, n0, lane, xst);            // the states after memory tile m (scan order)
-#endif
-        RLPROF(4)                                                   // state loop
-#if SIGMA_RL_ABL & 16
-        asm volatile("" :: "v"(y[0]), "v"(y[5]), "v"(y[10]), "v"(y[15]));
-#else
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const v4f t = {y[4 * c], y[4 * c + 1], y[4 * c + 2], y[4 * c + 3]};
             sEx[(buf * 4 + sw) * 256 + rl_unit(c, lane)] = t;
         }
-#endif
-        RLPROF(5)                                                   // exchange writes
-        rl_barrier();
-        RLPROF(6)                                                   // barrier
+        lds_barrier();
     };
-    // steady-state range [lo, hi]: it >= 1, it + 1 + PF <= nst - 1, and the partial tile (the first step of a reversed
-    // group, the last of a forward one) not among tiles it - 1 .. it + 1 + PF
+    // steady-state range [lo, hi]: it >= 1, it + 2 <= nst - 1, and the partial tile (the first step of a reversed
+    // group, the last of a forward one) not among tiles it - 1 .. it + 2
     const int tail_tile = (L % T) ? ntiles - 1 : -1;                // memory tile with fewer than 16 positions
     int lo = (REV && tile_of(0) == tail_tile) ? 2 : 1;
-    int hi = nst - 1 - (PF + 1) - ((!REV && tile_of(nst - 1) == tail_tile) ? 1 : 0);
+    int hi = nst - 3 - ((!REV && tile_of(nst - 1) == tail_tile) ? 1 : 0);
     if (hi < lo) { lo = nst; hi = nst - 1; }
-    // steps outside the steady state use set 0 only (an odd step swaps the sets around itself: copies, and the waits they
-    // imply, cost nothing there)
-    auto slow = [&](int it) {
-        const bool odd = PF == 2 && (it & 1);
-        if (odd) { const v4f tu = u_s0, td = d_s0; u_s0 = u_s1; d_s0 = d_s1; u_s1 = tu; d_s1 = td; }
-        step(it, std::false_type{}, u_s0, d_s0);
-        if (odd) { const v4f tu = u_s0, td = d_s0; u_s0 = u_s1; d_s0 = d_s1; u_s1 = tu; d_s1 = td; }
-    };
     int it = 0;
-    const int lo2 = PF == 2 ? ((lo + 1) & ~1) : lo;                 // steady state starts on an even step (register set 0)
-    for (; it < lo2 && it < nst; ++it) slow(it);
-    if (PF == 2) {
-        for (; it + 1 <= hi; it += 2) { step(it, std::true_type{}, u_s0, d_s0); step(it + 1, std::true_type{}, u_s1, d_s1); }
-    } else {
-        for (; it <= hi; ++it) step(it, std::true_type{}, u_s0, d_s0);
-    }
-    for (; it < nst; ++it) slow(it);
-    RLPROF_FLUSH(g_fwdr_prof)
+    for (; it < lo && it < nst; ++it) step(it, std::false_type{}, u_nx, d_nx);
+    for (; it <= hi; ++it) step(it, std::true_type{}, u_nx, d_nx);
+    for (; it < nst; ++it) step(it, std::false_type{}, u_nx, d_nx);
     // ---- drain: the sum and the store of the last tile
     {
         v4f acc = du_prev;
@@ -597,13 +486,11 @@ scan_fwdr_kernel(const FwdArgs p) {
     const int rem2 = rem - g * PS;
     const int rbg = rem2 / S;
     const int seg = rem2 - rbg * S;
-#if SIGMA_FWDR_PIPE
     if constexpr (NW == 4 && MODE != 2) {
         if ((p.rev_mask >> g) & 1u) scan_fwdp_body<NS, true, MODE == 1>(p, smem, b, g, rbg, seg);
         else scan_fwdp_body<NS, false, MODE == 1>(p, smem, b, g, rbg, seg);
         return;
     }
-#endif
     if ((p.rev_mask >> g) & 1u) scan_fwdr_body<NS, NW, true, MODE>(p, smem, b, g, rbg, seg);
     else scan_fwdr_body<NS, NW, false, MODE>(p, smem, b, g, rbg, seg);
 }

@@ -4,15 +4,11 @@
 #include <atomic>
 #include "scan_device.h"
 
-// rows (waves) per workgroup the backward kernel may use with T = 10 (640-element tiles):
-// 12 = ~164 VGPRs, 3 waves per SIMD; 16 needs the kernel to fit 128 VGPRs (build knob for A/B runs)
-#ifndef SIGMA_BWD_MAXW_T10
-#define SIGMA_BWD_MAXW_T10 12
-#endif
-
 namespace sigma {
 
-constexpr int kBwdMaxWavesT10 = SIGMA_BWD_MAXW_T10;
+// rows (waves) per workgroup the backward kernel may use with T = 10 (640-element tiles):
+// 12 = ~164 VGPRs, 3 waves per SIMD; 16 would need the kernel to fit 128 VGPRs
+constexpr int kBwdMaxWavesT10 = 12;
 
 // forward: double-buffered B/C stage [2][2][NB][W][TILE] + tile aggregates + A, running state
 inline size_t fwd_lds_bytes(int T, int R, int W, int NB, int N) {
@@ -54,20 +50,9 @@ inline size_t fwd4_lds_bytes(int N) { return sizeof(float) * (2 * 2 * (size_t)N 
 
 // row-lane kernels (scan_fwdr.hip / scan_bwdr.hip): [arrays][4 chunks][64 rows] float4 of pre-processed operands +
 // [state waves][...] partial sums over the states
-// round 6 (SIGMA_FWDR_PIPE): four state waves run the pipelined body on double-buffered blocks (48 KB: three workgroups per CU)
-#ifndef SIGMA_FWDR_PIPE
-#define SIGMA_FWDR_PIPE 1
-#endif
-// tiles the (row, chunk) loads of u / delta run ahead of the state loop (1 or 2)
-#ifndef SIGMA_FWDR_PF
-#define SIGMA_FWDR_PF 1
-#endif
-inline size_t fwdr_lds_bytes(int NW) { return SIGMA_FWDR_PIPE && NW == 4 ? 16 * (size_t)(4 * 256 + 2 * 4 * 256) : 16 * (size_t)(2 * 256 + NW * 256); }
-#if defined(SIGMA_RL_ABL) && (SIGMA_RL_ABL & 128)
-inline size_t bwdr_lds_bytes(int NW) { return 16 * (size_t)(5 * 256 + NW * 256 + 3 * 256); }        // timing probe: half the exchange area
-#else
+// round 6: four state waves run the pipelined body on double-buffered blocks (48 KB: three workgroups per CU)
+inline size_t fwdr_lds_bytes(int NW) { return NW == 4 ? 16 * (size_t)(4 * 256 + 2 * 4 * 256) : 16 * (size_t)(2 * 256 + NW * 256); }
 inline size_t bwdr_lds_bytes(int NW) { return 16 * (size_t)(5 * 256 + NW * 2 * 256 + 3 * 256); }
-#endif
 
 constexpr int kMaxDevices = 16;    // per-device cache of the raised dynamic-LDS cap (hipFuncSetAttribute is per device)
 
@@ -94,12 +79,7 @@ hipError_t launch_scan_bwdr(const BwdArgs& a, hipStream_t stream);
 int bwdr_resident_per_cu(int N);                                     // workgroups of scan_bwdr_kernel a CU holds (occupancy query, cached)   // a.P = 64-row blocks per (batch, group); a.S / a.seg_tiles / a.summ
 hipError_t launch_reduce_partials(const BwdArgs& a, hipStream_t stream);
 hipError_t launch_reduce_after(const BwdArgs& a, hipStream_t stream);   // the reduce pass a backward needs (none, dB/dC, + rows)
-hipError_t bwd4_prof_read(unsigned long long* out16);
-hipError_t fwdr_prof_read(unsigned long long* out16);     // development builds (SIGMA_RL_PROF), zeros otherwise
-hipError_t bwdr_prof_read(unsigned long long* out16);
 hipError_t bwdr_chain_timeouts_read(unsigned int* out);   // chained walk: hand-over waits that ran out since the last call
-hipError_t gemm_prof_read(unsigned long long* out16);     // development builds (SIGMA_GEMM_PROF), zeros otherwise
-hipError_t bwd2_prof_read(unsigned long long* out16);     // development builds (SIGMA_BWD2_PROF), zeros otherwise
 hipError_t launch_scan_fwd(const FwdArgs& a, int dtype, int T, bool glds, bool prefetch, hipStream_t stream);
 hipError_t launch_scan_bwd(const BwdArgs& a, int dtype, int T, bool glds, hipStream_t stream);
 hipError_t launch_selftest(float* out, hipStream_t stream);

@@ -11,44 +11,18 @@
 //     are rotated by 4 * chunk so that both access patterns are bank-conflict free;
 //   * the sums over the states (out; du, ddelta) of the four waves meet in LDS once per tile (two barriers per tile);
 //   * the state entering a tile comes from a checkpoint per tile (pitch 16) in a layout private to these kernels:
-//         x[(((b * dim/64 + rowblock) * ntiles + tile) * N + n) * 64 + lane]
-//     (256 contiguous bytes per (tile, state) for the wave that owns the row block, in both kernels).
+//         x[((b * dim/64 + rowblock) * ntiles + tile) * N * 64 + rl_ck_slot(n, lane)]
 // Tiles are taken in MEMORY order (tile m = elements [16m, 16m + 16)); a reversed group walks them from the last to the
 // first and the positions of a tile from 15 down to 0, so a partial last tile is always the memory-last one.
 #pragma once
 #include "scan_device.h"
 
-// phase timing of development builds (-DSIGMA_RL_PROF=1; tools/rowlane_prof.py): cycles per phase, summed over the waves
-#ifndef SIGMA_RL_PROF
-#define SIGMA_RL_PROF 0
-#endif
-#if SIGMA_RL_PROF
-#define RLPROF_DECL long long prof_t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long prof_last = __builtin_readcyclecounter();
-#define RLPROF(i) { const long long t_ = __builtin_readcyclecounter(); prof_t[i] += t_ - prof_last; prof_last = t_; }
-#define RLPROF_FLUSH(arr) if ((threadIdx.x & 63) == 0) { for (int i_ = 0; i_ < 12; ++i_) atomicAdd(&arr[i_], (unsigned long long)prof_t[i_]); atomicAdd(&arr[15], 1ull); }
-#else
-#define RLPROF_DECL
-#define RLPROF(i)
-#define RLPROF_FLUSH(arr)
-#endif
-
-// Ablation builds (-DSIGMA_RL_ABL=<bits>; results are WRONG, timing only; tools/gpu_r4.sh):
-//   1 B / C from constants (no scalar loads)   2 no checkpoint stores / loads   4 u / delta / dout from constants
-//   8 no workgroup barriers   16 no exchange through LDS   32 no softplus (prologue arithmetic)   64 no dB/dC reduce network
-#ifndef SIGMA_RL_ABL
-#define SIGMA_RL_ABL 0
-#endif
-
-// Round 6: 1 = ONE checkpoint per tile -- the state after the tile, a block of N * 64 floats per (row block, tile) (rl_store_ck below) -- so
-// the forward writes half as many checkpoint bytes (it is bound by HBM traffic: 0.5 of its 1.3 GB per launch were
+// Round 6: ONE checkpoint per tile -- the state after the tile, a block of N * 64 floats per (row block, tile) (rl_store_ck below) -- so
+// the forward writes half as many checkpoint bytes as round 4's two per tile (it is bound by HBM traffic: 0.5 of its 1.3 GB per launch were
 // checkpoints) and the backward reads half as many, walking the tile WHOLE: per state a forward replay of its 16 positions
 // from the state entering the tile, then the reverse recurrence over the 16 positions.  Same arithmetic per element-state as
-// the half-tile walk (every position is replayed exactly once either way), 16-entry per-lane arrays (~250 VGPRs: the two
+// round 4's half-tile walk (every position is replayed exactly once either way), 16-entry per-lane arrays (~250 VGPRs: the two
 // waves per SIMD this kernel runs with have them), B / C of a (state, tile) in ONE 16-dword scalar request each.
-// 0: the round-4 scheme (two checkpoints per tile, the backward in halves of 8 positions).
-#ifndef SIGMA_BWDR_FULL
-#define SIGMA_BWDR_FULL 1
-#endif
 
 namespace sigma {
 namespace {
@@ -70,12 +44,6 @@ __device__ __forceinline__ int rl_unit(int c, int r) { return c * 64 + ((r + 4 *
 // B or C of one (state, tile): 16 consecutive floats at a wave-uniform address -> SGPRs.  nch = valid 16-byte chunks
 // (4 except in a partial last tile; L % 4 == 0 is a precondition of the kernels), missing ones read as zero.
 __device__ __forceinline__ void rl_load_bc(const float* base, int nch, float (&v)[kRT]) {
-#if SIGMA_RL_ABL & 1
-    float c = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane((int)(reinterpret_cast<uintptr_t>(base) & 0xffff) | 0x3f000000));
-#pragma unroll
-    for (int k = 0; k < kRT; ++k) { v[k] = c; asm volatile("" : "+s"(c)); }
-    return;
-#endif
     if (nch >= 4) {
         const v16f t = *reinterpret_cast<cv16p_t>(reinterpret_cast<uintptr_t>(base));
 #pragma unroll
@@ -92,11 +60,6 @@ __device__ __forceinline__ void rl_load_bc(const float* base, int nch, float (&v
 
 __device__ __forceinline__ v4f rl_load4(const float* __restrict__ p, bool ok) {
     const v4f z = {0.0f, 0.0f, 0.0f, 0.0f};
-#if SIGMA_RL_ABL & 4
-    const float c = 0.001f * (float)(reinterpret_cast<uintptr_t>(p) & 0xff);
-    const v4f t = {c, 0.5f * c, 0.25f * c, -c};
-    return ok ? t : z;
-#endif
     return ok ? *reinterpret_cast<const v4f*>(p) : z;
 }
 
@@ -121,7 +84,7 @@ __device__ __forceinline__ void rl_dma_wait() { asm volatile("s_waitcnt vmcnt(0)
 template <int YOUNGER>
 __device__ __forceinline__ void rl_dma_wait_keep() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(YOUNGER) : "memory"); }
 
-// Checkpoints of one tile (SIGMA_BWDR_FULL): a block of N * 64 floats in which the states go in groups of G = N / 4 (the
+// Checkpoints of one tile: a block of N * 64 floats in which the states go in groups of G = N / 4 (the
 // states of one wave of the backward, which always runs four state waves) and a group is innermost -- slot of state n of
 // lane l = ((n / G) * 64 + l) * G + n % G -- so that the states of a wave are ONE 16- / 8- / 4-byte access per lane and
 // 1 KB / 512 B / 256 B contiguous per wave (a vector-memory instruction costs the issuing SIMD ~25 ns whatever its
@@ -143,12 +106,6 @@ __device__ __forceinline__ void rl_load_ck(const float* __restrict__ tile_block,
     if constexpr (NS == 4) { const v4f v = *reinterpret_cast<const v4f*>(p); x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3]; }
     else if constexpr (NS == 2) { const float2 v = *reinterpret_cast<const float2*>(p); x[0] = v.x; x[1] = v.y; }
     else { x[0] = p[0]; }
-}
-
-__device__ __forceinline__ void rl_barrier() {
-#if !(SIGMA_RL_ABL & 8)
-    lds_barrier();
-#endif
 }
 
 }  // namespace

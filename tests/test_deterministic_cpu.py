@@ -108,9 +108,9 @@ def row_sum_depth(plan, batch, L):
     return lane + levels + batch * S * per_wg, lane + levels + per_wg + batch * S
 
 
-def test_abi_version_and_struct_fields(tmp_path):
+def test_abi_version_12_and_struct_fields(tmp_path):
     lib = _capi.load()
-    assert _capi.SIGMA_SCAN_ABI_VERSION == 11 and lib.sigma_scan_abi_version() == 11
+    assert _capi.SIGMA_SCAN_ABI_VERSION == 12 and lib.sigma_scan_abi_version() == 12
     fields = [("sigma_scan_bwd_params", "flags", _capi.BwdParams), ("sigma_dwconv_params", "flags", _capi.DwConvParams),
               ("sigma_dwconv_params", "workspace", _capi.DwConvParams),
               ("sigma_dwconv_params", "workspace_bytes", _capi.DwConvParams)]

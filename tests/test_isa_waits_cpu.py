@@ -2,13 +2,14 @@
 THIS toolchain emits -- no GPU needed (hipcc cross-compiles; ~15 s).
 
 The tile loop requests the next tile's u / delta / dout with three ``global_load_lds_dwordx4`` from inline assembly and, one
-iteration later, retires them with ``s_waitcnt vmcnt(N)``, N = 3 + 2 NS: vector-memory operations retire in order, so the
+iteration later, retires them with ``s_waitcnt vmcnt(N)``, N = 4 + NS: vector-memory operations retire in order, so the
 requests have landed once at most the K operations issued AFTER them are outstanding -- which is only true while K >= N.  A
 compiler that drops, merges or moves one of those younger loads / stores in front of the requests (or an edit that changes N
 without changing the loop) makes the wait a no-op for the last request: wrong u / delta / dout, silently and only under
-memory pressure.  A run-time self test on an idle chip does not see that (tools/diag/r5_selftest_power.sh: a build with
-N + 3 passes sigma_scan_rowlane_selftest three times out of three), so the count is checked where it is decided: in the
-ISA, with N read from the instruction itself.  The same build is caught here ("only 11 ... keeps 14")."""
+memory pressure.  A run-time self test on an idle chip does not see that (a build with N + 3 passed
+sigma_scan_rowlane_selftest three times out of three), so the count is checked where it is decided: in
+the ISA, with N read from the instruction itself.  The same build (-DSIGMA_BWDR_WAIT_SKEW=3, the one build switch left in the
+kernels) is caught here."""
 import os
 import re
 import subprocess
@@ -93,7 +94,7 @@ def test_counted_wait_of_the_row_lane_backward_is_covered_by_younger_operations(
 
 def test_a_miscounted_wait_is_refused(tmp_path_factory):
     """the check has teeth: a build whose wait keeps three operations too many in flight (the build a run-time self test on an
-    idle chip passes, tools/diag/README.md) fails it"""
+    idle chip passes) fails it"""
     from sigma_amd import build
     if not os.path.exists(build.HIPCC):
         pytest.skip(f"no hipcc at {build.HIPCC}")
