@@ -319,6 +319,9 @@ def test_long_sequences_of_the_720x1280_configuration(shape, pitch):
     rg = list(so.selective_scan_oracle_bwd(fr(u_f), fr(delta), A, fg(B), fg(C), D, bias, fr(g_f), True))
     rg[0], rg[1], rg[3], rg[4] = fr(rg[0]), fr(rg[1]), fg(rg[3]), fg(rg[4])
     assert_grads_close(grads, rg)
+    # and the derived bound against the fp64 reference on the device (tests/scan_fp64_ref.py): |got - ref| <= U S
+    from tests.test_scan_fp64_gpu import bound_check
+    bound_check((*args, g_h.to(dev), True), shape, pitch, 0, "init (long)", out, grads, None)
 
 
 def test_checkpoint_tensor_shape_and_documented_layout():
@@ -584,6 +587,10 @@ def test_full_size_step_launches_against_oracle(shape):
     for i, name in ((0, "du"), (1, "ddelta"), (3, "dB"), (4, "dC")):
         assert torch.equal(det[i], grads[i]), f"{name}: deterministic mode changed a per-element gradient"
     _check_row_sums(shape, pitch, u_f.to(dev), g_f.to(dev), grads, det)
+    # and the derived bound against the fp64 reference on the device (tests/scan_fp64_ref.py), both forms of the backward:
+    # |got - ref| <= U S on every element of the forward and the seven gradients
+    from tests.test_scan_fp64_gpu import bound_check
+    bound_check((*args, g_dev, True), shape[:7], pitch, 0, "init (full)", out, grads, det)
 
 
 def _check_row_sums(shape, pitch, u_f, g_f, grads, det):

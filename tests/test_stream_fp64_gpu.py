@@ -989,8 +989,19 @@ def _scan_covered():
             covers(k, f"tests/test_deterministic_gpu.py::test_every_family_writes_all_row_gradients[{c}]")
 
 
+def _scan_fp64_cases():
+    """the scan keys that have a case under the derived fp64 bound (tests/test_scan_fp64_gpu.py): key -> that case"""
+    from tests.test_scan_fp64_gpu import CASES
+    tight = {}
+    for c in CASES:
+        for k in scan_case_keys(*c[1:9], IO_DTYPES[c[9]], det=(False, True)):
+            tight.setdefault(k, f"tests/test_scan_fp64_gpu.py::test_every_family_on_every_regime[{c[0]}-*]")
+    return tight
+
+
 IO_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 LONG_PITCHES = (0, 640, 320, 160)
+COVERED.update(_scan_fp64_cases())          # first: where a scan key has the tighter test, it is the one named
 _scan_covered()
 
 
