@@ -30,36 +30,7 @@
 
 namespace sigma {
 
-namespace {
-
-// Register path of the B/C staging (16-bit IO types, unaligned tensors): rows of states [n0, n0+nbn)
-// of ONE tile into dst laid out [arr][NB][TILE]; the f32 / aligned case uses StagePlan (scan_device.h).
-template <typename io_t, int T>
-__device__ __forceinline__ void stage_tile(float* __restrict__ dst, const io_t* __restrict__ Bg,
-                                           const io_t* __restrict__ Cg, long B_ns, long C_ns, int n0, int nbn, int NB,
-                                           int tile, int L, bool rev, bool vec, bool with_c) {
-    constexpr int TILE = 64 * T;
-    constexpr int CPR = TILE / 4;
-    const int total = (with_c ? 2 : 1) * NB * CPR;
-    const int l0 = tile * TILE;
-    for (int ci = threadIdx.x; ci < total; ci += blockDim.x) {
-        const int row = ci / CPR;                      // arr * NB + nn
-        const int c4 = (ci - row * CPR) * 4;
-        const int arr = row / NB;
-        const int nn = row - arr * NB;
-        const int m = rev ? (L - l0 - TILE + c4) : (l0 + c4);
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (nn < nbn && m < L && m + 4 > 0) {
-            const io_t* __restrict__ srow = arr == 0 ? Bg + (long)(n0 + nn) * B_ns : Cg + (long)(n0 + nn) * C_ns;
-            load4_guard<io_t>(srow, m, L, vec, v);
-        }
-        *reinterpret_cast<float4*>(dst + (long)ci * 4) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-}
-
-}  // namespace
-
-template <typename io_t, int T, bool GLDS, bool REV, bool DET = false>
+template <typename io_t, int T, bool GLDS, bool REV, bool DET>
 __device__ __forceinline__ void scan_bwd_body(const BwdArgs& q, float* smem, int b, int row0, int g) {
     constexpr int TILE = 64 * T;
     constexpr int TPSMAX = kCkptPitch / TILE;         // LDS sizing: tiles per span at the default pitch
@@ -126,7 +97,7 @@ __device__ __forceinline__ void scan_bwd_body(const BwdArgs& q, float* smem, int
             plan.issue(dst, reinterpret_cast<const float*>(Bg), reinterpret_cast<const float*>(Cg), (int)p.B_ns, (int)p.C_ns,
                        n0, nbn, tile, L, NB * TILE, with_c);
         } else {
-            stage_tile<io_t, T>(dst, Bg, Cg, p.B_ns, p.C_ns, n0, nbn, NB, tile, L, REV, vec, with_c);
+            stage_bc<io_t, T>(dst, Bg, Cg, p.B_ns, p.C_ns, n0, nbn, NB, 1, tile, L, REV, vec, with_c);
         }
     };
 
@@ -398,6 +369,8 @@ __device__ __forceinline__ void scan_bwd_body(const BwdArgs& q, float* smem, int
 // needs ~150 VGPRs, i.e. 3 waves per SIMD = 12 rows per workgroup; T = 4 / 5 fit 16.
 template <int T> struct bwd_max_waves { static constexpr int value = (T >= 10) ? kBwdMaxWavesT10 : 16; };
 
+// The two wrappers repeat the workgroup -> (batch, row block, group) arithmetic: behind a shared entry function (as in
+// scan_bwd2.hip) or a coordinate helper the kernels are scheduled differently (60,000 of 237,600 assembly lines).
 template <typename io_t, int T, bool GLDS>
 __global__ void __launch_bounds__(64 * bwd_max_waves<T>::value)
 scan_bwd_kernel(const BwdArgs q) {
@@ -408,8 +381,8 @@ scan_bwd_kernel(const BwdArgs q) {
     const int rb = lb - b * q.f.rowblocks;
     const int row0 = rb * R;
     const int g = row0 / q.f.rows_per_group;
-    if ((q.f.rev_mask >> g) & 1u) scan_bwd_body<io_t, T, GLDS, true>(q, smem, b, row0, g);
-    else scan_bwd_body<io_t, T, GLDS, false>(q, smem, b, row0, g);
+    if ((q.f.rev_mask >> g) & 1u) scan_bwd_body<io_t, T, GLDS, true, false>(q, smem, b, row0, g);
+    else scan_bwd_body<io_t, T, GLDS, false, false>(q, smem, b, row0, g);
 }
 
 // deterministic mode (SIGMA_SCAN_BWD_DETERMINISTIC): the same backward with its per-row results stored to q.rpart
@@ -516,17 +489,26 @@ reduce_partials_det_kernel(const BwdArgs a, int bc_blocks) {
     }
 }
 
-hipError_t launch_reduce_partials(const BwdArgs& a, hipStream_t stream) {
+// blocks of 256 threads for the dB / dC slab sum (4 elements per thread, at most 4096 blocks) and which build of
+// reduce_partials_body the shapes allow
+struct ReduceGeom { long blocks; bool vec, ovec; };
+static ReduceGeom reduce_geom(const BwdArgs& a) {
+    ReduceGeom r;
     const long per = (long)a.f.batch * a.f.G * a.f.N * a.f.L;
-    long blocks = (per / 4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
-    const bool vec = (a.f.L & 3) == 0 && (long)a.f.batch * a.f.G * a.f.N < (1L << 31);
-    const bool ovec = vec && a.out_vec_ok != 0;
-#define SIGMA_RP(V, O) hipLaunchKernelGGL((reduce_partials_kernel<V, O>), dim3((unsigned)blocks), dim3(256), 0, stream, a.ws_dB, a.ws_dC, \
+    r.blocks = (per / 4 + 255) / 256;
+    if (r.blocks > 4096) r.blocks = 4096;
+    if (r.blocks < 1) r.blocks = 1;
+    r.vec = (a.f.L & 3) == 0 && (long)a.f.batch * a.f.G * a.f.N < (1L << 31);
+    r.ovec = r.vec && a.out_vec_ok != 0;
+    return r;
+}
+
+hipError_t launch_reduce_partials(const BwdArgs& a, hipStream_t stream) {
+    const ReduceGeom r = reduce_geom(a);
+#define SIGMA_RP(V, O) hipLaunchKernelGGL((reduce_partials_kernel<V, O>), dim3((unsigned)r.blocks), dim3(256), 0, stream, a.ws_dB, a.ws_dC, \
                        a.dB, a.dC, a.P, a.f.batch, a.f.G, a.f.N, a.f.L, a.dB_bs, a.dB_gs, a.dB_ns, a.dC_bs, a.dC_gs, a.dC_ns)
-    if (ovec) SIGMA_RP(true, true);
-    else if (vec) SIGMA_RP(true, false);
+    if (r.ovec) SIGMA_RP(true, true);
+    else if (r.vec) SIGMA_RP(true, false);
     else SIGMA_RP(false, false);
 #undef SIGMA_RP
     return hipGetLastError();
@@ -534,20 +516,13 @@ hipError_t launch_reduce_partials(const BwdArgs& a, hipStream_t stream) {
 
 // the reduce pass of a deterministic backward: dB / dC (when P > 1) and the per-row slots in ONE launch
 hipError_t launch_reduce_det(const BwdArgs& a, hipStream_t stream) {
-    long bc = 0;
-    if (a.P > 1) {
-        const long per = (long)a.f.batch * a.f.G * a.f.N * a.f.L;
-        bc = (per / 4 + 255) / 256;
-        if (bc > 4096) bc = 4096;
-        if (bc < 1) bc = 1;
-    }
+    const ReduceGeom r = reduce_geom(a);
+    const long bc = a.P > 1 ? r.blocks : 0;
     long rows = ((long)a.f.dim * (a.f.N + 2) + 255) / 256;
     if (rows > 1024) rows = 1024;
-    const bool vec = (a.f.L & 3) == 0 && (long)a.f.batch * a.f.G * a.f.N < (1L << 31);
-    const bool ovec = vec && a.out_vec_ok != 0;
     const dim3 grid((unsigned)(bc + rows));
-    if (ovec) hipLaunchKernelGGL((reduce_partials_det_kernel<true, true>), grid, dim3(256), 0, stream, a, (int)bc);
-    else if (vec) hipLaunchKernelGGL((reduce_partials_det_kernel<true, false>), grid, dim3(256), 0, stream, a, (int)bc);
+    if (r.ovec) hipLaunchKernelGGL((reduce_partials_det_kernel<true, true>), grid, dim3(256), 0, stream, a, (int)bc);
+    else if (r.vec) hipLaunchKernelGGL((reduce_partials_det_kernel<true, false>), grid, dim3(256), 0, stream, a, (int)bc);
     else hipLaunchKernelGGL((reduce_partials_det_kernel<false, false>), grid, dim3(256), 0, stream, a, (int)bc);
     return hipGetLastError();
 }
@@ -562,18 +537,7 @@ template <typename io_t, int T, bool GLDS>
 static hipError_t launch_bwd_t(const BwdArgs& a, hipStream_t stream) {
     const size_t lds = bwd_lds_bytes(T, a.f.R, a.f.NB, a.f.N, a.slab2 != 0);
     const int grid = a.f.rowblocks * a.f.batch;
-    if (a.rpart) {
-        constexpr auto kern = scan_bwd_det_kernel<io_t, T, GLDS>;
-        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
-    } else {
-        constexpr auto kern = scan_bwd_kernel<io_t, T, GLDS>;
-        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_reduce_after(a, stream);
+    return launch_bwd_pair<scan_bwd_det_kernel<io_t, T, GLDS>, scan_bwd_kernel<io_t, T, GLDS>>(grid, a.f.R * 64, lds, a, stream);
 }
 
 template <typename io_t, bool GLDS>

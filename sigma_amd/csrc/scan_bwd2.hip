@@ -32,109 +32,6 @@
 
 namespace sigma {
 
-namespace {
-
-// Register path of the B/C staging (16-bit IO types, unaligned tensors): states [n0, n0+nbn) of ONE
-// tile into dst laid out [arr][NB][TILE]; the f32 / aligned case uses StagePlan (scan_device.h).
-template <typename io_t, int T>
-__device__ __forceinline__ void stage_tile2(float* __restrict__ dst, const io_t* __restrict__ Bg,
-                                            const io_t* __restrict__ Cg, long B_ns, long C_ns, int n0, int nbn, int NB,
-                                            int tile, int L, bool rev, bool vec) {
-    constexpr int TILE = 64 * T;
-    constexpr int CPR = TILE / 4;
-    const int total = 2 * NB * CPR;
-    const int l0 = tile * TILE;
-    for (int ci = threadIdx.x; ci < total; ci += blockDim.x) {
-        const int row = ci / CPR;                      // arr * NB + nn
-        const int c4 = (ci - row * CPR) * 4;
-        const int arr = row / NB;
-        const int nn = row - arr * NB;
-        const int m = rev ? (L - l0 - TILE + c4) : (l0 + c4);
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (nn < nbn && m < L && m + 4 > 0) {
-            const io_t* __restrict__ srow = arr == 0 ? Bg + (long)(n0 + nn) * B_ns : Cg + (long)(n0 + nn) * C_ns;
-            load4_guard<io_t>(srow, m, L, vec, v);
-        }
-        *reinterpret_cast<float4*>(dst + (long)ci * 4) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-}
-
-__device__ __forceinline__ float lane_pick(float v, int n) {          // v_readlane with a uniform lane index
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), n));
-}
-// lane n of `old` <- a wave-uniform value (v_writelane_b32; no clang builtin in this toolchain).  The
-// s_nop covers the "VALU writes SGPR -> v_writelane uses it" wait states for the readfirstlane result.
-__device__ __forceinline__ float lane_put(float uniform_val, int n, float old) {
-    const int sval = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, uniform_val));
-    int keep;      // gfx9 VALU reads one SGPR: the lane select goes through M0 (saved: the compiler owns it)
-    asm volatile("s_mov_b32 %1, m0\n\ts_mov_b32 m0, %3\n\ts_nop 3\n\tv_writelane_b32 %0, %2, m0\n\ts_mov_b32 m0, %1"
-                 : "+v"(old), "=&s"(keep) : "s"(sval), "s"(n));
-    return old;
-}
-
-// The parameter block is ~110 SGPRs wide; kept live across the state loop it spills into VGPR lanes
-// (v1: 293 v_writelane / 1411 v_readlane of spill code).  Fields that are only needed once per
-// (row, tile) -- row pointers, strides, the small per-row outputs -- are therefore read through the
-// kernarg segment pointer, laundered so that the loads stay where they are used (s_load, ~15 per
-// row and tile) instead of being hoisted out of every loop.
-typedef const __attribute__((address_space(4))) BwdArgs* cold_args_t;   // constant address space: s_load
-__device__ __forceinline__ cold_args_t cold_args() {
-    cold_args_t kp = (cold_args_t)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(kp));
-    return kp;
-}
-
-// L2 warm-up of the NEXT tile's u / delta / dout segments of a row (2.5 KB each at T = 10): lanes 0..nl-1 touch
-// one 128-byte line each.  Issued as LDS-DMA into a 256-byte dummy area: no VGPR destination, so nothing the
-// compiler could reuse while the load is in flight (an asm load INTO a register counts as written at once and
-// its register was re-used as the next address: memory faults).  Untracked like the B/C stream; the caller's
-// lds_dma_wait() at the end of the staging block retires them.  Turns the ~2 us HBM miss at the top of the next
-// row step into an L2 hit.
-__device__ __forceinline__ void touch_lines(const void* seg, int nbytes, int lane, unsigned lds_dummy) {
-    const char* pa = reinterpret_cast<const char*>(seg) + lane * 128;
-    if (lane * 128 < nbytes) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(pa), "s"(lds_dummy) : "memory");
-    }
-}
-
-// Sum of one float2 column over the RR row slabs, fixed order w = 0 .. RR-1.  All RR reads are issued
-// before the first add: with a run-time trip count hipcc emits read / s_waitcnt lgkmcnt(0) / add per
-// slab, i.e. RR LDS latencies back to back (~2000 cycles per state at RR = 16, profiles/r02_bwd2_phases.txt).
-template <int RR>
-__device__ __forceinline__ float2 colsum_fixed(const float* __restrict__ colp, int stride) {
-    float2 v[RR];
-#pragma unroll
-    for (int w = 0; w < RR; ++w) v[w] = *reinterpret_cast<const float2*>(colp + w * stride);
-    float2 s = make_float2(0.f, 0.f);
-#pragma unroll
-    for (int w = 0; w < RR; ++w) { s.x += v[w].x; s.y += v[w].y; }
-    return s;
-}
-
-__device__ __forceinline__ float2 colsum(const float* __restrict__ colp, int stride, int R) {
-    // batches of 8 reads in flight (16 temporaries): more would push the 128-VGPR build into spills
-    float2 s = make_float2(0.f, 0.f);
-    int w = 0;
-    for (; w + 8 <= R; w += 8) {
-        const float2 t = colsum_fixed<8>(colp + w * stride, stride);
-        s.x += t.x; s.y += t.y;
-    }
-    if (w + 4 <= R) {
-        const float2 t = colsum_fixed<4>(colp + w * stride, stride);
-        s.x += t.x; s.y += t.y;
-        w += 4;
-    }
-    for (; w < R; ++w) {
-        const float2 v = *reinterpret_cast<const float2*>(colp + w * stride);
-        s.x += v.x; s.y += v.y;
-    }
-    return s;
-}
-
-}  // namespace
-
 template <typename io_t, int T, bool GLDS, bool REV, bool DET>
 __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, int b, int g, int chunk) {
     constexpr int TILE = 64 * T;
@@ -159,6 +56,8 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
     const io_t* __restrict__ Cg = reinterpret_cast<const io_t*>(p.C) + (long)b * p.C_bs + (long)g * p.C_gs;
     // where this workgroup's dB/dC sums go: the tensors themselves (it owns the whole group) or
     // its slab of the caller's workspace, summed over the P chunks by reduce_partials_kernel
+    // (scan_bwd3.hip, scan_bwd4.hip and scan_bwdr.hip hold the same block: behind one function returning the four
+    // values the compiler numbers the merged values differently and the kernels' register assignment changes)
     float* __restrict__ oB;
     float* __restrict__ oC;
     long o_nsB, o_nsC;
@@ -190,7 +89,7 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
             plan.issue_async(dst, reinterpret_cast<const float*>(Bg), reinterpret_cast<const float*>(Cg), (int)p.B_ns,
                              (int)p.C_ns, n0, nbn, tile, L, NB * TILE);
         } else {
-            stage_tile2<io_t, T>(dst, Bg, Cg, p.B_ns, p.C_ns, n0, nbn, NB, tile, L, REV, vec);
+            stage_bc<io_t, T>(dst, Bg, Cg, p.B_ns, p.C_ns, n0, nbn, NB, 1, tile, L, REV, vec, true);
         }
     };
 
@@ -280,9 +179,9 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
                     const int m0 = REV ? (L - l0n - TILE < 0 ? 0 : L - l0n - TILE) : l0n;         // first memory element
                     const int m1 = REV ? L - l0n : (l0n + TILE < L ? l0n + TILE : L);
                     const int nb = (m1 - m0) * (int)sizeof(io_t);
-                    touch_lines(reinterpret_cast<const io_t*>(kq->f.u) + (long)b * kq->f.u_bs + (long)urn * kq->f.u_ds + m0, nb, lane, touch_sink);
-                    touch_lines(reinterpret_cast<const io_t*>(kq->f.delta) + (long)b * kq->f.dt_bs + (long)rn * kq->f.dt_ds + m0, nb, lane, touch_sink);
-                    touch_lines(reinterpret_cast<const io_t*>(kq->dout) + (long)b * kq->g_bs + (long)grn * kq->g_ds + m0, nb, lane, touch_sink);
+                    touch_line(reinterpret_cast<const char*>(reinterpret_cast<const io_t*>(kq->f.u) + (long)b * kq->f.u_bs + (long)urn * kq->f.u_ds + m0) + lane * 128, lane * 128 < nb, touch_sink);
+                    touch_line(reinterpret_cast<const char*>(reinterpret_cast<const io_t*>(kq->f.delta) + (long)b * kq->f.dt_bs + (long)rn * kq->f.dt_ds + m0) + lane * 128, lane * 128 < nb, touch_sink);
+                    touch_line(reinterpret_cast<const char*>(reinterpret_cast<const io_t*>(kq->dout) + (long)b * kq->g_bs + (long)grn * kq->g_ds + m0) + lane * 128, lane * 128 < nb, touch_sink);
                 }
             }
             for (int sb = 0; sb < nsb; ++sb) {
@@ -295,10 +194,10 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
 #pragma unroll 1
                 for (int nn = 0; nn < nend; ++nn) {
                     const int n = n0 + nn;
-                    const float An = lane_pick(Av, n);
+                    const float An = lane_bcast(Av, n);
                     const float A2 = An * kLog2e;
-                    const float x0 = lane_pick(X0v, n);
-                    const float carry = lane_pick(Rvv, n);
+                    const float x0 = lane_bcast(X0v, n);
+                    const float carry = lane_bcast(Rvv, n);
                     const float* tB = cur + nn * TILE;
                     const float* tC = tB + NB * TILE;
                     float a[T], xs[T], gc[T];
@@ -436,14 +335,9 @@ __device__ __forceinline__ void scan_bwd2_body(const BwdArgs& q, float* smem, in
 
 template <typename io_t, int T, bool GLDS, bool DET>
 __device__ __forceinline__ void scan_bwd2_entry(const BwdArgs& q, float* smem) {
-    const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
-    const int per_b = q.f.G * q.P;                    // workgroups per batch entry
-    const int b = lb / per_b;
-    const int rem = lb - b * per_b;
-    const int g = rem / q.P;
-    const int chunk = rem - g * q.P;
-    if ((q.f.rev_mask >> g) & 1u) scan_bwd2_body<io_t, T, GLDS, true, DET>(q, smem, b, g, chunk);
-    else scan_bwd2_body<io_t, T, GLDS, false, DET>(q, smem, b, g, chunk);
+    const BwdBlock w = bwd_block(q, 1);
+    if ((q.f.rev_mask >> w.g) & 1u) scan_bwd2_body<io_t, T, GLDS, true, DET>(q, smem, w.b, w.g, w.chunk);
+    else scan_bwd2_body<io_t, T, GLDS, false, DET>(q, smem, w.b, w.g, w.chunk);
 }
 
 template <typename io_t, int T, bool GLDS, int MAXW>
@@ -465,18 +359,7 @@ template <typename io_t, int T, bool GLDS, int MAXW>
 static hipError_t launch_bwd2_t(const BwdArgs& a, hipStream_t stream) {
     const size_t lds = bwd2_lds_bytes(T, a.f.R, a.f.NB, a.f.N, a.slab2 != 0, a.RB);
     const int grid = a.f.batch * a.f.G * a.P;
-    if (a.rpart) {
-        constexpr auto kern = scan_bwd2_det_kernel<io_t, T, GLDS, MAXW>;
-        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
-    } else {
-        constexpr auto kern = scan_bwd2_kernel<io_t, T, GLDS, MAXW>;
-        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_reduce_after(a, stream);
+    return launch_bwd_pair<scan_bwd2_det_kernel<io_t, T, GLDS, MAXW>, scan_bwd2_kernel<io_t, T, GLDS, MAXW>>(grid, a.f.R * 64, lds, a, stream);
 }
 
 template <typename io_t, int T, bool GLDS>

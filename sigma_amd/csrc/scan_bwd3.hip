@@ -33,22 +33,9 @@ namespace {
 constexpr int kT3 = 5;                 // elements per lane
 constexpr int kTile3 = 64 * kT3;       // 320
 
-typedef const __attribute__((address_space(4))) BwdArgs* cold_args3_t;   // see scan_bwd2.hip: cold_args()
-__device__ __forceinline__ cold_args3_t cold_args3() {
-    cold_args3_t kp = (cold_args3_t)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(kp));
-    return kp;
-}
-
-__device__ __forceinline__ float lane_put3(float uniform_val, int n, float old) {
-    const int sval = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, uniform_val));
-    int keep;
-    asm volatile("s_mov_b32 %1, m0\n\ts_mov_b32 m0, %3\n\ts_nop 3\n\tv_writelane_b32 %0, %2, m0\n\ts_mov_b32 m0, %1"
-                 : "+v"(old), "=&s"(keep) : "s"(sval), "s"(n));
-    return old;
-}
-
-// register staging (16-bit IO, unaligned tensors): all N states of one tile -> dst [arr][N][TILE]
+// register staging (16-bit IO, unaligned tensors): all N states of one tile -> dst [arr][N][TILE].  Kept apart from
+// stage_bc (scan_device.h), which it equals with n0 = 0, nbn = NB = N, W = 1: the state test of the blocked form
+// (nn < nbn) does not fold away and both kernels compile to different code.
 template <typename io_t>
 __device__ __forceinline__ void stage_tile3(float* __restrict__ dst, const io_t* __restrict__ Bg, const io_t* __restrict__ Cg,
                                             long B_ns, long C_ns, int N, int tile, int L, bool rev, bool vec) {
@@ -139,7 +126,7 @@ __device__ __forceinline__ void scan_bwd3_body(const BwdArgs& q, float* smem, in
         for (int step = 0; step < RB; ++step) {
             const int rl = step * slots + slot;           // row inside the chunk
             const int r = row_c0 + rl;
-            cold_args3_t kq = cold_args3();
+            cold_args_t kq = cold_args();
             const int rpg = kq->f.rows_per_group;
             const int ur = r - ((g - (g >> kq->f.u_gshift)) * rpg);
             const int gr = r - ((g - (g >> kq->g_gshift)) * rpg);
@@ -227,8 +214,8 @@ __device__ __forceinline__ void scan_bwd3_body(const BwdArgs& q, float* smem, in
                     accB[s][k] = fmaf(dx, dlu[k], accB[s][k]);    // this row's term of dB[n, l]
                     accC[s][k] = fmaf(gg[k], xs[k], accC[s][k]);  // this row's term of dC[n, l]
                 }
-                rvout_v = lane_put3(e, s, rvout_v);
-                dA_v = lane_put3(wave_sum(dAp), s, dA_v);
+                rvout_v = lane_put(e, s, rvout_v);
+                dA_v = lane_put(wave_sum(dAp), s, dA_v);
                 // The four states are unrolled only for static accumulator indices.  Left alone, hipcc sinks the
                 // psx / psa updates of all four states below the last one and keeps dx, B and t of every state
                 // alive until then (+15 registers per state: 143 instead of 87 VGPRs).  Pinning the sums here
@@ -237,7 +224,7 @@ __device__ __forceinline__ void scan_bwd3_body(const BwdArgs& q, float* smem, in
                 for (int k = 0; k < T; ++k) asm volatile("" : "+v"(psx[k]), "+v"(psa[k]));
             }
 
-            cold_args3_t ke = cold_args3();
+            cold_args_t ke = cold_args();
             if (lane < 4) {
                 sRv[rl * N + nq0 + lane] = rvout_v;
                 row_result<DET>(ke, ke->dA + (long)pr * ke->dA_ds + (long)(nq0 + lane) * ke->dA_ns, b, pr, nq0 + lane, j == ntiles - 1, dA_v);
@@ -347,14 +334,9 @@ __device__ __forceinline__ void scan_bwd3_body(const BwdArgs& q, float* smem, in
 // MAXW = 16: 128-VGPR budget (4 waves per SIMD); MAXW = 12: 168 VGPRs (3 waves per SIMD, no spills)
 template <typename io_t, bool GLDS, bool DET>
 __device__ __forceinline__ void scan_bwd3_entry(const BwdArgs& q, float* smem) {
-    const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
-    const int per_b = q.f.G * q.P;
-    const int b = lb / per_b;
-    const int rem = lb - b * per_b;
-    const int g = rem / q.P;
-    const int chunk = rem - g * q.P;
-    if ((q.f.rev_mask >> g) & 1u) scan_bwd3_body<io_t, GLDS, true, DET>(q, smem, b, g, chunk);
-    else scan_bwd3_body<io_t, GLDS, false, DET>(q, smem, b, g, chunk);
+    const BwdBlock w = bwd_block(q, 1);
+    if ((q.f.rev_mask >> w.g) & 1u) scan_bwd3_body<io_t, GLDS, true, DET>(q, smem, w.b, w.g, w.chunk);
+    else scan_bwd3_body<io_t, GLDS, false, DET>(q, smem, w.b, w.g, w.chunk);
 }
 
 template <typename io_t, bool GLDS, int MAXW>
@@ -377,18 +359,7 @@ static hipError_t launch_bwd3_w(const BwdArgs& a, hipStream_t stream) {
     const int nw = a.f.R;                                  // waves per workgroup = slots * Q
     const size_t lds = bwd3_lds_bytes(nw, a.f.N, a.RB);
     const int grid = a.f.batch * a.f.G * a.P;
-    if (a.rpart) {
-        constexpr auto kern = scan_bwd3_det_kernel<io_t, GLDS, MAXW>;
-        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(nw * 64), lds, stream, a);
-    } else {
-        constexpr auto kern = scan_bwd3_kernel<io_t, GLDS, MAXW>;
-        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(nw * 64), lds, stream, a);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_reduce_after(a, stream);
+    return launch_bwd_pair<scan_bwd3_det_kernel<io_t, GLDS, MAXW>, scan_bwd3_kernel<io_t, GLDS, MAXW>>(grid, nw * 64, lds, a, stream);
 }
 
 template <typename io_t, bool GLDS>

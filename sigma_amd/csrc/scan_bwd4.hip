@@ -30,38 +30,6 @@
 
 namespace sigma {
 
-namespace {
-
-typedef const __attribute__((address_space(4))) BwdArgs* cold4_t;   // kernarg segment: s_load (see scan_bwd2.hip)
-__device__ __forceinline__ cold4_t cold_args4() {
-    cold4_t kp = (cold4_t)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(kp));
-    return kp;
-}
-
-// sum of one column over the W wave slabs, fixed order, reads batched ahead of the adds
-template <int RR>
-__device__ __forceinline__ float colsum1_fixed(const float* __restrict__ colp, int stride) {
-    float v[RR];
-#pragma unroll
-    for (int w = 0; w < RR; ++w) v[w] = colp[w * stride];
-    float s = 0.0f;
-#pragma unroll
-    for (int w = 0; w < RR; ++w) s += v[w];
-    return s;
-}
-__device__ __forceinline__ float colsum1(const float* __restrict__ colp, int stride, int W) {
-    float s = 0.0f;
-    int w = 0;
-    for (; w + 12 <= W; w += 12) s += colsum1_fixed<12>(colp + w * stride, stride);
-    if (w + 8 <= W) { s += colsum1_fixed<8>(colp + w * stride, stride); w += 8; }
-    if (w + 4 <= W) { s += colsum1_fixed<4>(colp + w * stride, stride); w += 4; }
-    for (; w < W; ++w) s += colp[w * stride];
-    return s;
-}
-
-}  // namespace
-
 template <bool REV, bool DET>
 __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, int b, int g, int chunk, int seg) {
     constexpr int T = kT4;
@@ -172,7 +140,7 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
             asm volatile("" : "+v"(lbase));
             const int rl = (rb * W + wave) * 4 + qr;   // row inside the chunk (per DPP row)
             const int r = row_c0 + rl;
-            cold4_t kq = cold_args4();
+            cold_args_t kq = cold_args();
             const int rpg = kq->f.rows_per_group;
             const int ur = r - ((g - (g >> kq->f.u_gshift)) * rpg);   // same row of group g >> u_gshift
             const int gr = r - ((g - (g >> kq->g_gshift)) * rpg);
@@ -230,7 +198,7 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
                     // next step of THIS wave: same tile, next row block -- or the tile to the left of its first rows
                     const int jn = (rb + 1 < RB) ? j : j - 1;
                     if (jn >= t_lo) {
-                        cold4_t kt = cold_args4();
+                        cold_args_t kt = cold_args();
                         const int trow = lane / 6, tline = lane - trow * 6;          // 24 lanes: 4 rows x 6 lines
                         const int rn = row_c0 + (((rb + 1 < RB) ? rb + 1 : 0) * W + wave) * 4 + trow;
                         const int rpgt = kt->f.rows_per_group;
@@ -242,9 +210,9 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
                         const bool on = trow < 4 && tline * 32 < (m1 - m0) + 31;
                         const int me = m0 + tline * 32 < m1 ? m0 + tline * 32 : m1 - 1;                // element inside the line
                         const unsigned sink = (unsigned)(uintptr_t)(lptr_t)sSink;
-                        touch_line4(reinterpret_cast<const char*>(reinterpret_cast<const float*>(kt->f.u) + (long)b * kt->f.u_bs + (long)urn * kt->f.u_ds + me), on, sink);
-                        touch_line4(reinterpret_cast<const char*>(reinterpret_cast<const float*>(kt->f.delta) + (long)b * kt->f.dt_bs + (long)rn * kt->f.dt_ds + me), on, sink);
-                        touch_line4(reinterpret_cast<const char*>(reinterpret_cast<const float*>(kt->dout) + (long)b * kt->g_bs + (long)grn * kt->g_ds + me), on, sink);
+                        touch_line(reinterpret_cast<const char*>(reinterpret_cast<const float*>(kt->f.u) + (long)b * kt->f.u_bs + (long)urn * kt->f.u_ds + me), on, sink);
+                        touch_line(reinterpret_cast<const char*>(reinterpret_cast<const float*>(kt->f.delta) + (long)b * kt->f.dt_bs + (long)rn * kt->f.dt_ds + me), on, sink);
+                        touch_line(reinterpret_cast<const char*>(reinterpret_cast<const float*>(kt->dout) + (long)b * kt->g_bs + (long)grn * kt->g_ds + me), on, sink);
                     }
                 }
                 const float A2 = An * kLog2e;
@@ -353,7 +321,7 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
             // ---- per-row results of this tile (cold parameters re-read here)
             // Row indices are rebuilt from the (laundered) lane id: otherwise r, pr, lbase and the address parts the
             // compiler pre-computes from them stay live across the state loop -- in the 128-VGPR build as scratch spills.
-            cold4_t ke = cold_args4();
+            cold_args_t ke = cold_args();
             int lane_e = lane;
             asm volatile("" : "+v"(lane_e));
             const int li_e = lane_e & 15;
@@ -427,17 +395,9 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
 
 template <bool DET>
 __device__ __forceinline__ void scan_bwd4_entry(const BwdArgs& q, float* smem) {
-    const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
-    const int PS = q.P * q.S;                         // workgroups per (batch, group): row chunks x sequence segments
-    const int per_b = q.f.G * PS;
-    const int b = lb / per_b;
-    const int rem = lb - b * per_b;
-    const int g = rem / PS;
-    const int rem2 = rem - g * PS;
-    const int chunk = rem2 / q.S;
-    const int seg = rem2 - chunk * q.S;
-    if ((q.f.rev_mask >> g) & 1u) scan_bwd4_body<true, DET>(q, smem, b, g, chunk, seg);
-    else scan_bwd4_body<false, DET>(q, smem, b, g, chunk, seg);
+    const BwdBlock w = bwd_block(q, q.S);
+    if ((q.f.rev_mask >> w.g) & 1u) scan_bwd4_body<true, DET>(q, smem, w.b, w.g, w.chunk, w.seg);
+    else scan_bwd4_body<false, DET>(q, smem, w.b, w.g, w.chunk, w.seg);
 }
 
 template <int MAXW>
@@ -578,18 +538,7 @@ template <int MAXW>
 static hipError_t launch_bwd4_t(const BwdArgs& a, hipStream_t stream) {
     const size_t lds = bwd4_lds_bytes(a.f.R, a.f.N, a.slab2, a.RB, a.f.NB);
     const int grid = a.f.batch * a.f.G * a.P * a.S;
-    if (a.rpart) {
-        constexpr auto kern = scan_bwd4_det_kernel<MAXW>;
-        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
-    } else {
-        constexpr auto kern = scan_bwd4_kernel<MAXW>;
-        if (hipError_t e = raise_lds_cap<kern>(lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(a.f.R * 64), lds, stream, a);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_reduce_after(a, stream);
+    return launch_bwd_pair<scan_bwd4_det_kernel<MAXW>, scan_bwd4_kernel<MAXW>>(grid, a.f.R * 64, lds, a, stream);
 }
 
 // the pre-pass of the sequence split: W4 = waves per workgroup (<= 8) over the same rows, one workgroup per segment 1..S-1

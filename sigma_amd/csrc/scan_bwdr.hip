@@ -45,18 +45,6 @@ hipError_t bwdr_chain_timeouts_read(unsigned int* out) {
 
 namespace {
 
-// a + b with the halves / rows regrouped (semantics pinned by tools/ubench/lane_ops_probe.hip, as scan_quad.h):
-//   swap32: lanes 0-31 of the result = a[0:32] + a[32:64], lanes 32-63 = b[0:32] + b[32:64]
-//   swap16: DPP rows of the result = {a.r0 + a.r1, b.r0 + b.r1, a.r2 + a.r3, b.r2 + b.r3}
-__device__ __forceinline__ float rl_fold32(float a, float b) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
-}
-__device__ __forceinline__ float rl_fold16(float a, float b) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
-}
-
 // Sum of the dB / dC terms of a tile over the 64 lanes.  The 32 slots of a tile are (memory half hm, position j in the
 // half, array dB / dC).  rl_reduce_half takes the eight fold32(dB term, dC term) registers of ONE half (w[j]: lanes 0-31
 // = dB of position j summed over lane pairs l, l + 32; lanes 32-63 = dC) to ONE register in which every lane holds the sum
@@ -68,7 +56,7 @@ __device__ __forceinline__ float rl_fold16(float a, float b) {
 // checked lane by lane with a symbolic model (tools/rowlane_reduce_model.py prints the table above).
 // Hazard: a VALU write followed by a DPP read of the same VGPR needs two wait states.
 __device__ __forceinline__ float rl_reduce_half(const float (&w)[8]) {
-    const float z0 = rl_fold16(w[0], w[4]), z1 = rl_fold16(w[1], w[5]), z2 = rl_fold16(w[2], w[6]), z3 = rl_fold16(w[3], w[7]);
+    const float z0 = fold16(w[0], w[4]), z1 = fold16(w[1], w[5]), z2 = fold16(w[2], w[6]), z3 = fold16(w[3], w[7]);
     float q0, q1, ph;
     asm volatile(
         "s_nop 1\n\t"
@@ -380,7 +368,7 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
                     const float t = e * xprev;                      // dx * a_k * x_{k-1}
                     sAx[k] = fmaf(A2[s], t, sAx[k]);                // x ln 2 in the epilogue
                     dAacc[s] = fmaf(dl[k], t, dAacc[s]);
-                    w[k & 7] = rl_fold32(dx * dlu[k], gg[k] * xs[k]);  // this row's terms of dB[n, l] and dC[n, l], wave halves summed
+                    w[k & 7] = fold32(dx * dlu[k], gg[k] * xs[k]);  // this row's terms of dB[n, l] and dC[n, l], wave halves summed
                     if (kk == H) {                                  // the half walked first is complete: memory half REV ? 0 : 1
                         ph_first = rl_reduce_half(w);
                     }

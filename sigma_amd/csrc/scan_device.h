@@ -549,4 +549,156 @@ __device__ __forceinline__ void row_result(QP q, float* grad, int k, int pr, int
     }
 }
 
+// ---- B/C staging through registers ---------------------------------------------------------------
+// Register path of the B/C staging (16-bit IO types, unaligned tensors): rows of states [n0, n0+nbn)
+// for the W tiles starting at tile index tile0 into `dst` laid out [arr = B,C][NB][W][TILE] (floats,
+// memory order; with_c false: the B array only).  The f32 / aligned case streams with global_load_lds
+// instead (StagePlan above).  The backward kernels stage one tile at a time (W = 1).
+template <typename io_t, int T>
+__device__ __forceinline__ void stage_bc(float* __restrict__ dst, const io_t* __restrict__ Bg,
+                                         const io_t* __restrict__ Cg, long B_ns, long C_ns, int n0, int nbn, int NB,
+                                         int W, int tile0, int L, bool rev, bool vec, bool with_c) {
+    constexpr int TILE = 64 * T;
+    constexpr int CPR = TILE / 4;                      // 16-byte chunks per (state, tile) row
+    const int rows = NB * W;                           // rows per array in the LDS image
+    const int total = (with_c ? 2 : 1) * rows * CPR;
+    for (int ci = threadIdx.x; ci < total; ci += blockDim.x) {
+        const int row = ci / CPR;                      // arr * rows + nn * W + w
+        const int c4 = (ci - row * CPR) * 4;
+        const int arr = row / rows;
+        const int rr = row - arr * rows;
+        const int nn = rr / W;
+        const int w = rr - nn * W;
+        const int l0 = (tile0 + w) * TILE;
+        const int m = rev ? (L - l0 - TILE + c4) : (l0 + c4);
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (nn < nbn && m < L && m + 4 > 0) {
+            const io_t* __restrict__ srow = arr == 0 ? Bg + (long)(n0 + nn) * B_ns : Cg + (long)(n0 + nn) * C_ns;
+            load4_guard<io_t>(srow, m, L, vec, v);
+        }
+        *reinterpret_cast<float4*>(dst + (long)ci * 4) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+// ---- helpers shared by the backward kernel families ------------------------------------------------
+// The parameter block is ~110 SGPRs wide; kept live across the state loop it spills into VGPR lanes
+// (v1: 293 v_writelane / 1411 v_readlane of spill code).  Fields that are only needed once per
+// (row, tile) -- row pointers, strides, the small per-row outputs -- are therefore read through the
+// kernarg segment pointer, laundered so that the loads stay where they are used (s_load, ~15 per
+// row and tile) instead of being hoisted out of every loop.
+typedef const __attribute__((address_space(4))) BwdArgs* cold_args_t;   // constant address space: s_load
+__device__ __forceinline__ cold_args_t cold_args() {
+    cold_args_t kp = (cold_args_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    return kp;
+}
+
+// lane n of `old` <- a wave-uniform value (v_writelane_b32; no clang builtin in this toolchain).  The
+// s_nop covers the "VALU writes SGPR -> v_writelane uses it" wait states for the readfirstlane result.
+__device__ __forceinline__ float lane_put(float uniform_val, int n, float old) {
+    const int sval = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, uniform_val));
+    int keep;      // gfx9 VALU reads one SGPR: the lane select goes through M0 (saved: the compiler owns it)
+    asm volatile("s_mov_b32 %1, m0\n\ts_mov_b32 m0, %3\n\ts_nop 3\n\tv_writelane_b32 %0, %2, m0\n\ts_mov_b32 m0, %1"
+                 : "+v"(old), "=&s"(keep) : "s"(sval), "s"(n));
+    return old;
+}
+
+// a + b with the halves / rows regrouped (gfx950 lane swaps; semantics pinned by tools/ubench/lane_ops_probe.hip):
+//   swap32: lanes 0-31 of the result = a[0:32] + a[32:64], lanes 32-63 = b[0:32] + b[32:64]
+//   swap16: DPP rows of the result = {a.r0 + a.r1, b.r0 + b.r1, a.r2 + a.r3, b.r2 + b.r3}
+__device__ __forceinline__ float fold32(float a, float b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
+    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
+}
+__device__ __forceinline__ float fold16(float a, float b) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
+    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
+}
+
+// L2 warm-up of the u / delta / dout segments a wave loads in its NEXT row step: a lane for which `on` holds touches
+// the 128-byte line at pa.  Issued as LDS-DMA into a 256-byte dummy area: no VGPR destination, so nothing the
+// compiler could reuse while the load is in flight (an asm load INTO a register counts as written at once and
+// its register was re-used as the next address: memory faults).  Untracked like the B/C stream; the caller's
+// next lds_dma_wait() retires them.  Turns the ~2 us HBM miss that all waves of the workgroup would otherwise sit
+// out together at the top of the next row step into an L2 hit.
+__device__ __forceinline__ void touch_line(const char* pa, bool on, unsigned lds_dummy) {
+    if (on) {
+        unsigned keep;
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(pa), "s"(lds_dummy) : "memory");
+    }
+}
+
+// Sum of one float2 column over the RR row slabs, fixed order w = 0 .. RR-1.  All RR reads are issued
+// before the first add: with a run-time trip count hipcc emits read / s_waitcnt lgkmcnt(0) / add per
+// slab, i.e. RR LDS latencies back to back (~2000 cycles per state at RR = 16, profiles/r02_bwd2_phases.txt).
+// The float2 form (scan_bwd2) and the float form (scan_bwd4) stay two functions: as one template over the
+// element type the float2 sums of scan_bwd2 compile to different code.
+template <int RR>
+__device__ __forceinline__ float2 colsum_fixed(const float* __restrict__ colp, int stride) {
+    float2 v[RR];
+#pragma unroll
+    for (int w = 0; w < RR; ++w) v[w] = *reinterpret_cast<const float2*>(colp + w * stride);
+    float2 s = make_float2(0.f, 0.f);
+#pragma unroll
+    for (int w = 0; w < RR; ++w) { s.x += v[w].x; s.y += v[w].y; }
+    return s;
+}
+__device__ __forceinline__ float2 colsum(const float* __restrict__ colp, int stride, int R) {
+    // batches of 8 reads in flight (16 temporaries): more would push the 128-VGPR build into spills
+    float2 s = make_float2(0.f, 0.f);
+    int w = 0;
+    for (; w + 8 <= R; w += 8) {
+        const float2 t = colsum_fixed<8>(colp + w * stride, stride);
+        s.x += t.x; s.y += t.y;
+    }
+    if (w + 4 <= R) {
+        const float2 t = colsum_fixed<4>(colp + w * stride, stride);
+        s.x += t.x; s.y += t.y;
+        w += 4;
+    }
+    for (; w < R; ++w) {
+        const float2 v = *reinterpret_cast<const float2*>(colp + w * stride);
+        s.x += v.x; s.y += v.y;
+    }
+    return s;
+}
+// the same for one float column over the W wave slabs (batches of 12, 8, 4)
+template <int RR>
+__device__ __forceinline__ float colsum1_fixed(const float* __restrict__ colp, int stride) {
+    float v[RR];
+#pragma unroll
+    for (int w = 0; w < RR; ++w) v[w] = colp[w * stride];
+    float s = 0.0f;
+#pragma unroll
+    for (int w = 0; w < RR; ++w) s += v[w];
+    return s;
+}
+__device__ __forceinline__ float colsum1(const float* __restrict__ colp, int stride, int W) {
+    float s = 0.0f;
+    int w = 0;
+    for (; w + 12 <= W; w += 12) s += colsum1_fixed<12>(colp + w * stride, stride);
+    if (w + 8 <= W) { s += colsum1_fixed<8>(colp + w * stride, stride); w += 8; }
+    if (w + 4 <= W) { s += colsum1_fixed<4>(colp + w * stride, stride); w += 4; }
+    for (; w < W; ++w) s += colp[w * stride];
+    return s;
+}
+
+// Workgroup id -> (batch, group, row chunk, sequence segment) of a backward grid of batch x G x P x S workgroups
+// (S = 1 for the kernels that do not cut the sequence), after the XCD remap.
+struct BwdBlock { int b, g, chunk, seg; };
+__device__ __forceinline__ BwdBlock bwd_block(const BwdArgs& q, int S) {
+    const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
+    const int PS = q.P * S;                           // workgroups per (batch, group): row chunks x sequence segments
+    const int per_b = q.f.G * PS;
+    BwdBlock w;
+    w.b = lb / per_b;
+    const int rem = lb - w.b * per_b;
+    w.g = rem / PS;
+    const int rem2 = rem - w.g * PS;
+    w.chunk = rem2 / S;
+    w.seg = rem2 - w.chunk * S;
+    return w;
+}
+
 }  // namespace sigma

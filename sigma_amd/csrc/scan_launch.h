@@ -84,4 +84,24 @@ hipError_t launch_scan_fwd(const FwdArgs& a, int dtype, int T, bool glds, bool p
 hipError_t launch_scan_bwd(const BwdArgs& a, int dtype, int T, bool glds, hipStream_t stream);
 hipError_t launch_selftest(float* out, hipStream_t stream);
 
+// One backward launch: Det in deterministic mode (a.rpart), else Plain, with its dynamic-LDS cap raised, followed by
+// the reduce pass the backward needs.  (Det first: a translation unit emits its kernels in the order they are named.)
+template <auto Det, auto Plain>
+static hipError_t launch_bwd_pair(int grid, int block, size_t lds, const BwdArgs& a, hipStream_t stream) {
+    if (a.rpart) {
+        if (hipError_t e = raise_lds_cap<Det>(lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(Det, dim3(grid), dim3(block), lds, stream, a);
+    } else {
+        if (hipError_t e = raise_lds_cap<Plain>(lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(Plain, dim3(grid), dim3(block), lds, stream, a);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_reduce_after(a, stream);
+}
+
+// Error report of the C ABI (capi.hip): formats the thread-local message that sigma_scan_last_error() returns and
+// hands `code` back.  Internal to the library: not part of include/sigma_scan.h.
+__attribute__((visibility("hidden"))) int fail(int code, const char* fmt, ...);
+
 }  // namespace sigma

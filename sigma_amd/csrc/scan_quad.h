@@ -49,19 +49,6 @@ __device__ __forceinline__ void stage_tile4(float* dst, const float* Bg, const f
     }
 }
 
-// L2 warm-up of the u / delta / dout segments (640 B per row) the wave loads in its NEXT row step: lane
-// 6*row + line touches one 128-byte line through LDS-DMA into a dummy area (no VGPR destination; untracked like
-// the B/C stream, retired by the next vmcnt wait).  Issued a few states before the end of the current row step,
-// so the lines are still in L2 when the real loads arrive: the ~2 us HBM miss that all waves of the workgroup
-// would otherwise sit out together at the top of a row step becomes an L2 hit.
-__device__ __forceinline__ void touch_line4(const char* pa, bool on, unsigned lds_dummy) {
-    if (on) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(pa), "s"(lds_dummy) : "memory");
-    }
-}
-
 // positions 2q, 2q+1 of the lane's 10 (li = lane inside its DPP row); the image is in memory order
 template <bool REV>
 __device__ __forceinline__ void lds_read_pair(const float* __restrict__ tile, int li, int q, float (&v)[2]) {
@@ -129,18 +116,6 @@ __device__ __forceinline__ float row_rotate_left(float v) {
 // every lane <- lane (16*row + n) of its own DPP row (n wave-uniform)
 __device__ __forceinline__ float row_pick(float v, int addr4) {
     return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr4, __builtin_bit_cast(int, v)));
-}
-
-// a + b with the halves / rows regrouped (tools/ubench/lane_ops_probe.hip):
-//   swap32: lanes 0-31 of the result = a[0:32] + a[32:64], lanes 32-63 = b[0:32] + b[32:64]
-//   swap16: DPP rows of the result = {a.r0 + a.r1, b.r0 + b.r1, a.r2 + a.r3, b.r2 + b.r3}
-__device__ __forceinline__ float fold32(float a, float b) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
-}
-__device__ __forceinline__ float fold16(float a, float b) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
 }
 
 }  // namespace

@@ -89,40 +89,39 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _f32_vec4(tensors, any_dtype=()) -> bool:
+    """f32 `tensors`, and with `any_dtype` 16-byte aligned, unit inner stride, outer strides multiples of 4 elements:
+    what the kernels' 16-byte accesses need"""
+    if any(t.dtype != torch.float32 for t in tensors):
+        return False
+    return all(t.data_ptr() % 16 == 0 and t.stride(-1) == 1 and all(s % 4 == 0 for s in t.stride()[:-1])
+               for t in tuple(tensors) + tuple(any_dtype))
+
+
 def quad_backward_ok(u, delta, B, C) -> bool:
     """True when the quad-row backward (csrc/scan_bwd4.hip, ckpt_pitch 160) can take these operands: f32 IO,
     dstate in {4, 8, 16}, rows per group divisible by 4, L % 4 == 0, 16-byte aligned u / delta / B / C with
     strides that are multiples of 4 elements (plan_bwd4 in csrc/capi.hip is the authority and fails loudly)."""
-    if any(t.dtype != torch.float32 for t in (u, delta, B, C)):
-        return False
     Bv = B if B.dim() == 4 else B.unsqueeze(1)
     Cv = C if C.dim() == 4 else C.unsqueeze(1)
     n_groups, dstate, seqlen = Bv.shape[1], Bv.shape[2], Bv.shape[3]
     if dstate not in (4, 8, 16) or seqlen % 4 != 0 or delta.shape[1] % (4 * n_groups) != 0:
         return False
-    for t in (u, delta, Bv, Cv):
-        if t.data_ptr() % 16 != 0 or t.stride(-1) != 1 or any(s % 4 != 0 for s in t.stride()[:-1]):
-            return False
-    return True
+    return _f32_vec4((u, delta, Bv, Cv))
 
 
 def rowlane_ok(u, delta, B, C, dout=None) -> bool:
     """True when the row-lane kernels (csrc/scan_fwdr.hip / scan_bwdr.hip, ckpt_pitch 16) can take these operands: f32 IO,
     dstate in {4, 8, 16}, rows per group divisible by 64, L % 4 == 0, 16-byte aligned u / delta / B / C (/ dout) with
     strides that are multiples of 4 elements (rowlane_legal in csrc/capi.hip is the authority and fails loudly)."""
-    if any(t.dtype != torch.float32 for t in (u, delta, B, C)):
-        return False
     Bv = B if B.dim() == 4 else B.unsqueeze(1)
     Cv = C if C.dim() == 4 else C.unsqueeze(1)
     n_groups, dstate, seqlen = Bv.shape[1], Bv.shape[2], Bv.shape[3]
     if dstate not in (4, 8, 16) or seqlen % 4 != 0 or seqlen == 0 or delta.shape[1] % (64 * n_groups) != 0:
         return False
-    for t in (u, delta, Bv, Cv) + ((dout,) if dout is not None else ()):
-        if t.data_ptr() % 16 != 0 or t.stride(-1) != 1 or any(s % 4 != 0 for s in t.stride()[:-1]):
-            return False
-    if dstate * max(Bv.stride(2), Cv.stride(2)) + seqlen >= (1 << 29):
+    if not _f32_vec4((u, delta, Bv, Cv), () if dout is None else (dout,)):
         return False
-    return True
+    return dstate * max(Bv.stride(2), Cv.stride(2)) + seqlen < (1 << 29)
 
 
 _FINE_PITCHES = (_capi.SIGMA_SCAN_CKPT_PITCH_FINE, _capi.SIGMA_SCAN_CKPT_PITCH_320, _capi.SIGMA_SCAN_CKPT_PITCH_160,

@@ -31,47 +31,47 @@ Constants (``constants``).  Every line is a rounding of the kernels, U each unle
 v_rcp_f32 are 1 ulp = 2 U.  They are counted from the source, not fitted to what a kernel achieves.
 
   c = 3, per position a contribution travels (the larger of the two ways into x_t):
-      the carried part a x:  v_exp_f32 result 2 (scan_fwd.hip:203, scan_fwd4.hip:118, scan_fwdr.hip:194/435,
-      scan_bwd.hip:261, scan_bwd2.hip:315, scan_bwd3.hip:197, scan_bwd4.hip:264, scan_bwdr.hip:364) + the fma 1
-      (scan_fwd.hip:205/238, scan_fwd4.hip:120/134, scan_fwdr.hip:195/436, scan_bwd4.hip:267/277);
-      the injected part w:   delta * u 1 (scan_fwd.hip:154, scan_fwd4.hip:87, scan_fwdr.hip:152, scan_bwd4.hip:205)
-      + times B 1 (scan_fwd.hip:204, scan_fwd4.hip:119, scan_fwdr.hip:195, scan_bwd4.hip:265) + the fma 1.
+      the carried part a x:  v_exp_f32 result 2 (scan_fwd.hip:170, scan_fwd4.hip:118, scan_fwdr.hip:194/435,
+      scan_bwd.hip:232, scan_bwd2.hip:214, scan_bwd3.hip:184, scan_bwd4.hip:232, scan_bwdr.hip:352) + the fma 1
+      (scan_fwd.hip:172/205, scan_fwd4.hip:120/134, scan_fwdr.hip:195/436, scan_bwd4.hip:235/245);
+      the injected part w:   delta * u 1 (scan_fwd.hip:121, scan_fwd4.hip:87, scan_fwdr.hip:152, scan_bwd4.hip:173)
+      + times B 1 (scan_fwd.hip:171, scan_fwd4.hip:119, scan_fwdr.hip:195, scan_bwd4.hip:233) + the fma 1.
       A lane that is skipped by the scan network instead of walked costs v_exp 2 + one product 1 for its T >= 4
-      positions (scan_fwd.hip:211, scan_device.h:289-290 SIGMA_MSTEP), which the same 3 per position covers.
-  c_b = 5, the adjoint step e = a (g C + e) (scan_bwd4.hip:282/296-297, scan_bwdr.hip:549): g * C 1
-      (scan_bwd4.hip:266), the add 1, the product 1, v_exp 2.
+      positions (scan_fwd.hip:178, scan_device.h:289-290 SIGMA_MSTEP), which the same 3 per position covers.
+  c_b = 5, the adjoint step e = a (g C + e) (scan_bwd4.hip:250/264-265, scan_bwdr.hip:537): g * C 1
+      (scan_bwd4.hip:234), the add 1, the product 1, v_exp 2.
   k = 2.5 + (T - 1) + levels_log, roundings that land in the exponent, relative to sum |delta A|:
-      A * log2(e) 1 and the constant itself 0.5 (scan_bwd4.hip:250; scan_device.h:12), the product with delta or with
-      the lane's sum of delta 1 (scan_fwd.hip:203/211), the serial sum of the lane's T deltas T - 1 (scan_fwd.hip:159,
-      scan_fwd4.hip:89, scan_bwd4.hip:213, scan_bwd2.hip:321), and where the decay travels as a sum of log2 (the
+      A * log2(e) 1 and the constant itself 0.5 (scan_bwd4.hip:218; scan_device.h:12), the product with delta or with
+      the lane's sum of delta 1 (scan_fwd.hip:170/178), the serial sum of the lane's T deltas T - 1 (scan_fwd.hip:126,
+      scan_fwd4.hip:89, scan_bwd4.hip:181, scan_bwd2.hip:220), and where the decay travels as a sum of log2 (the
       wave-split forward, scan_device.h:216-231: 6 adds; the row-lane segment summaries, scan_fwdr.hip:199 and
-      scan_bwdr.hip:559: one fma per tile of the segment, after a 16-term serial sum scan_fwdr.hip:174) those adds.
+      scan_bwdr.hip:547: one fma per tile of the segment, after a 16-term serial sum scan_fwdr.hip:174) those adds.
       T and the segment geometry come from the planner's report.
   c_0 = levels + 2, once per output: the fma of each level of the scan network (scan_device.h:297-308: 6;
-      scan_quad.h:94-113: 4; none in the row-lane kernels), the hand-over of the state entering the lane
-      (scan_fwd.hip:227, scan_fwd4.hip:125) 1 and, with sequence segments, the fma that applies a summary 1 per segment.
-  c_r = N + 1: the sum over the states is a serial fma chain started from D u (scan_fwd.hip:155/239,
+      scan_quad.h:81-100: 4; none in the row-lane kernels), the hand-over of the state entering the lane
+      (scan_fwd.hip:194, scan_fwd4.hip:125) 1 and, with sequence segments, the fma that applies a summary 1 per segment.
+  c_r = N + 1: the sum over the states is a serial fma chain started from D u (scan_fwd.hip:122/206,
       scan_fwd4.hip:88/135; the row-lane kernels add NS = N / waves states serially, then the waves and D u,
       scan_fwdr.hip:196/214/403, at most as deep).  c_o = c_0 + c_r; c_g = c_0 + c_r + 2 (the gradient forms
-      dx = g C + e 1, scan_bwd4.hip:296, and the product with delta or u 1, scan_bwd4.hip:398/414).
+      dx = g C + e 1, scan_bwd4.hip:264, and the product with delta or u 1, scan_bwd4.hip:366/382).
   esp_t, the relative error of delta from softplus_ref (scan_device.h:181-191), with kappa = |raw| sigmoid / softplus
-      the condition of softplus: raw = delta + bias 1 kappa (scan_fwd.hip:150), raw * log2(e) 1.5 kappa (:183),
+      the condition of softplus: raw = delta + bias 1 kappa (scan_fwd.hip:117), raw * log2(e) 1.5 kappa (:183),
       v_exp 2 (:183), v_log 2 and * ln 2 1.5 (:185), v_rcp 2, the two products 2 (:187); 1 + e is undone by w - 1
       (Kahan).  esp = 9.5 + 2.5 kappa, rounded up to 10 + 2.5 kappa.  It enters w (esp |w|) and the exponent (k_t = k + esp).
-  c_sig = esp + 15, softplus' (the largest over the families): scan_bwd4.hip:381-393 rebuilds u sdxB from
+  c_sig = esp + 15, softplus' (the largest over the families): scan_bwd4.hip:349-361 rebuilds u sdxB from
       (delta u) sdxB / delta (v_rcp 2, two products 2, delta u 1: 5) and sigmoid as 1 - exp(-delta) (the error of delta,
       esp, at a condition <= 1; v_exp and the subtraction near 0.25, or the degree-7 series: 10 at most,
-      scan_bwd4.hip:379); the others take e / (1 + e) (scan_bwd2.hip:420-421, scan_bwd3.hip:291-292,
-      scan_bwd.hip:376: 2.5 (1 - sigmoid) |raw| + 7 <= esp + 15).
+      scan_bwd4.hip:347); the others take e / (1 + e) (scan_bwd2.hip:319-320, scan_bwd3.hip:278-279,
+      scan_bwd.hip:347: 2.5 (1 - sigmoid) |raw| + 7 <= esp + 15).
   under_t = ETA (4 + |u B| + (1 + |A|) max_t X), ETA = 2^-126 / U: a delta, a decay (or a product of decays) or a
       product below 2^-126 may be flushed to zero by v_exp_f32 / v_rcp_f32 / the multipliers; the allowance of each
-      travels through the same recurrence.  scan_bwd4.hip:383 returns ddelta = 0 where delta < 2^-126: ETA |dd_pre|.
+      travels through the same recurrence.  scan_bwd4.hip:351 returns ddelta = 0 where delta < 2^-126: ETA |dd_pre|.
   K_rows (dB, dC: the sum over the rows of a group): rows / P + P, the rows a workgroup adds (order taken as serial:
-      fold16 / fold32 / colsum1, scan_bwd4.hip:306/324) and the P slabs reduce_partials_kernel adds
-      (scan_bwd.hip:436-487); P = workgroups / (batch G segments) from the planner's report.
+      fold16 / fold32 / colsum1, scan_bwd4.hip:274/292) and the P slabs reduce_partials_kernel adds
+      (scan_bwd.hip:409-460); P = workgroups / (batch G segments) from the planner's report.
   K_row (dA, dD, ddelta_bias): row_sum_depth of tests/test_deterministic_cpu.py, default and deterministic form; dA
-      takes the same road as dD (scan_bwd4.hip:301/311/367, scan_bwd2.hip:371/402, scan_bwd3.hip:231/243,
-      scan_bwdr.hip:456); scan_bwd.hip adds its tiles in LDS first (:308/325/328): T + 6 + tiles + batch.
+      takes the same road as dD (scan_bwd4.hip:269/279/335, scan_bwd2.hip:270/301, scan_bwd3.hip:218/230,
+      scan_bwdr.hip:444); scan_bwd.hip adds its tiles in LDS first (:279/296/299): T + 6 + tiles + batch.
   16-bit IO: the operands are exact, the arithmetic is fp32, and out / du / ddelta -- through the binding dB / dC too,
       which it returns in the dtype of B / C (selective_scan_cuda_core.py bwd_ext, ``io_bc``); the C ABI writes them in
       fp32 -- are rounded to the IO format: half a unit in the last place of their own format (2^-8 bf16, 2^-11 f16, and
