@@ -105,7 +105,8 @@ int sigma_gemm_nn_split3(const sigma_gemm_params *params, void *stream);
  *       partial tiles are stored and summed by a second kernel (C = or C +=, deterministic); without it they are
  *       summed with fp32 atomics into C, which the CALLER then zero-fills unless accumulate = 1 (run-to-run
  *       differences at rounding level, like the reference's atomicAdd gradients,
- *       selective_scan_bwd_kernel.cuh:214-231).                                                             */
+ *       selective_scan_bwd_kernel.cuh:214-231).  A weight gradient has no bias, shared outputs or residuals:
+ *       params->bias, c_mod and residual must be NULL / 0 (SIGMA_OPS_ERR_ARG otherwise).                    */
 int sigma_gemm_tn_split3(const sigma_gemm_params *params, void *stream);
 
 /*   sigma_gemm_workspace_bytes
@@ -113,6 +114,23 @@ int sigma_gemm_tn_split3(const sigma_gemm_params *params, void *stream);
  *       partial results in two stages; 0 = every work item owns its output (no scratch needed); -1 = bad arguments.
  *       params->workspace / workspace_bytes themselves are ignored by the query.                                     */
 int64_t sigma_gemm_workspace_bytes(const sigma_gemm_params *params, int form);
+
+/*   sigma_gemm_plan
+ *       host-only: which kernel the launch described by `params` (form 0 = nt, 1 = nn, 2 = tn) runs and how, from the
+ *       same planning code as the entry points (nothing is launched, no pointer is dereferenced; params->workspace /
+ *       workspace_bytes decide between the two-stage sum and the atomics as they do in the launch).  0 and
+ *           out[0]  tile width (128, 96 or 64 columns; a tile has 128 rows)
+ *           out[1], out[2]  row tiles, column tiles          out[3], out[4]  reduction slices, elements per slice
+ *           out[5]  work items = problems x tiles x slices (the persistent grid runs at most 1024 at once)
+ *           out[6]  bf16 pieces (2 or 3) | 16 if the kernel variant that loads the residuals into its accumulators runs
+ *           out[7]  bits 0-1: epilogue, 0 = row-contiguous (16-byte stores through LDS), 1 = direct (dword stores),
+ *                             2 = row-contiguous with the transposed column range t_cols
+ *                   bits 2-3: residual loads, 0 = none, 1 = 16-byte vector loads, 2 = scalar loads
+ *                   bit 4: the work items do not each own their output (summed), bit 5: ... and are summed in two stages
+ *                   bits 6-7: how the kernel writes: 0 = store, 1 = read-add-store (accumulate), 2 = fp32 atomics
+ *                   bit 8: the second stage reads and writes four columns per thread
+ *       (all zero for an empty problem), or the SIGMA_OPS_ERR_* code with which the launch would be refused.        */
+int sigma_gemm_plan(const sigma_gemm_params *params, int form, int32_t out[8]);
 
 /*   sigma_gemm_selftest
  *       runs the three forms on a small ragged problem whose products are exact in fp32 and compares with host

@@ -166,7 +166,11 @@ SIGMA_SEG_LDS_HIST_BYTES = 32768    # include/sigma_ops.h
 
 # every symbol include/sigma_gemm.h declares
 GEMM_SYMBOLS = ("sigma_gemm_nt_split3", "sigma_gemm_nn_split3", "sigma_gemm_tn_split3")
-GEMM_AUX_SYMBOLS = ("sigma_gemm_selftest", "sigma_gemm_workspace_bytes")
+GEMM_AUX_SYMBOLS = ("sigma_gemm_selftest", "sigma_gemm_workspace_bytes", "sigma_gemm_plan")
+GEMM_FORMS = {"nt": 0, "nn": 1, "tn": 2}
+GEMM_EPILOGUES = ("rows", "direct", "transposed")      # sigma_gemm_plan out[7] bits 0-1
+GEMM_RES_LOADS = ("none", "vector", "scalar")          # bits 2-3
+GEMM_STORES = ("store", "accumulate", "atomic")        # bits 6-7
 
 # every symbol include/sigma_ops.h declares
 OPS_SYMBOLS = ("sigma_dwconv3x3_silu_fwd", "sigma_dwconv3x3_silu_bwd", "sigma_cross_merge_nhwc", "sigma_cross_split_nhwc",
@@ -282,11 +286,26 @@ def load() -> ctypes.CDLL:
     lib.sigma_gemm_selftest.restype = ctypes.c_int
     lib.sigma_gemm_workspace_bytes.argtypes = [P(GemmParams), ctypes.c_int]
     lib.sigma_gemm_workspace_bytes.restype = ctypes.c_int64
+    lib.sigma_gemm_plan.argtypes = [P(GemmParams), ctypes.c_int, P(ctypes.c_int32 * 8)]
+    lib.sigma_gemm_plan.restype = ctypes.c_int
     if lib.sigma_scan_abi_version() != SIGMA_SCAN_ABI_VERSION:
         raise SigmaHipUnavailable(
             f"ABI mismatch: library {lib.sigma_scan_abi_version()} vs binding {SIGMA_SCAN_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
+
+
+def gemm_plan(p: GemmParams, form, lib=None) -> Optional[dict]:
+    """sigma_gemm_plan decoded (include/sigma_gemm.h; host only): the kernel variant and regime of the launch `p`
+    describes, None where the launch would be refused.  form: 'nt' / 'nn' / 'tn' or 0 / 1 / 2."""
+    out = (ctypes.c_int32 * 8)()
+    f = GEMM_FORMS[form] if isinstance(form, str) else int(form)
+    if (lib or load()).sigma_gemm_plan(ctypes.byref(p), f, ctypes.byref(out)) != 0:
+        return None
+    bits = out[7]
+    return dict(form=("nt", "nn", "tn")[f], bn=out[0], ntm=out[1], ntn=out[2], slices=out[3], slice_k=out[4], items=out[5],
+                pieces=out[6] & 15, res=bool(out[6] & 16), epilogue=GEMM_EPILOGUES[bits & 3], res_load=GEMM_RES_LOADS[(bits >> 2) & 3],
+                summed=bool(bits & 16), two_stage=bool(bits & 32), store=GEMM_STORES[(bits >> 6) & 3], reduce_vec=bool(bits & 256))
 
 
 def last_error() -> str:

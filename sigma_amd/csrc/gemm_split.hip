@@ -337,7 +337,7 @@ gemm_split3_kernel(const GemmArgs g) {
     // RES: the accumulators of a tile START as its epilogue addends (C = residual (+ residual2) + A B): the loads land
     // straight in the accumulator registers while the first k-steps are staged, no registers of their own and nothing
     // added to the epilogue.  Wave-uniform base + 32-bit element offsets (host: M * ldr < 2^31); rows / columns past the
-    // matrix are clamped (their sums are never stored).
+    // matrix are clamped (their sums are never stored).  (res_rows: evaluated again on the host by host_res_rows, below)
     const bool res_rows = RES && (g.N & 3) == 0 && (g.ldr & 3) == 0 && (g.sR & 3) == 0 && (reinterpret_cast<uintptr_t>(g.R) & 15) == 0 &&
                           (g.R2 == nullptr || (reinterpret_cast<uintptr_t>(g.R2) & 15) == 0);
     auto init_acc = [&](const Item& it) {
@@ -521,6 +521,7 @@ gemm_split3_kernel(const GemmArgs g) {
             }
         }
     };
+    // (rows_ok: evaluated again on the host by host_rows_ok, below)
     const bool rows_ok = (g.N & 3) == 0 && (g.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(g.C) & 15) == 0 && (g.sC & 3) == 0;
 
     while (c_on) {
@@ -723,10 +724,15 @@ int64_t parts_bytes(const GemmArgs& g, int batch) {
 // (ws / ws_bytes from the caller) as plain partial stores + reduce_parts_kernel, otherwise with fp32 atomics into C (which
 // the caller then zero-filled or accumulates into).  Round 6: the 64 dword atomics per thread and item were HALF of a
 // weight-gradient launch (profiles/r06_gemm_phases.jsonl) and its shape-independent floor of ~50 us.
+// the scratch a caller passed carries the two-stage sum of a summed launch (launch_summed; reported by sigma_gemm_plan)
+bool two_stage_ok(const GemmArgs& g, int batch, const void* ws, int64_t ws_bytes) {
+    const int64_t need = parts_bytes(g, batch);
+    return need != 0 && ws != nullptr && ws_bytes >= need && aligned16(ws);
+}
+
 template <bool A_KS, bool B_KS>
 hipError_t launch_summed(GemmArgs& g, int batch, int pieces, void* ws, int64_t ws_bytes, bool accumulate, hipStream_t stream) {
-    const int64_t need = parts_bytes(g, batch);
-    if (need == 0 || ws == nullptr || ws_bytes < need || !aligned16(ws)) {
+    if (!two_stage_ok(g, batch, ws, ws_bytes)) {
         g.mode = 2;
         g.nparts = 0;
         return launch_any<A_KS, B_KS>(g, batch, pieces, stream);
@@ -862,7 +868,8 @@ int plan_tn(const sigma_gemm_params* p, Planned& pl) {
     int rc = fill_common(p, g);
     if (rc) return rc;
     if (p->N % 4 != 0 || p->K % 4 != 0) return SIGMA_OPS_ERR_ARG;
-    if (p->c_mod != 0 || p->residual) return SIGMA_OPS_ERR_ARG;      // nt / nn only
+    // nt / nn only; a weight gradient has no bias either (sigma_gemm.h: the tn formula has none)
+    if (p->c_mod != 0 || p->residual || p->bias) return SIGMA_OPS_ERR_ARG;
     pl.batch = p->batch > 0 ? p->batch : 1;
     pl.summed = false;
     pl.empty = p->N == 0 || p->K == 0 || p->M == 0;
@@ -921,6 +928,55 @@ extern "C" int64_t sigma_gemm_workspace_bytes(const sigma_gemm_params* p, int fo
     const int rc = form == 0 ? sigma::plan_nt(p, pl) : form == 1 ? sigma::plan_nn(p, pl) : form == 2 ? sigma::plan_tn(p, pl) : SIGMA_OPS_ERR_ARG;
     if (rc) return -1;
     return (pl.empty || !pl.summed) ? 0 : sigma::parts_bytes(pl.g, pl.batch);
+}
+
+namespace sigma {
+namespace {
+
+// The two epilogue predicates the kernel evaluates on its arguments, evaluated on the host for sigma_gemm_plan: the same
+// expressions as `rows_ok` and `res_rows` in gemm_split3_kernel (keep the two places equal), on the GemmArgs the
+// kernel would receive.
+bool host_rows_ok(const GemmArgs& g) { return (g.N & 3) == 0 && (g.ldc & 3) == 0 && aligned16(g.C) && (g.sC & 3) == 0; }
+bool host_res_rows(const GemmArgs& g) {
+    return (g.N & 3) == 0 && (g.ldr & 3) == 0 && (g.sR & 3) == 0 && aligned16(g.R) && (g.R2 == nullptr || aligned16(g.R2));
+}
+
+}  // namespace
+}  // namespace sigma
+
+extern "C" int sigma_gemm_plan(const sigma_gemm_params* p, int form, int32_t out[8]) {
+    if (!out) return SIGMA_OPS_ERR_ARG;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    sigma::Planned pl;
+    const int rc = form == 0 ? sigma::plan_nt(p, pl) : form == 1 ? sigma::plan_nn(p, pl) : form == 2 ? sigma::plan_tn(p, pl) : SIGMA_OPS_ERR_ARG;
+    if (rc) return rc;
+    if (pl.empty) return SIGMA_OPS_OK;
+    sigma::GemmArgs& g = pl.g;
+    const int pieces = p->pieces == 3 ? 3 : 2;                       // launch_any
+    const bool res = g.R != nullptr;
+    if (res && (pieces != 2 || form == 2)) return SIGMA_OPS_ERR_ARG; // launch_p: no such kernel (the launch fails)
+    const int bn = sigma::pick_bn(g.N);                              // launch_r
+    g.ntm = (int)((g.M + 127) / 128);
+    g.ntn = (g.N + bn - 1) / bn;
+    const long items = (long)pl.batch * g.ntm * g.ntn * g.slices;    // launch_cfg
+    if (items <= 0 || items > 0x7fffffffL) return SIGMA_OPS_ERR_ARG;
+    // launch_summed: the arguments the first-stage kernel receives
+    const bool two_stage = pl.summed && sigma::two_stage_ok(g, pl.batch, p->workspace, p->workspace_bytes);
+    bool reduce_vec = false;
+    if (pl.summed && two_stage) {
+        reduce_vec = (g.N & 3) == 0 && (g.ldc & 3) == 0 && (g.sC & 3) == 0 && sigma::aligned16(g.C);
+        g.C = static_cast<float*>(p->workspace); g.ldc = g.N; g.sC = 0; g.mode = 0;
+    } else if (pl.summed) {
+        g.mode = 2;
+    }
+    // the epilogue choice at the end of a tile in gemm_split3_kernel
+    const int epilogue = g.t_cols != 0 ? 2 : (g.mode != 2 && sigma::host_rows_ok(g)) ? 0 : 1;
+    const int res_load = !res ? 0 : sigma::host_res_rows(g) ? 1 : 2;
+    out[0] = bn; out[1] = g.ntm; out[2] = g.ntn; out[3] = g.slices; out[4] = g.slice_k;
+    out[5] = (int32_t)items;
+    out[6] = pieces | (res ? 16 : 0);
+    out[7] = epilogue | (res_load << 2) | (pl.summed ? 16 : 0) | (two_stage ? 32 : 0) | (g.mode << 6) | (reduce_vec ? 256 : 0);
+    return SIGMA_OPS_OK;
 }
 
 // Self test: the three kernel forms on operands whose products and sums are exact in fp32 (integers of small magnitude:

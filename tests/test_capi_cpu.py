@@ -236,3 +236,52 @@ def test_gemm_ragged_shared_outputs_and_transposed_range_are_planned_on_the_host
         if field == "batch":
             bad.strideA, bad.strideB = 64 * 32, 128 * 32
         assert q(bad, 0) == -1, field
+
+
+def test_gemm_plan_reports_the_kernel_variant_on_the_host():
+    """sigma_gemm_plan (include/sigma_gemm.h): tile width, tiles, slices, kernel variant, epilogue and residual load kind,
+    from the planning code of the entry points, without a GPU"""
+    def params(M, N, K, lda, ldb, ldc, **kw):
+        p = _capi.GemmParams()
+        p.M, p.N, p.K, p.lda, p.ldb, p.ldc = M, N, K, lda, ldb, ldc
+        p.A, p.Bt, p.C = 0x10000, 0x20000, 0x30000          # never dereferenced (16-byte aligned non-null)
+        p.batch, p.pieces = kw.pop("batch", 1), kw.pop("pieces", 2)
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+    plan = _capi.gemm_plan
+    a = plan(params(19200, 1536, 384, 384, 384, 1536), "nt")                 # in_proj of stage 2
+    assert (a["bn"], a["ntm"], a["ntn"], a["slices"], a["items"]) == (128, 150, 12, 1, 1800)
+    assert (a["pieces"], a["res"], a["epilogue"], a["store"], a["res_load"], a["summed"]) == (2, False, "rows", "store", "none", False)
+    assert plan(params(3000, 192, 96, 96, 96, 192), "nt")["bn"] == 96
+    assert plan(params(1001, 36, 68, 68, 68, 36), "nt")["bn"] == 64
+    assert plan(params(257, 70, 100, 100, 100, 70, pieces=3), "nt") == dict(a, bn=96, ntm=3, ntn=1, items=3, slice_k=128, pieces=3, epilogue="direct")
+    # the weight gradient of the stage-2 in_proj: 14 slices (the workspace query above); two-stage only with the scratch
+    w = params(19200, 1536, 384, 1536, 384, 384)
+    t = plan(w, "tn")
+    assert (t["bn"], t["ntm"], t["ntn"], t["slices"], t["items"]) == (128, 12, 3, 14, 504) and t["slice_k"] * 14 >= 19200 > t["slice_k"] * 13
+    assert (t["summed"], t["two_stage"], t["store"], t["epilogue"]) == (True, False, "atomic", "direct")
+    w.workspace, w.workspace_bytes = 0x50000, 14 * 1536 * 384 * 4
+    t = plan(w, "tn")
+    assert (t["summed"], t["two_stage"], t["store"], t["epilogue"], t["reduce_vec"]) == (True, True, "store", "rows", True)
+    w.workspace_bytes -= 1
+    assert plan(w, "tn")["store"] == "atomic"
+    # accumulate, a misaligned C, residuals as vector and as scalar loads
+    r = params(300, 768, 1536, 1536, 1536, 768, accumulate=1, residual=0x60000, ldr=768)
+    got = plan(r, "nt")
+    assert (got["res"], got["res_load"], got["epilogue"], got["store"]) == (True, "vector", "rows", "accumulate")
+    r.ldr, r.C = 770, 0x30004
+    got = plan(r, "nt")
+    assert (got["res_load"], got["epilogue"]) == ("scalar", "direct")
+    assert plan(params(257, 70, 100, 100, 100, 70, residual=0x60000, ldr=70), "nt")["res_load"] == "scalar"
+    x = plan(params(64, 128, 32, 32, 32, 96, Ct=0x40000, ldct=64, t_cols=32, strideC=2), "nt")
+    assert x["epilogue"] == "transposed"
+    # refused as the launch refuses: unknown form, K % 4, residuals with three pieces or on tn, a bias on tn
+    assert plan(params(19200, 1536, 384, 384, 384, 1536), 7) is None
+    assert plan(params(19200, 1536, 383, 384, 384, 1536), "nt") is None
+    assert plan(params(300, 768, 1536, 1536, 1536, 768, residual=0x60000, ldr=768, pieces=3), "nt") is None
+    assert plan(params(300, 768, 1536, 768, 1536, 1536, residual=0x60000, ldr=1536), "tn") is None
+    assert plan(params(300, 768, 1536, 768, 1536, 1536, bias=0x70000), "tn") is None
+    assert plan(params(300, 768, 1536, 768, 1536, 1536), "tn") is not None
+    assert plan(params(0, 768, 1536, 1536, 1536, 768), "nt")["items"] == 0       # empty: nothing is launched

@@ -387,19 +387,8 @@ def test_shared_outputs_sum_in_two_stages():
     _assert_close(acc, want + 1.0, bound + 1.0, "nt_sum accumulate")
 
 
-def _guarded(n, margin, fill=float("nan")):
-    """(buffer, view of n floats inside it): the margins on both sides (>= one row + 64 floats, multiples of 4 so that the
-    view stays 16-byte aligned) belong to the same allocation, so a store past either end of the view lands in memory the
-    test owns and is detected afterwards instead of faulting"""
-    assert margin % 4 == 0
-    buf = torch.full((n + 2 * margin,), fill, device=DEV)
-    return buf, buf[margin:margin + n]
-
-
-def _margins_intact(buf, n, margin):
-    torch.cuda.synchronize()
-    head, tail = buf[:margin], buf[margin + n:]
-    return bool(torch.isnan(head).all()) and bool(torch.isnan(tail).all())
+# guard bands: shared with the exact suite (tests/gemm_exact_ref.py)
+from tests.gemm_exact_ref import guarded as _guarded, margins_intact as _margins_intact  # noqa: E402
 
 
 def _call(name, p, dev):
@@ -490,3 +479,43 @@ def test_sliced_nn_of_one_problem_ignores_a_larger_c_mod(c_mod):
     first = c.clone()
     assert _call("sigma_gemm_nn_split3", p, a.device) == 0
     assert torch.equal(c, first)                                  # fixed summation order, no racing stores
+
+
+# ---- operands scaled per row and per column over 2^-40 .. 2^40 -----------------------------------------------------------
+
+def _pow2_scales(n, seed, lo=-40, hi=40):
+    """n powers of two with exponents spread evenly over [lo, hi], in a shuffled order"""
+    g = torch.Generator().manual_seed(seed)
+    e = torch.linspace(lo, hi, n).round()[torch.randperm(n, generator=g)]
+    return torch.pow(2.0, e).to(DEV)
+
+
+@pytest.mark.parametrize("form", ["nt", "nn", "tn"])
+def test_gemm_keeps_its_relative_bound_under_row_and_column_scales(form):
+    """C = diag(r) (A B) diag(c) with r, c powers of two from 2^-40 to 2^40: bf16 keeps fp32's exponent, so every piece,
+    product and sum scales exactly and the error bound relative to sum |a||b| must hold UNCHANGED (outputs range over
+    2^-80 .. 2^80; products and lo pieces stay normal in bf16 and fp32).  A scale shared by a tile, a narrower
+    accumulator or a piece held in fp16 anywhere would break it.  nt, nn, and tn with reduction slices."""
+    from sigma_amd import gemm
+    M, N, K = (8000, 132, 200) if form == "tn" else (300, 200, 132)          # tn: C is N x K, 8000 tokens in several slices
+    rows, cols = (N, K) if form == "tn" else (M, N)
+    r, c = _pow2_scales(rows, 91), _pow2_scales(cols, 92)
+    if form == "nt":
+        a, b = _rand(M, K, seed=93) * r[:, None], _rand(N, K, seed=94, scale=0.05) * c[:, None]
+        got, a64, b64 = gemm.gemm_nt(a, b), a.double(), b.double().t()
+    elif form == "nn":
+        a, b = _rand(M, K, seed=93) * r[:, None], _rand(K, N, seed=94, scale=0.05) * c[None, :]
+        got, a64, b64 = gemm.gemm_nn(a, b), a.double(), b.double()
+    else:
+        a, b = _rand(M, N, seed=93, scale=0.1) * r[None, :], _rand(M, K, seed=94) * c[None, :]
+        got, a64, b64 = gemm.gemm_tn(a, b), a.double().t(), b.double()
+    want, bound = a64 @ b64, _bound(a64, b64)
+    assert float(bound.min()) > 2.0 ** -110 and float(bound.max()) < 2.0 ** 100 and bool(torch.isfinite(got).all())
+    err = (got.double() - want).abs()
+    worst = float((err / bound).max())
+    assert worst < 3e-5, f"{form} scaled: max error / sum|a||b| = {worst:.3e}"
+    # the rms check of _assert_close per output element's own scale (a global rms would only see the largest scales)
+    rel = err / (r[:, None].double() * c[None, :].double())
+    ref = want / (r[:, None].double() * c[None, :].double())
+    rms = float(rel.pow(2).mean().sqrt() / ref.pow(2).mean().sqrt())
+    assert rms < 2e-5, f"{form} scaled: relative rms error {rms:.3e}"

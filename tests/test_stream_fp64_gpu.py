@@ -109,9 +109,11 @@ def launch_key(lib, name, args):
         form = name[11:13]
         need = int(lib.sigma_gemm_workspace_bytes(ctypes.byref(p), {"nt": 0, "nn": 1, "tn": 2}[form]))   # gemm_split.hip plan_*
         stage = "own" if need == 0 else ("two-stage" if p.workspace and p.workspace_bytes >= need else "atomic")
+        from sigma_amd import _capi
+        plan = _capi.gemm_plan(p, form, lib) or {}                  # sigma_gemm_plan: which kernel runs, with which epilogue
         return ("gemm", form, p.pieces or 2, p.batch > 1, p.a_mod > 0, bool(p.c_mod > 0 and p.batch > p.c_mod),
                 bool(p.k_slices), p.t_cols > 0, int(bool(p.residual)) + int(bool(p.residual2)), bool(p.bias),
-                bool(p.accumulate), stage)
+                bool(p.accumulate), plan.get("bn", 0), plan.get("epilogue", "refused"), stage)
     return None
 
 
@@ -929,29 +931,31 @@ _G = ("gemm",)
 # key -> (test function of tests/test_gemm_gpu.py, its arguments): test_gemm_cases_launch_their_census_keys RUNS each case
 # under the recorder and asserts that it launches the key; the census then only needs the key to be here
 GEMM_CASES = {
-    # (form, pieces, batch > 1, a_mod, c_mod summed, k_slices, t_cols, residuals, bias, accumulate, stage)
-    _G + ("nt", 2, False, False, False, False, False, 0, False, False, "own"): ("test_gemm_nt_against_fp64", ((19200, 384, 1536), False)),
-    _G + ("nt", 2, False, False, False, False, False, 0, True, False, "own"): ("test_gemm_nt_against_fp64", ((19200, 384, 1536), True)),
-    _G + ("nt", 2, False, False, False, False, False, 1, False, False, "own"): ("test_linear_with_the_residual_added_in_the_kernel",
+    # (form, pieces, batch > 1, a_mod, c_mod summed, k_slices, t_cols, residuals, bias, accumulate, tile width, epilogue, stage);
+    # tile width and epilogue kind are sigma_gemm_plan's report: a dispatch change that moves a model launch to another kernel
+    # variant or epilogue changes its key
+    _G + ("nt", 2, False, False, False, False, False, 0, False, False, 128, "rows", "own"): ("test_gemm_nt_against_fp64", ((19200, 384, 1536), False)),
+    _G + ("nt", 2, False, False, False, False, False, 0, True, False, 128, "rows", "own"): ("test_gemm_nt_against_fp64", ((19200, 384, 1536), True)),
+    _G + ("nt", 2, False, False, False, False, False, 1, False, False, 128, "rows", "own"): ("test_linear_with_the_residual_added_in_the_kernel",
                                                                                ((19200, 768, 384),)),
-    _G + ("nt", 2, False, False, False, False, True, 0, False, False, "own"): ("test_in_proj_with_channel_major_x_half_against_fp64",
+    _G + ("nt", 2, False, False, False, False, True, 0, False, False, 128, "transposed", "own"): ("test_in_proj_with_channel_major_x_half_against_fp64",
                                                                               ((2, 30, 40, 384, 768), False)),
-    _G + ("nt", 2, True, False, True, False, False, 0, False, False, "two-stage"): ("test_shared_outputs_sum_in_two_stages", ()),
-    _G + ("nn", 2, False, False, False, False, False, 0, False, False, "own"): ("test_gemm_nn_against_fp64", ((19200, 1536, 384),)),
-    _G + ("nn", 2, False, False, False, True, False, 0, False, False, "two-stage"):
+    _G + ("nt", 2, True, False, True, False, False, 0, False, False, 96, "rows", "two-stage"): ("test_shared_outputs_sum_in_two_stages", ()),
+    _G + ("nn", 2, False, False, False, False, False, 0, False, False, 128, "rows", "own"): ("test_gemm_nn_against_fp64", ((19200, 1536, 384),)),
+    _G + ("nn", 2, False, False, False, True, False, 0, False, False, 128, "rows", "two-stage"):
         ("test_gemm_nn_with_a_sliced_reduction_against_fp64", ((768, 19200, 384),)),
-    _G + ("nn", 2, True, True, False, False, False, 0, False, False, "own"):
+    _G + ("nn", 2, True, True, False, False, False, 0, False, False, 96, "rows", "own"):
         ("test_stacked_projections_of_the_scan_core_against_fp64", ((2, 768, 56, 24, 1200),)),
-    _G + ("nn", 2, True, True, False, False, False, 2, False, False, "own"):
+    _G + ("nn", 2, True, True, False, False, False, 2, False, False, 96, "rows", "own"):
         ("test_stacked_projections_of_the_scan_core_against_fp64", ((2, 768, 56, 24, 1200),)),
-    _G + ("nn", 2, True, False, False, False, False, 0, False, False, "own"):
+    _G + ("nn", 2, True, False, False, False, False, 0, False, False, 128, "rows", "own"):
         ("test_stacked_projections_of_the_scan_core_against_fp64", ((1, 1536, 80, 48, 300),)),
-    _G + ("nn", 2, True, False, False, False, False, 2, False, False, "own"):
+    _G + ("nn", 2, True, False, False, False, False, 2, False, False, 128, "rows", "own"):
         ("test_stacked_projections_of_the_scan_core_against_fp64", ((1, 1536, 80, 48, 300),)),
-    _G + ("tn", 2, False, False, False, False, False, 0, False, False, "own"): ("test_gemm_tn_against_fp64", ((300, 1536, 768),)),
-    _G + ("tn", 2, False, False, False, False, False, 0, False, True, "own"): ("test_gemm_tn_against_fp64", ((300, 1536, 768),)),
-    _G + ("tn", 2, False, False, False, False, False, 0, False, False, "two-stage"): ("test_gemm_tn_against_fp64", ((19200, 1536, 384),)),
-    _G + ("tn", 2, False, False, False, False, False, 0, False, True, "two-stage"): ("test_gemm_tn_against_fp64", ((19200, 1536, 384),)),
+    _G + ("tn", 2, False, False, False, False, False, 0, False, False, 128, "rows", "own"): ("test_gemm_tn_against_fp64", ((300, 1536, 768),)),
+    _G + ("tn", 2, False, False, False, False, False, 0, False, True, 128, "rows", "own"): ("test_gemm_tn_against_fp64", ((300, 1536, 768),)),
+    _G + ("tn", 2, False, False, False, False, False, 0, False, False, 128, "rows", "two-stage"): ("test_gemm_tn_against_fp64", ((19200, 1536, 384),)),
+    _G + ("tn", 2, False, False, False, False, False, 0, False, True, 128, "rows", "two-stage"): ("test_gemm_tn_against_fp64", ((19200, 1536, 384),)),
 }
 GEMM_COVERED = {k: f"tests/test_gemm_gpu.py::{fn}{list(args)}" for k, (fn, args) in GEMM_CASES.items()}
 _GEMM_RUNS = sorted({(fn, args) for fn, args in GEMM_CASES.values()}, key=repr)
@@ -968,7 +972,27 @@ def test_gemm_cases_launch_their_census_keys(run, record):
     assert want <= set(record), f"{fn}{args} does not launch {want - set(record)}"
 
 
-COVERED.update(GEMM_COVERED)
+def _gemm_exact_cases():
+    """census key -> the exact case of tests/test_gemm_exact_gpu.py that launches it (planned on the host, as
+    tests/test_gemm_exact_cpu.py does): where a key has an exact case, it is the one named"""
+    from sigma_amd import _capi
+    from tests.test_gemm_exact_gpu import CASES
+    lib = _capi.load()
+    exact = {}
+    for c in CASES:
+        p = c.params(c.FAKE)
+        need = int(lib.sigma_gemm_workspace_bytes(ctypes.byref(p), _capi.GEMM_FORMS[c.form]))
+        if need > 0 and c.ws != "none":
+            p.workspace, p.workspace_bytes = c.FAKE["ws"], need - (1 if c.ws == "short" else 0)
+        exact.setdefault(launch_key(lib, f"sigma_gemm_{c.form}_split3", (ctypes.byref(p), None)),
+                         f"tests/test_gemm_exact_gpu.py::test_exact_case[{c.name}]")
+    return exact
+
+
+GEMM_EXACT = _gemm_exact_cases()
+COVERED.update(GEMM_EXACT)
+for _k, _v in GEMM_COVERED.items():            # the fp64 case at the real shape is named as well
+    COVERED[_k] = f"{COVERED[_k]} + {_v}" if _k in COVERED else _v
 
 
 # ---------------------------------------------------------------------------------------------------------------------
