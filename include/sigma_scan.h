@@ -33,8 +33,10 @@
 extern "C" {
 #endif
 
-/* ABI 12 removed the cycle-counter read-out of the phase-profiling builds, along with those builds. */
-#define SIGMA_SCAN_ABI_VERSION 12
+/* ABI 12 removed the cycle-counter read-out of the phase-profiling builds, along with those builds.
+ * ABI 13 removed the chained walk of the row-lane backward: the options "rl_chain" and "rl_chain_timeouts" are unknown
+ * names now, and the workspace of a ckpt_pitch-16 backward no longer holds a hand-over area. */
+#define SIGMA_SCAN_ABI_VERSION 13
 
 /* dtype of u, delta, B, C, out, dout, du, ddelta  (input_t of the reference,
  * selective_scan.cpp:174: float / half / bfloat16).  A, D, delta_bias, x, dA,
@@ -179,8 +181,7 @@ typedef struct sigma_scan_bwd_params {
  * partials to a slot of its own in the workspace with plain stores (summed over its tiles in a fixed order), and the
  * pass that adds the dB / dC partials adds the slots in a fixed order too: the results are bitwise reproducible from run
  * to run, and dA, dD, ddelta_bias are fully WRITTEN (the caller need not zero them).  The plan (kernel family and
- * geometry) is the one without the bit; the workspace grows by the slots (sigma_scan_bwd_workspace_bytes).  The
- * chained walk of the row-lane backward (option "rl_chain") is not used in this mode. */
+ * geometry) is the one without the bit; the workspace grows by the slots (sigma_scan_bwd_workspace_bytes). */
 #define SIGMA_SCAN_BWD_DETERMINISTIC 1
 
 /* Forward: out, x <- scan(u, delta, A, B, C, D, delta_bias). */
@@ -227,13 +228,6 @@ int sigma_scan_abi_version(void);
  *   "bwd_wgs"                  quad-row backward: 2 = two workgroups of <= 8 waves per CU (A/B knob)
  *   "rl_waves"                 row-lane kernels (ckpt_pitch 16): state waves per 64-row block {4, 8, 16}; 0 = cost model
  *   "rl_segs"                  row-lane kernels: sequence segments (1 = never split, 2..64); 0 = cost model
- *   "rl_chain"                 row-lane backward: chained walk (row blocks laid end to end over exactly as many workgroups as
- *                              the chip holds, a cut row block hands its reverse carry to the neighbour): 2 = whenever
- *                              there are more row blocks than resident workgroups; 0 / 1 = never (measured: no gain)
- *   "rl_chain_timeouts"        READ-ONLY (get_option; set_option refuses it): hand-over waits of the chained walk that ran
- *                              out since the last read -- each one poisoned its row block's du / ddelta / dA with NaN (the
- *                              producer workgroup was not resident: another stream's kernel held its slot).  Reading
- *                              synchronises the device and resets the count; -1 on a device error.
  * Returns SIGMA_ERR_BAD_OPTION for unknown names / unsupported values. */
 int sigma_scan_set_option(const char *name, int value);
 int sigma_scan_get_option(const char *name);

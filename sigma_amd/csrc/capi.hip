@@ -39,7 +39,7 @@ using sigma::fail;
 std::atomic<int> g_opt_fwd_items{0}, g_opt_fwd_waves{0}, g_opt_fwd_tiles{0}, g_opt_fwd_nb{0};
 std::atomic<int> g_opt_bwd_items{0}, g_opt_bwd_waves{0}, g_opt_bwd_nb{0}, g_opt_no_glds{0}, g_opt_bwd_slab2{0}, g_opt_fwd_prefetch{0};
 std::atomic<int> g_opt_bwd_gen{0}, g_opt_bwd_rb{0}, g_opt_bwd_touch{0}, g_opt_bwd_sb{0}, g_opt_bwd_wgs{0}, g_opt_fwd_gen{0}, g_opt_bwd_seg{0};
-std::atomic<int> g_opt_rl_waves{0}, g_opt_rl_segs{0}, g_opt_rl_chain{0};
+std::atomic<int> g_opt_rl_waves{0}, g_opt_rl_segs{0};
 
 int elem_size(int dtype) { return dtype == SIGMA_DTYPE_F32 ? 4 : 2; }
 
@@ -266,7 +266,7 @@ Plan plan_bwd(const sigma_scan_fwd_params* p, bool vec) {
 
 // scan_bwd2 (scan_bwd2.hip): one checkpoint per backward tile, dstate <= 64.  A workgroup is R rows x
 // RB row blocks of one (batch, group); P = rows_per_group / (R * RB) workgroups share a group.
-struct Plan2 { bool ok; int items, rows, nb, RB, P, nacc, grid; bool glds, slab2; size_t lds; };
+struct Plan2 { bool ok; int items, rows, nb, RB, P, grid; bool glds, slab2; size_t lds; };
 
 Plan2 plan_bwd2(const sigma_scan_fwd_params* p, bool vec) {
     Plan2 pl;
@@ -307,7 +307,6 @@ Plan2 plan_bwd2(const sigma_scan_fwd_params* p, bool vec) {
         for (int d = 1; d <= rowblocks; ++d)
             if (rowblocks % d == 0 && (long)p->batch * p->n_groups * (rowblocks / d) >= kCUs) RB = d;
     }
-    const int nacc = 0;
     const int sl = g_opt_bwd_slab2.load();
     bool slab2 = sl != 2;                                            // two slab sets when they fit beside NB = 4
     while (sigma::bwd2_lds_bytes(T, R, NB, p->dstate, slab2, RB) > kLdsLimit) {
@@ -317,7 +316,7 @@ Plan2 plan_bwd2(const sigma_scan_fwd_params* p, bool vec) {
         else return pl;
     }
     pl.ok = true;
-    pl.items = T; pl.rows = R; pl.nb = NB; pl.RB = RB; pl.P = rowblocks / RB; pl.nacc = nacc;
+    pl.items = T; pl.rows = R; pl.nb = NB; pl.RB = RB; pl.P = rowblocks / RB;
     pl.grid = p->batch * p->n_groups * pl.P;
     pl.slab2 = slab2;
     pl.lds = sigma::bwd2_lds_bytes(T, R, NB, p->dstate, slab2, RB);
@@ -560,28 +559,6 @@ int64_t summary_floats(const sigma_scan_fwd_params* p, int S) {
     return S > 1 ? (int64_t)(S - 1) * p->batch * p->dim * (int64_t)p->dstate * 2 : 0;
 }
 
-// chained walk of the row-lane backward: hand-over slots [row blocks][N][64] floats + one flag per row block (reserved
-// for every row-lane backward, so that the workspace size does not depend on the device's occupancy answer)
-int64_t rowlane_chain_floats(const sigma_scan_fwd_params* p) {
-    const int64_t nrb = (int64_t)p->batch * (p->dim / 64);
-    return nrb * p->dstate * 64 + ((nrb + 3) / 4) * 4;
-}
-
-// tiles per workgroup of the chained walk, or 0: used when the row blocks do not fill whole rounds of resident
-// workgroups (768 blocks on 512 slots = two rounds, the second half empty: 1.5 rounds' worth of work in the time of 2)
-int rowlane_chain_tiles(const sigma_scan_fwd_params* p, int P, int S) {
-    const int mode = g_opt_rl_chain.load();
-    // measured (profiles/r04_rowlane_chain.txt): (16,3072,1200,N16) 800 us chained against 779 us in 1.5 plain rounds --
-    // the kernel is bound by the issue rate of a SIMD, and the workgroups of a half-empty last round simply run faster;
-    // the walk is kept for launches that are latency-bound per wave, on request only
-    if (mode != 2 || S != 1) return 0;
-    const long nrb = (long)p->batch * p->n_groups * P;
-    const int ntiles = (p->seqlen + 15) / 16;
-    const long cap = (long)kCUs * sigma::bwdr_resident_per_cu(p->dstate);
-    if (nrb <= cap || nrb * ntiles >= (1L << 31)) return 0;
-    return (int)((nrb * ntiles + cap - 1) / cap);
-}
-
 bool vec_ok_bwd(const sigma_scan_bwd_params* q) {
     const sigma_scan_fwd_params* p = &q->fwd;
     const size_t al = 4 * (size_t)elem_size(p->io_dtype);
@@ -605,11 +582,11 @@ struct ScanPlan {
     int items = 0, rows = 0, tiles = 1, nb = 0, P = 1, S = 1, seg_tiles = 0, RB = 0, slab2 = 0, flags = 0;
     bool glds = false;
     size_t lds = 0;
-    // workspace layout in floats: [dB partials][dC partials][segment summaries][hand-over area of the chained walk]
+    // workspace layout in floats: [dB partials][dC partials][segment summaries]
     // [per-row partials of the deterministic backward: rpart_K slots of dim x (dstate + 2)]
-    int64_t slab = 0, summ = 0, chain = 0, rpart = 0;
+    int64_t slab = 0, summ = 0, rpart = 0;
     int rpart_K = 0;
-    int64_t workspace_bytes() const { return (2 * slab + summ + chain + rpart) * (int64_t)sizeof(float); }
+    int64_t workspace_bytes() const { return (2 * slab + summ + rpart) * (int64_t)sizeof(float); }
 };
 
 int refuse_rowlane(bool launch) {
@@ -665,7 +642,6 @@ ScanPlan plan_backward(const sigma_scan_bwd_params* q, bool launch) {
         s.family = Family::Bwdr;
         s.rows = r.NW; s.P = r.P; s.S = r.S; s.seg_tiles = r.seg_tiles;
         s.lds = sigma::bwdr_lds_bytes(4);
-        s.chain = rowlane_chain_floats(p);
         s.report = {16, r.NW, r.grid, (int32_t)s.lds, r.S, -200};
     } else if (p->ckpt_pitch == SIGMA_SCAN_CKPT_PITCH_160) {
         // B/C alignment is part of the plan: the caller chose the pitch at forward time with the same tensors
@@ -718,7 +694,6 @@ ScanPlan plan_backward(const sigma_scan_bwd_params* q, bool launch) {
     return s;
 }
 
-// everything of the backward's arguments but the chained walk's tiles (rowlane_chain_tiles, a launch-time decision)
 sigma::BwdArgs make_bwd_args(const sigma_scan_bwd_params* q, const ScanPlan& s) {
     const sigma_scan_fwd_params* p = &q->fwd;
     sigma::BwdArgs a;
@@ -741,12 +716,8 @@ sigma::BwdArgs make_bwd_args(const sigma_scan_bwd_params* q, const ScanPlan& s) 
     a.ws_dB = s.slab ? ws : nullptr;
     a.ws_dC = s.slab ? ws + s.slab : nullptr;
     a.summ = s.summ ? ws + 2 * s.slab : nullptr;
-    if (s.chain) {
-        a.chain_carry = ws + 2 * s.slab + s.summ;
-        a.chain_flag = reinterpret_cast<int*>(a.chain_carry + (int64_t)p->batch * (p->dim / 64) * p->dstate * 64);
-    }
     if (s.rpart) {
-        a.rpart = ws + 2 * s.slab + s.summ + s.chain;
+        a.rpart = ws + 2 * s.slab + s.summ;
         a.rpart_K = s.rpart_K;
     }
     return a;
@@ -795,7 +766,6 @@ OptDesc g_opts[] = {
     {"bwd_rb", &g_opt_bwd_rb, {-3}},                       // scan_bwd2: row blocks per workgroup, 0..256
     {"rl_waves", &g_opt_rl_waves, {0, 4, 8, 16, -1}},       // row-lane kernels: state waves per 64-row block
     {"rl_segs", &g_opt_rl_segs, {-4}},                      // row-lane kernels: sequence segments, 0..64
-    {"rl_chain", &g_opt_rl_chain, {0, 1, 2, -1}},           // row-lane backward: chained walk 1 = never, 2 = whenever legal
 };
 }  // namespace
 
@@ -818,11 +788,6 @@ int sigma_scan_set_option(const char* name, int value) {
 int sigma_scan_get_option(const char* name) {
     if (!name) return -1;
     for (auto& o : g_opts) if (!std::strcmp(name, o.name)) return o.var->load();
-    if (!std::strcmp(name, "rl_chain_timeouts")) {      // read-only: see sigma_scan.h
-        unsigned int n = 0;
-        if (sigma::bwdr_chain_timeouts_read(&n) != hipSuccess) return -1;
-        return (int)(n > 0x7fffffffu ? 0x7fffffffu : n);
-    }
     return -1;
 }
 
@@ -906,15 +871,11 @@ int sigma_selective_scan_bwd(const sigma_scan_bwd_params* q, void* stream) {
     if (s.status) return s.status;
     rc = check_workspace(q->workspace, q->workspace_bytes, s.workspace_bytes(), "");
     if (rc) return rc;
-    sigma::BwdArgs a = make_bwd_args(q, s);
+    const sigma::BwdArgs a = make_bwd_args(q, s);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t e;
     switch (s.family) {
-        case Family::Bwdr:
-            // asks the device for occupancy; the deterministic backward never chains (a cut row block has two writers)
-            a.chain_W = s.rpart ? 0 : rowlane_chain_tiles(p, s.P, s.S);
-            e = sigma::launch_scan_bwdr(a, st);
-            break;
+        case Family::Bwdr: e = sigma::launch_scan_bwdr(a, st); break;
         case Family::Bwd4: e = sigma::launch_scan_bwd4(a, st); break;
         case Family::Bwd3: e = sigma::launch_scan_bwd3(a, p->io_dtype, s.glds, st); break;
         case Family::Bwd2: e = sigma::launch_scan_bwd2(a, p->io_dtype, s.items, s.glds, st); break;

@@ -32,20 +32,20 @@ v_rcp_f32 are 1 ulp = 2 U.  They are counted from the source, not fitted to what
 
   c = 3, per position a contribution travels (the larger of the two ways into x_t):
       the carried part a x:  v_exp_f32 result 2 (scan_fwd.hip:170, scan_fwd4.hip:118, scan_fwdr.hip:194/435,
-      scan_bwd.hip:232, scan_bwd2.hip:214, scan_bwd3.hip:184, scan_bwd4.hip:232, scan_bwdr.hip:352) + the fma 1
+      scan_bwd.hip:232, scan_bwd2.hip:214, scan_bwd3.hip:184, scan_bwd4.hip:232, scan_bwdr.hip:318) + the fma 1
       (scan_fwd.hip:172/205, scan_fwd4.hip:120/134, scan_fwdr.hip:195/436, scan_bwd4.hip:235/245);
       the injected part w:   delta * u 1 (scan_fwd.hip:121, scan_fwd4.hip:87, scan_fwdr.hip:152, scan_bwd4.hip:173)
       + times B 1 (scan_fwd.hip:171, scan_fwd4.hip:119, scan_fwdr.hip:195, scan_bwd4.hip:233) + the fma 1.
       A lane that is skipped by the scan network instead of walked costs v_exp 2 + one product 1 for its T >= 4
       positions (scan_fwd.hip:178, scan_device.h:289-290 SIGMA_MSTEP), which the same 3 per position covers.
-  c_b = 5, the adjoint step e = a (g C + e) (scan_bwd4.hip:250/264-265, scan_bwdr.hip:537): g * C 1
+  c_b = 5, the adjoint step e = a (g C + e) (scan_bwd4.hip:250/264-265, scan_bwdr.hip:491): g * C 1
       (scan_bwd4.hip:234), the add 1, the product 1, v_exp 2.
   k = 2.5 + (T - 1) + levels_log, roundings that land in the exponent, relative to sum |delta A|:
       A * log2(e) 1 and the constant itself 0.5 (scan_bwd4.hip:218; scan_device.h:12), the product with delta or with
       the lane's sum of delta 1 (scan_fwd.hip:170/178), the serial sum of the lane's T deltas T - 1 (scan_fwd.hip:126,
       scan_fwd4.hip:89, scan_bwd4.hip:181, scan_bwd2.hip:220), and where the decay travels as a sum of log2 (the
       wave-split forward, scan_device.h:216-231: 6 adds; the row-lane segment summaries, scan_fwdr.hip:199 and
-      scan_bwdr.hip:547: one fma per tile of the segment, after a 16-term serial sum scan_fwdr.hip:174) those adds.
+      scan_bwdr.hip:501: one fma per tile of the segment, after a 16-term serial sum scan_fwdr.hip:174) those adds.
       T and the segment geometry come from the planner's report.
   c_0 = levels + 2, once per output: the fma of each level of the scan network (scan_device.h:297-308: 6;
       scan_quad.h:81-100: 4; none in the row-lane kernels), the hand-over of the state entering the lane
@@ -71,7 +71,7 @@ v_rcp_f32 are 1 ulp = 2 U.  They are counted from the source, not fitted to what
       (scan_bwd.hip:409-460); P = workgroups / (batch G segments) from the planner's report.
   K_row (dA, dD, ddelta_bias): row_sum_depth of tests/test_deterministic_cpu.py, default and deterministic form; dA
       takes the same road as dD (scan_bwd4.hip:269/279/335, scan_bwd2.hip:270/301, scan_bwd3.hip:218/230,
-      scan_bwdr.hip:444); scan_bwd.hip adds its tiles in LDS first (:279/296/299): T + 6 + tiles + batch.
+      scan_bwdr.hip:398); scan_bwd.hip adds its tiles in LDS first (:279/296/299): T + 6 + tiles + batch.
   16-bit IO: the operands are exact, the arithmetic is fp32, and out / du / ddelta -- through the binding dB / dC too,
       which it returns in the dtype of B / C (selective_scan_cuda_core.py bwd_ext, ``io_bc``); the C ABI writes them in
       fp32 -- are rounded to the IO format: half a unit in the last place of their own format (2^-8 bf16, 2^-11 f16, and

@@ -15,10 +15,12 @@ from sigma_amd import _capi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # (batch, KD, L, N, G, rev_mask, u_gshift, ckpt_pitch, io_dtype, family, workspace bytes WITHOUT the flag: the answers of
-# the tree before deterministic mode existed -- the flag-clear contract must not move)
+# the tree before deterministic mode existed -- the flag-clear contract must not move.  The two row-lane answers are
+# those less the hand-over area of the chained walk, (row blocks * (N * 64 + 1)) floats = 3148800 and 49200 bytes, which
+# left the workspace with the walk in ABI 13: 12 dB + dC slab pairs; 3 slab pairs + the summaries of 40 segments)
 SHAPES = [
-    (16, 3072, 1200, 16, 4, 0b1010, 1, 16, 0, "Bwdr", 121113600),
-    (1, 768, 19200, 16, 4, 0b1010, 1, 16, 0, "Bwdr", 33374256),        # row-lane with sequence segments
+    (16, 3072, 1200, 16, 4, 0b1010, 1, 16, 0, "Bwdr", 117964800),
+    (1, 768, 19200, 16, 4, 0b1010, 1, 16, 0, "Bwdr", 33325056),        # row-lane with sequence segments
     (16, 768, 19200, 16, 4, 0b1010, 1, 160, 0, "Bwd4", 629145600),
     (1, 768, 19200, 16, 4, 0b1010, 1, 160, 0, "Bwd4", 79331328),        # quad-row with sequence segments
     (8, 768, 19200, 4, 4, 0b1010, 1, 640, 0, "Bwd2", 157286400),
@@ -108,9 +110,9 @@ def row_sum_depth(plan, batch, L):
     return lane + levels + batch * S * per_wg, lane + levels + per_wg + batch * S
 
 
-def test_abi_version_12_and_struct_fields(tmp_path):
+def test_abi_version_13_and_struct_fields(tmp_path):
     lib = _capi.load()
-    assert _capi.SIGMA_SCAN_ABI_VERSION == 12 and lib.sigma_scan_abi_version() == 12
+    assert _capi.SIGMA_SCAN_ABI_VERSION == 13 and lib.sigma_scan_abi_version() == 13
     fields = [("sigma_scan_bwd_params", "flags", _capi.BwdParams), ("sigma_dwconv_params", "flags", _capi.DwConvParams),
               ("sigma_dwconv_params", "workspace", _capi.DwConvParams),
               ("sigma_dwconv_params", "workspace_bytes", _capi.DwConvParams)]

@@ -5,6 +5,7 @@ csrc/capi.hip plans grids from "workgroups a CU holds" per kernel build (plan_ro
 row-lane backward, two workgroups per CU of the GEMMs): those numbers are register counts of a particular compiler.  A
 toolchain that allocates more registers -- or starts spilling the hot loops to scratch -- silently turns a plan of whole
 rounds into one with a half-empty tail; this test makes that loud."""
+import itertools
 import os
 import re
 import subprocess
@@ -50,18 +51,18 @@ def _waves_per_simd(r):
 def test_row_lane_backward_fits_the_two_workgroups_its_lds_allows_without_scratch_in_the_tile_loops(tmp_path_factory):
     """Round 6: the whole-tile walk of the 16-state build sits AT the 256 registers two waves per SIMD allow and spills a few
     dozen prologue / epilogue values; what must not happen is scratch traffic INSIDE the tile loops (the loops that issue the
-    LDS-DMA requests) -- checked in the ISA."""
+    LDS-DMA requests) -- checked in the ISA.  MODE 0 is the backward proper, MODE 3 the one deterministic training runs."""
     from tests.test_isa_waits_cpu import _asm, _function, _tile_loops
     rows = _resources("scan_bwdr.hip")
     asm = None
-    for ns in (4, 2, 1):
-        (name, r), = _pick(rows, rf"scan_bwdr_kernel<{ns}, 0>").items()
+    for ns, mode in itertools.product((4, 2, 1), (0, 3)):
+        (name, r), = _pick(rows, rf"scan_bwdr_kernel<{ns}, {mode}>").items()
         # bwdr_lds_bytes(4) = 64 KB -> two 4-wave workgroups per CU = two waves per SIMD (plan_rowlane: {4, 2})
         assert _waves_per_simd(r) >= 2, (name, r)
         if r["ScratchSize [bytes/lane]"] == 0 and r["VGPRs Spill"] == 0:
             continue
         asm = asm or _asm(tmp_path_factory)
-        body = _function(asm, ns, 0)
+        body = _function(asm, ns, mode)
         loops = _tile_loops(body)
         assert loops, name
         for h, b in loops:

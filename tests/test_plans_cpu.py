@@ -103,8 +103,8 @@ def test_dominant_launch_plans_are_the_documented_ones():
 
 def test_row_lane_plans_of_every_model_shape():
     """ckpt_pitch 16 (csrc/scan_fwdr.hip / scan_bwdr.hip): every model shape with rows per group divisible by 64 gets a
-    legal plan -- state waves dividing dstate, segments of >= 2 tiles none of them empty, workspace = slabs + summaries +
-    the hand-over slots of the chained walk -- and the others are refused by BOTH entry points."""
+    legal plan -- state waves dividing dstate, segments of >= 2 tiles none of them empty, workspace = slabs + summaries
+    -- and the others are refused by BOTH entry points."""
     lib = _capi.load()
     seen = 0
     for (dim, N, G), L, batch in itertools.product(MODEL_DIMS, LENGTHS, BATCHES):
@@ -128,10 +128,8 @@ def test_row_lane_plans_of_every_model_shape():
             assert S == 1 or (st >= 2 and st * (S - 1) < ntiles)
             summ = (S - 1) * batch * dim * N * 2 * 4
             if backward:
-                nrb = batch * dim // 64
-                chain = (nrb * N * 64 + (nrb + 3) // 4 * 4) * 4
                 slabs = 0 if P == 1 else 2 * P * batch * G * N * L * 4
-                assert lib.sigma_scan_bwd_workspace_bytes(ctypes.byref(bp)) == slabs + summ + chain
+                assert lib.sigma_scan_bwd_workspace_bytes(ctypes.byref(bp)) == slabs + summ
             else:
                 assert lib.sigma_scan_fwd_workspace_bytes(ctypes.byref(bp.fwd)) == summ
         seen += 1

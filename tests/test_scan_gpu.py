@@ -702,8 +702,8 @@ ROWLANE_CASES = [
     ((1, 256, 4800, 16, 4, 0b1010, 1), {}),                  # few rows: automatic segments
     ((1, 768, 19200, 16, 4, 0b1010, 1), {}),                 # one image per GPU, encoder stage 0 (SURVEY's headline shape)
     ((1, 384, 38400, 4, 2, 0b10, 1), {}),                    # one image per GPU, ConMB stage 0 (the longest sequence at 480x640)
-    ((11, 3072, 176, 16, 4, 0b1010, 1), {"rl_chain": 2}),    # 528 row blocks > resident workgroups: chained walk of the backward
-    ((11, 3072, 172, 16, 4, 0b0101, 1), {"rl_chain": 2}),    # ... with a partial last tile
+    ((11, 3072, 176, 16, 4, 0b1010, 1), {}),                 # 528 row blocks > the 512 resident workgroups of the backward
+    ((11, 3072, 172, 16, 4, 0b0101, 1), {}),                 # ... with a partial last tile
     ((2, 64, 16, 4, 1, 0, 0), {}),                           # exactly one tile
     ((2, 64, 8, 4, 1, 1, 0), {}),                            # less than one tile, reversed
 ]
@@ -760,15 +760,9 @@ def test_row_lane_kernels_against_oracle(case):
     """csrc/scan_fwdr.hip / scan_bwdr.hip (ckpt_pitch 16: a lane is a channel row, B / C as scalar operands, per-tile
     checkpoints, lane-reduce network for dB / dC) against the CPU oracle: forward with and without checkpoints and all
     seven gradients; reversed groups, shared u / dout rows, partial tiles, workspace slabs, state-wave counts, sequence
-    segments (forced and automatic) and the chained walk."""
+    segments (forced and automatic) and more row blocks than the chip holds workgroups."""
     shape, opts = case
     _rowlane_run(shape, opts)
-    if opts.get("rl_chain") == 2:
-        from sigma_amd import _capi
-        # no hand-over wait ran out (bwd_ext raises when one does; the count is read-only and resets on read)
-        assert _capi.get_option("rl_chain_timeouts") == 0
-        with pytest.raises(RuntimeError):
-            _capi.set_option("rl_chain_timeouts", 0)
 
 
 @pytest.mark.parametrize("flags", [dict(softplus=False), dict(with_D=False, with_bias=False), dict(softplus=False, with_D=False)],

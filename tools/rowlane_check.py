@@ -108,9 +108,8 @@ CASES = [
     ((2, 256, 1200, 16, 4, 0b1010, 1), {"rl_waves": 4}),     # forward with 4 state waves
     ((1, 256, 4800, 16, 4, 0b1010, 1), {}),                  # few rows: automatic segments
     ((1, 768, 19200, 16, 4, 0b1010, 1), {}),                 # one image per GPU, encoder stage 0
-    ((11, 3072, 176, 16, 4, 0b1010, 1), {"rl_chain": 2}),    # 528 row blocks > 512 resident workgroups: chained walk
-    ((11, 3072, 172, 16, 4, 0b0101, 1), {"rl_chain": 2}),    # chained walk with a partial last tile
-    ((11, 3072, 176, 16, 4, 0b1010, 1), {"rl_chain": 1}),    # the same without the chain
+    ((11, 3072, 176, 16, 4, 0b1010, 1), {}),                 # 528 row blocks > 512 resident workgroups
+    ((11, 3072, 172, 16, 4, 0b0101, 1), {}),                 # ... with a partial last tile
     ((2, 64, 16, 4, 1, 0, 0), {}),                           # one tile
     ((2, 64, 8, 4, 1, 1, 0), {}),                            # less than one tile, reversed
 ]
