@@ -162,6 +162,21 @@ int sigma_softmax_ce_fwd(const float *logits, const int64_t *labels, int64_t row
                          float *lse, float *partial, void *stream);
 int sigma_softmax_ce_bwd(const float *logits, const int64_t *labels, const float *lse, const float *scale, int64_t rows,
                          int32_t classes, int64_t ignore_index, float *dlogits, void *stream);
+/*   sigma_softmax_ce_fwd_ld / sigma_softmax_ce_bwd_ld (added under ABI 13: two functions, no struct or signature changed)
+ *       The same loss for ANY class count (the reference's MFNet 9, PST900 5, SUN-RGBD 37): row r holds its `classes`
+ *       logits at logits + r * ld, with the pitch ld % 4 == 0, ld >= classes, classes >= 1 and 16-byte aligned pointers --
+ *       the (rows, ld) output of the classifier GEMM against a weight zero-padded to ld rows.  `dlogits` has the same
+ *       pitch.  ld == classes IS sigma_softmax_ce_fwd / _bwd (same kernels, same bits).
+ *           fwd : columns >= classes take no part; they may hold anything (NaN, Inf) and reach neither lse nor partial.
+ *                 lse and the SIGMA_CE_BLOCKS (sum, count) pairs are laid out as above.
+ *           bwd : columns < classes as above; columns [classes, ld) are WRITTEN with exact zeros (chosen by index), so
+ *                 GEMMs may read whole rows of ld.
+ *       A label in [classes, ld) is out of range like any label >= classes: the pixel is ignored.
+ *       Rows of up to 64 classes (16 chunks of 16 bytes) are held in registers, longer ones are walked.               */
+int sigma_softmax_ce_fwd_ld(const float *logits, const int64_t *labels, int64_t rows, int32_t classes, int32_t ld,
+                            int64_t ignore_index, float *lse, float *partial, void *stream);
+int sigma_softmax_ce_bwd_ld(const float *logits, const int64_t *labels, const float *lse, const float *scale, int64_t rows,
+                            int32_t classes, int32_t ld, int64_t ignore_index, float *dlogits, void *stream);
 
 /*   sigma_colscale_bwd
  *       backward of  y = a + x * scale  with a per-channel `scale` on contiguous channels-last rows (rows, C): the residual

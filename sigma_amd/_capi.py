@@ -176,7 +176,8 @@ GEMM_STORES = ("store", "accumulate", "atomic")        # bits 6-7
 OPS_SYMBOLS = ("sigma_dwconv3x3_silu_fwd", "sigma_dwconv3x3_silu_bwd", "sigma_cross_merge_nhwc", "sigma_cross_split_nhwc",
                "sigma_layernorm_fwd", "sigma_layernorm_bwd", "sigma_layernorm_bwd_partial_rows", "sigma_transpose2d",
                "sigma_pair_sum_add", "sigma_upsample2x_nhwc", "sigma_plane_pool", "sigma_plane_scale",
-               "sigma_plane_dot", "sigma_plane_gate_bwd", "sigma_softmax_ce_fwd", "sigma_softmax_ce_bwd", "sigma_colscale_bwd",
+               "sigma_plane_dot", "sigma_plane_gate_bwd", "sigma_softmax_ce_fwd", "sigma_softmax_ce_bwd", "sigma_softmax_ce_fwd_ld",
+               "sigma_softmax_ce_bwd_ld", "sigma_colscale_bwd",
                "sigma_colscale_bwd_ws", "sigma_seg_accumulate", "sigma_seg_argmax_confusion")
 # the size queries include/sigma_ops.h declares (int64_t results)
 OPS_AUX_SYMBOLS = ("sigma_dwconv3x3_silu_bwd_workspace_bytes", "sigma_colscale_bwd_workspace_bytes")
@@ -265,6 +266,12 @@ def load() -> ctypes.CDLL:
         elif name == "sigma_softmax_ce_bwd":
             fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                            ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+        elif name == "sigma_softmax_ce_fwd_ld":
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        elif name == "sigma_softmax_ce_bwd_ld":
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                           ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
         elif name == "sigma_seg_accumulate":
             fn.argtypes = [P(SegAccumulateParams), ctypes.c_void_p]
         elif name == "sigma_seg_argmax_confusion":

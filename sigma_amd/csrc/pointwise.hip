@@ -157,18 +157,31 @@ __global__ void __launch_bounds__(256) plane_gate_bwd_kernel(const GateBwdArgs a
     }
 }
 
-// ---- softmax cross entropy over rows of `nc` contiguous logits (nc % 4 == 0), one thread per row
+// ---- softmax cross entropy over rows of `nc` logits at a pitch of `ld` floats (ld % 4 == 0, ld >= nc), one thread per row
+// PAD = false: nc % 4 == 0 and ld == nc, the contiguous rows of sigma_softmax_ce_fwd / _bwd.  PAD = true (the _ld entry
+// points): only columns < nc count.  The forward reads the last 16-byte chunk that holds a valid column whole and puts
+// -inf over its tail, later chunks are not read; the backward writes exact zeros over [nc, ld), chosen by index (the pad
+// of the input may hold NaN, and the GEMMs that read dlogits take whole rows of ld).
+__device__ __forceinline__ void ce_mask_tail(float4& v, int n, float fill) {      // n in [1, 4] columns of v are valid
+    if (n < 2) v.y = fill;
+    if (n < 3) v.z = fill;
+    if (n < 4) v.w = fill;
+}
+
+template <bool PAD>
 __global__ void __launch_bounds__(256)
-softmax_ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, long rows, int nc, long ignore,
+softmax_ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, long rows, int nc, int ld, long ignore,
                       float* __restrict__ lse, float* __restrict__ partial) {
     __shared__ float sh[4];
     float loss = 0.0f, count = 0.0f;
     const long stride = (long)gridDim.x * blockDim.x;
+    const int pitch = PAD ? ld : nc;
     for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
-        const float* __restrict__ xr = logits + r * nc;
+        const float* __restrict__ xr = logits + r * pitch;
         float m = kNegInf, s = 0.0f;                   // running max and sum of exp(x - m)
         for (int c = 0; c < nc; c += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(xr + c);
+            float4 v = *reinterpret_cast<const float4*>(xr + c);
+            if (PAD) ce_mask_tail(v, nc - c, kNegInf);
             const float vm = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
             if (vm > m) { s *= __expf(m - vm); m = vm; }
             s += (__expf(v.x - m) + __expf(v.y - m)) + (__expf(v.z - m) + __expf(v.w - m));
@@ -183,45 +196,54 @@ softmax_ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restric
     if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = tc; }
 }
 
+template <bool PAD>
 __global__ void __launch_bounds__(256)
 softmax_ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ lse,
-                      const float* __restrict__ scale, long rows, int nc, long ignore, float* __restrict__ dlogits) {
+                      const float* __restrict__ scale, long rows, int nc, int ld, long ignore, float* __restrict__ dlogits) {
     const float sc = scale[0];
     const long stride = (long)gridDim.x * blockDim.x;
+    const int pitch = PAD ? ld : nc;
     for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
-        const float* __restrict__ xr = logits + r * nc;
-        float* __restrict__ dr = dlogits + r * nc;
+        const float* __restrict__ xr = logits + r * pitch;
+        float* __restrict__ dr = dlogits + r * pitch;
         const long y = labels[r];
         const bool on = y != ignore && y >= 0 && y < nc;
         const float l = lse[r];
         const float f = on ? sc : 0.0f;
-        for (int c = 0; c < nc; c += 4) {
+        int c = 0;
+        for (; c < nc; c += 4) {
             const float4 v = *reinterpret_cast<const float4*>(xr + c);
             float4 o;
             o.x = (__expf(v.x - l) - (y == c ? 1.0f : 0.0f)) * f;
             o.y = (__expf(v.y - l) - (y == c + 1 ? 1.0f : 0.0f)) * f;
             o.z = (__expf(v.z - l) - (y == c + 2 ? 1.0f : 0.0f)) * f;
             o.w = (__expf(v.w - l) - (y == c + 3 ? 1.0f : 0.0f)) * f;
+            if (PAD) ce_mask_tail(o, nc - c, 0.0f);
             *reinterpret_cast<float4*>(dr + c) = o;
         }
+        if (PAD)
+            for (; c < ld; c += 4) *reinterpret_cast<float4*>(dr + c) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
 }
 
 // Same kernels with the row (NC4 float4) held in registers: every load of a row is issued before the first use.  The
-// generic kernels above walk the row with one load in flight per thread (1.2 TB/s on 8 x 480 x 640 x 40).
-template <int NC4>
+// generic kernels above walk the row with one load in flight per thread (1.2 TB/s on 8 x 480 x 640 x 40).  PAD = true:
+// NC4 = ceil(nc / 4) chunks hold the valid columns.
+template <int NC4, bool PAD>
 __global__ void __launch_bounds__(256)
-softmax_ce_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, long rows, long ignore,
+softmax_ce_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, long rows, int nc_, int ld, long ignore,
                           float* __restrict__ lse, float* __restrict__ partial) {
     __shared__ float sh[4];
-    constexpr int nc = NC4 * 4;
+    const int nc = PAD ? nc_ : NC4 * 4;
+    const int pitch = PAD ? ld : NC4 * 4;
     float loss = 0.0f, count = 0.0f;
     const long stride = (long)gridDim.x * blockDim.x;
     for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
-        const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * nc);
+        const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * pitch);
         float4 v[NC4];
 #pragma unroll
         for (int c = 0; c < NC4; ++c) v[c] = xr[c];
+        if (PAD) ce_mask_tail(v[NC4 - 1], nc - 4 * (NC4 - 1), kNegInf);
         const long y = labels[r];
         float m = kNegInf;
 #pragma unroll
@@ -241,16 +263,17 @@ softmax_ce_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* __res
     if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = tc; }
 }
 
-template <int NC4>
+template <int NC4, bool PAD>
 __global__ void __launch_bounds__(256)
 softmax_ce_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ lse,
-                          const float* __restrict__ scale, long rows, long ignore, float* __restrict__ dlogits) {
-    constexpr int nc = NC4 * 4;
+                          const float* __restrict__ scale, long rows, int nc_, int ld, long ignore, float* __restrict__ dlogits) {
+    const int nc = PAD ? nc_ : NC4 * 4;
+    const int pitch = PAD ? ld : NC4 * 4;
     const float sc = scale[0];
     const long stride = (long)gridDim.x * blockDim.x;
     for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
-        const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * nc);
-        float4* __restrict__ dr = reinterpret_cast<float4*>(dlogits + r * nc);
+        const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * pitch);
+        float4* __restrict__ dr = reinterpret_cast<float4*>(dlogits + r * pitch);
         float4 v[NC4];
 #pragma unroll
         for (int c = 0; c < NC4; ++c) v[c] = xr[c];
@@ -264,12 +287,15 @@ softmax_ce_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* __res
             o.y = (__expf(v[c].y - l) - (y == 4 * c + 1 ? 1.0f : 0.0f)) * f;
             o.z = (__expf(v[c].z - l) - (y == 4 * c + 2 ? 1.0f : 0.0f)) * f;
             o.w = (__expf(v[c].w - l) - (y == 4 * c + 3 ? 1.0f : 0.0f)) * f;
+            if (PAD && c == NC4 - 1) ce_mask_tail(o, nc - 4 * (NC4 - 1), 0.0f);
             dr[c] = o;
         }
+        if (PAD)
+            for (int c = NC4; c < (ld >> 2); ++c) dr[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
 }
 
-// NC4 = classes / 4 held in registers up to 64 classes
+// NC4 = ceil(classes / 4) chunks held in registers up to 64 classes
 template <typename F>
 bool dispatch_nc4(int nc4, F&& f) {
     switch (nc4) {
@@ -453,34 +479,59 @@ int sigma_plane_gate_bwd(const sigma_gate_bwd_params* p, void* stream) {
 
 int sigma_softmax_ce_fwd(const float* logits, const int64_t* labels, int64_t rows, int32_t classes, int64_t ignore_index, float* lse,
                          float* partial, void* stream) {
-    if (rows < 0 || classes <= 0 || classes % 4 != 0) return SIGMA_OPS_ERR_ARG;
-    if (!partial) return SIGMA_OPS_ERR_ARG;
-    if (rows > 0 && (!logits || !labels || !lse || !sigma::al16(logits))) return SIGMA_OPS_ERR_ARG;
-    // every one of the SIGMA_CE_BLOCKS workgroups writes its (sum, count) pair, rows or not: the caller adds them up
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool reg = sigma::dispatch_nc4(classes / 4, [&](auto n) {
-        hipLaunchKernelGGL(sigma::softmax_ce_fwd_reg_kernel<decltype(n)::value>, dim3(SIGMA_CE_BLOCKS), dim3(256), 0, s, logits, labels,
-                           (long)rows, (long)ignore_index, lse, partial);
-    });
-    if (!reg)
-        hipLaunchKernelGGL(sigma::softmax_ce_fwd_kernel, dim3(SIGMA_CE_BLOCKS), dim3(256), 0, s, logits, labels, (long)rows, (int)classes,
-                           (long)ignore_index, lse, partial);
-    return sigma::done();
+    if (classes <= 0 || classes % 4 != 0) return SIGMA_OPS_ERR_ARG;
+    return sigma_softmax_ce_fwd_ld(logits, labels, rows, classes, classes, ignore_index, lse, partial, stream);
 }
 
 int sigma_softmax_ce_bwd(const float* logits, const int64_t* labels, const float* lse, const float* scale, int64_t rows, int32_t classes,
                          int64_t ignore_index, float* dlogits, void* stream) {
-    if (rows < 0 || classes <= 0 || classes % 4 != 0) return SIGMA_OPS_ERR_ARG;
+    if (classes <= 0 || classes % 4 != 0) return SIGMA_OPS_ERR_ARG;
+    return sigma_softmax_ce_bwd_ld(logits, labels, lse, scale, rows, classes, classes, ignore_index, dlogits, stream);
+}
+
+// ld == classes: the PAD = false kernels, i.e. what sigma_softmax_ce_fwd / _bwd have always launched
+int sigma_softmax_ce_fwd_ld(const float* logits, const int64_t* labels, int64_t rows, int32_t classes, int32_t ld, int64_t ignore_index,
+                            float* lse, float* partial, void* stream) {
+    if (rows < 0 || classes < 1 || ld % 4 != 0 || ld < classes) return SIGMA_OPS_ERR_ARG;
+    if (!partial) return SIGMA_OPS_ERR_ARG;
+    if (rows > 0 && (!logits || !labels || !lse || !sigma::al16(logits))) return SIGMA_OPS_ERR_ARG;
+    // every one of the SIGMA_CE_BLOCKS workgroups writes its (sum, count) pair, rows or not: the caller adds them up
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid(SIGMA_CE_BLOCKS), block(256);
+    const long nrows = (long)rows, ignore = (long)ignore_index;
+    const int nc = (int)classes, pitch = (int)ld;
+    const bool pad = ld != classes;
+    const bool reg = sigma::dispatch_nc4((classes + 3) / 4, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        if (pad) hipLaunchKernelGGL((sigma::softmax_ce_fwd_reg_kernel<N, true>), grid, block, 0, s, logits, labels, nrows, nc, pitch, ignore, lse, partial);
+        else hipLaunchKernelGGL((sigma::softmax_ce_fwd_reg_kernel<N, false>), grid, block, 0, s, logits, labels, nrows, nc, pitch, ignore, lse, partial);
+    });
+    if (!reg) {
+        if (pad) hipLaunchKernelGGL(sigma::softmax_ce_fwd_kernel<true>, grid, block, 0, s, logits, labels, nrows, nc, pitch, ignore, lse, partial);
+        else hipLaunchKernelGGL(sigma::softmax_ce_fwd_kernel<false>, grid, block, 0, s, logits, labels, nrows, nc, pitch, ignore, lse, partial);
+    }
+    return sigma::done();
+}
+
+int sigma_softmax_ce_bwd_ld(const float* logits, const int64_t* labels, const float* lse, const float* scale, int64_t rows, int32_t classes,
+                            int32_t ld, int64_t ignore_index, float* dlogits, void* stream) {
+    if (rows < 0 || classes < 1 || ld % 4 != 0 || ld < classes) return SIGMA_OPS_ERR_ARG;
     if (rows == 0) return SIGMA_OPS_OK;
     if (!logits || !labels || !lse || !scale || !dlogits || !sigma::al16(logits) || !sigma::al16(dlogits)) return SIGMA_OPS_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool reg = sigma::dispatch_nc4(classes / 4, [&](auto n) {
-        hipLaunchKernelGGL(sigma::softmax_ce_bwd_reg_kernel<decltype(n)::value>, dim3(sigma::stream_grid(rows)), dim3(256), 0, s, logits,
-                           labels, lse, scale, (long)rows, (long)ignore_index, dlogits);
+    const dim3 grid(sigma::stream_grid(rows)), block(256);
+    const long nrows = (long)rows, ignore = (long)ignore_index;
+    const int nc = (int)classes, pitch = (int)ld;
+    const bool pad = ld != classes;
+    const bool reg = sigma::dispatch_nc4((classes + 3) / 4, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        if (pad) hipLaunchKernelGGL((sigma::softmax_ce_bwd_reg_kernel<N, true>), grid, block, 0, s, logits, labels, lse, scale, nrows, nc, pitch, ignore, dlogits);
+        else hipLaunchKernelGGL((sigma::softmax_ce_bwd_reg_kernel<N, false>), grid, block, 0, s, logits, labels, lse, scale, nrows, nc, pitch, ignore, dlogits);
     });
-    if (!reg)
-        hipLaunchKernelGGL(sigma::softmax_ce_bwd_kernel, dim3(sigma::stream_grid(rows)), dim3(256), 0, s, logits, labels, lse, scale,
-                           (long)rows, (int)classes, (long)ignore_index, dlogits);
+    if (!reg) {
+        if (pad) hipLaunchKernelGGL(sigma::softmax_ce_bwd_kernel<true>, grid, block, 0, s, logits, labels, lse, scale, nrows, nc, pitch, ignore, dlogits);
+        else hipLaunchKernelGGL(sigma::softmax_ce_bwd_kernel<false>, grid, block, 0, s, logits, labels, lse, scale, nrows, nc, pitch, ignore, dlogits);
+    }
     return sigma::done();
 }
 

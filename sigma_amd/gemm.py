@@ -357,6 +357,71 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias=None, residual=None) -> t
     return y2.view(*x.shape[:-1], weight.shape[0])
 
 
+def padded_classes(nc: int) -> int:
+    """row pitch of the logits of an nc-class head: the next multiple of 4 (16-byte rows for the GEMM and loss kernels)"""
+    return (nc + 3) // 4 * 4
+
+
+def pad_rows(weight2: torch.Tensor, ld: int) -> torch.Tensor:
+    """(nc, C) -> (ld, C): the classifier weight followed by ld - nc rows of exact zeros (a new tensor, never a parameter)"""
+    return nn.functional.pad(weight2, (0, 0, 0, ld - weight2.shape[0]))
+
+
+def unpad_rows(dw_pad: torch.Tensor, shape) -> torch.Tensor:
+    """gradient of a parameter of `shape` (nc, C[, 1, 1]) from the (ld, C) gradient of its padded form: the first nc rows,
+    contiguous and in the parameter's shape (the strides DistributedDataParallel's buckets expect)"""
+    return dw_pad[:shape[0]].contiguous().view(shape)
+
+
+def classifier_ok(x2: torch.Tensor, weight: torch.Tensor) -> bool:
+    """an nc-class head with nc % 4 != 0 on the two-piece-or-better kernels in all three GEMMs"""
+    w2 = weight.reshape(weight.shape[0], -1)
+    return bool(_FWD and _DGRAD and _WGRAD and weight.shape[0] % 4 != 0 and x2.is_cuda and x2.dtype == torch.float32
+                and weight.dtype == torch.float32 and x2.dim() == 2 and x2.shape[0] > 0 and nt_ok(x2, w2))
+
+
+class ClassifierPadFn(torch.autograd.Function):
+    """F.linear(x2, weight) for a bias-free head whose class count nc is not a multiple of 4 (MFNet 9, PST900 5, SUN-RGBD 37).
+    The logits are the first nc columns of an (M, ld) buffer, ld = padded_classes(nc): one ``gemm_nt`` against the weight
+    zero-padded to ld rows (row epilogue; the pad columns come out as exact zeros).  Backward on the same kernels with
+    K = ld (``gemm_nn``) and N = ld (``gemm_tn``) instead of torch.mm on rows of nc floats.  The loss backward
+    (pointwise.SoftmaxCEFn) writes its gradient at the same pitch with a zeroed pad and hands the buffer over
+    (_handoff.py); a gradient from anywhere else is copied into a zero-padded buffer.  The logits are a view made inside
+    this Function (a slice taken outside would zero-fill and copy the gradient in backward): autograd refuses in-place
+    operations on them, and nothing in the model applies one."""
+
+    @staticmethod
+    def forward(ctx, x2, weight):
+        nc = weight.shape[0]
+        wp = pad_rows(weight.reshape(nc, -1), padded_classes(nc))
+        y = gemm_nt(x2, wp, pieces=_FWD)
+        ctx.save_for_backward(x2, wp)
+        ctx.weight_shape = weight.shape
+        return y[:, :nc]
+
+    @staticmethod
+    def backward(ctx, dy):
+        from ._handoff import claim_padded_grad_buffer
+        x2, wp = ctx.saved_tensors
+        ld, nc = wp.shape[0], ctx.weight_shape[0]
+        g2 = claim_padded_grad_buffer(dy, ld)
+        if g2 is None:
+            g2 = nn.functional.pad(dy, (0, ld - nc))           # zeros behind every row: the GEMMs read whole rows of ld
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = gemm_nn(g2, wp, pieces=_DGRAD)
+        if ctx.needs_input_grad[1]:
+            dw = unpad_rows(gemm_tn(g2, x2, pieces=_WGRAD), ctx.weight_shape)
+        return dx, dw
+
+
+def classifier(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """logits (..., nc) of a bias-free head, weight (nc, C) or the (nc, C, 1, 1) parameter of a 1x1 convolution, for nc % 4 != 0:
+    a VIEW of the first nc columns of a (..., padded_classes(nc)) buffer.  Callers check ``classifier_ok`` first."""
+    y2 = ClassifierPadFn.apply(x.reshape(-1, x.shape[-1]), weight)
+    return y2.view(*x.shape[:-1], weight.shape[0])
+
+
 def xz_ok(x2: torch.Tensor, weight: torch.Tensor) -> bool:
     """the in_proj GEMM with a transposed x half: (M, C) @ (2d, C)^T with d % 32 == 0, M % 4 == 0, two bf16 pieces forward"""
     return (_FWD == 2 and x2.is_cuda and x2.dtype == torch.float32 and weight.dtype == torch.float32 and x2.dim() == 2

@@ -179,7 +179,11 @@ class MambaDecoder(nn.Module):
             # and a weight gradient with the strides of a (nc, C, 1, 1) view that DistributedDataParallel has to re-lay
             # (the "Grad strides do not match bucket view strides" warning of round 2).  The logits come back as a
             # (B, nc, 4H, 4W) VIEW of the channels-last result.
-            from ...gemm import gemm_mode, linear
+            from ...gemm import classifier, classifier_ok, gemm_mode, linear
+            if gemm_mode() == "split3" and classifier_ok(x.reshape(-1, x.shape[-1]), self.output.weight):
+                # a class count that is no multiple of 4 (MFNet 9, PST900 5, SUN-RGBD 37): logits at a row pitch of
+                # 4 ceil(nc / 4) floats, so the classifier's three GEMMs and the loss stay on the project's kernels
+                return classifier(x, self.output.weight).permute(0, 3, 1, 2)
             w2 = self.output.weight.view(self.output.weight.shape[0], -1)
             y = linear(x, w2) if gemm_mode() == "split3" else F.linear(x, w2)
             return y.permute(0, 3, 1, 2)

@@ -19,6 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _capi
+from ._handoff import offer_padded_grad_buffer
 
 
 def _stream():
@@ -149,20 +150,26 @@ def scale_residual(a: torch.Tensor, x: torch.Tensor, scale: torch.Tensor) -> tor
 
 
 class SoftmaxCEFn(torch.autograd.Function):
-    """mean over the non-ignored pixels of -log softmax(logits)[label]; logits (rows, classes) contiguous"""
+    """mean over the non-ignored pixels of -log softmax(logits)[label]; logits2 (rows, classes) with contiguous rows at a
+    pitch of `ld` floats: the class count itself (sigma_softmax_ce_fwd / _bwd), or a multiple of 4 above it
+    (the padded buffer of gemm.ClassifierPadFn; sigma_softmax_ce_fwd_ld / _bwd_ld, the pad is never read)"""
 
     @staticmethod
-    def forward(ctx, logits2, labels, ignore_index):
+    def forward(ctx, logits2, labels, ignore_index, ld):
         lib = _capi.load()
         rows, nc = logits2.shape
         lse = torch.empty(rows, device=logits2.device, dtype=torch.float32)
         partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=logits2.device, dtype=torch.float32)
         with torch.cuda.device(logits2.device):
-            _capi.check(lib.sigma_softmax_ce_fwd(_p(logits2), _p(labels), rows, nc, int(ignore_index), _p(lse), _p(partial), _stream()),
-                        "softmax_ce_fwd")
+            if ld == nc:
+                _capi.check(lib.sigma_softmax_ce_fwd(_p(logits2), _p(labels), rows, nc, int(ignore_index), _p(lse), _p(partial), _stream()),
+                            "softmax_ce_fwd")
+            else:
+                _capi.check(lib.sigma_softmax_ce_fwd_ld(_p(logits2), _p(labels), rows, nc, ld, int(ignore_index), _p(lse), _p(partial),
+                                                        _stream()), "softmax_ce_fwd_ld")
         tot = partial.sum(0)
         ctx.save_for_backward(logits2, labels, lse, tot)
-        ctx.ignore_index = int(ignore_index)
+        ctx.ignore_index, ctx.ld = int(ignore_index), ld
         return tot[0] / tot[1]
 
     @staticmethod
@@ -170,17 +177,41 @@ class SoftmaxCEFn(torch.autograd.Function):
         lib = _capi.load()
         logits2, labels, lse, tot = ctx.saved_tensors
         rows, nc = logits2.shape
+        ld = ctx.ld
         scale = (g.float() / tot[1]).reshape(1).contiguous()
-        dl = torch.empty_like(logits2)
+        if ld == nc:
+            dl = torch.empty_like(logits2)
+            with torch.cuda.device(logits2.device):
+                _capi.check(lib.sigma_softmax_ce_bwd(_p(logits2), _p(labels), _p(lse), _p(scale), rows, nc, ctx.ignore_index, _p(dl), _stream()),
+                            "softmax_ce_bwd")
+            return dl, None, None, None
+        # the gradient at the logits' pitch, pad columns written with zeros: the classifier's backward claims the whole
+        # buffer for its GEMMs (_handoff.py) -- no zero fill, no re-laying copy
+        full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
         with torch.cuda.device(logits2.device):
-            _capi.check(lib.sigma_softmax_ce_bwd(_p(logits2), _p(labels), _p(lse), _p(scale), rows, nc, ctx.ignore_index, _p(dl), _stream()),
-                        "softmax_ce_bwd")
-        return dl, None, None
+            _capi.check(lib.sigma_softmax_ce_bwd_ld(_p(logits2), _p(labels), _p(lse), _p(scale), rows, nc, ld, ctx.ignore_index, _p(full),
+                                                    _stream()), "softmax_ce_bwd_ld")
+        offer_padded_grad_buffer(full)
+        return full[:, :nc], None, None, None
+
+
+def _row_pitch(nhwc: torch.Tensor):
+    """the pitch ld (floats) if `nhwc` (B, H, W, nc) is B*H*W rows of nc contiguous floats ld apart, else None"""
+    B, H, W, nc = nhwc.shape
+    sb, sh, sw, sc = nhwc.stride()
+    if nhwc.numel() == 0 or (nc > 1 and sc != 1):
+        return None
+    ld = sw if W > 1 else sh if H > 1 else sb if B > 1 else (nc + 3) // 4 * 4
+    if (W > 1 and sw != ld) or (H > 1 and sh != W * ld) or (B > 1 and sb != H * W * ld):
+        return None
+    return ld
 
 
 def cross_entropy(criterion, logits: torch.Tensor, label: torch.Tensor):
     """criterion(logits, label) for a plain mean-reduced nn.CrossEntropyLoss on channels-last logits -- logits is the
-    (B, classes, H, W) VIEW of a contiguous (B, H, W, classes) tensor -- or None when this path does not apply.
+    (B, classes, H, W) VIEW of a contiguous (B, H, W, classes) tensor with classes % 4 == 0, or of the first `classes`
+    columns of a (B, H, W, ld) buffer with ld % 4 == 0 (any class count: the padded classifier output of
+    MambaDecoder.up_x4) -- or None when this path does not apply.
     Labels outside [0, classes) that are not ``ignore_index`` are treated as ignored (csrc/pointwise.hip), where
     torch's kernel device-asserts: the reference's datasets map every unlabeled pixel to 255 = ignore_index
     (dataloader/RGBXDataset.py), so such labels do not occur on this path."""
@@ -191,10 +222,13 @@ def cross_entropy(criterion, logits: torch.Tensor, label: torch.Tensor):
         return None
     nhwc = logits.permute(0, 2, 3, 1)
     nc = nhwc.shape[-1]
-    if not nhwc.is_contiguous() or nc % 4 != 0 or nhwc.data_ptr() % 16 != 0 or tuple(label.shape) != tuple(nhwc.shape[:3]):
+    if nhwc.data_ptr() % 16 != 0 or tuple(label.shape) != tuple(nhwc.shape[:3]):
+        return None
+    ld = nc if nhwc.is_contiguous() else _row_pitch(nhwc)
+    if ld is None or ld % 4 != 0 or ld < nc:
         return None
     lab = label.long().contiguous()
-    return SoftmaxCEFn.apply(nhwc.reshape(-1, nc), lab.view(-1), criterion.ignore_index)
+    return SoftmaxCEFn.apply(nhwc.reshape(-1, nc), lab.view(-1), criterion.ignore_index, ld)      # reshape: a view at either pitch
 
 
 def cross_entropy_deterministic(criterion, logits: torch.Tensor, label: torch.Tensor):
