@@ -178,8 +178,45 @@ int sigma_softmax_ce_fwd_ld(const float *logits, const int64_t *labels, int64_t 
 int sigma_softmax_ce_bwd_ld(const float *logits, const int64_t *labels, const float *lse, const float *scale, int64_t rows,
                             int32_t classes, int32_t ld, int64_t ignore_index, float *dlogits, void *stream);
 
+/*   sigma_softmax_ce_opt_fwd / sigma_softmax_ce_opt_bwd (added under ABI 13: two functions and their own struct, no existing
+ *   struct or signature changed -- the version counts changes to what a caller built against an older header relies on)
+ *       Every option of nn.CrossEntropyLoss on the same rows: class weights w (all ones when NULL), label smoothing eps,
+ *       reduction 'mean' / 'sum' / 'none', ignore_index.  With W = sum_c w_c, p = softmax(logits[r]), y = labels[r] and
+ *       "valid" as above (y != ignore_index and 0 <= y < classes):
+ *           fwd : lse[r] as above;
+ *                 row_loss[r] = (1 - eps) w_y (lse - x_y) + (eps / classes) sum_c w_c (lse - x_c)  for valid rows, 0 otherwise
+ *                 (written when row_loss != NULL: reduction 'none');
+ *                 partial[2k], partial[2k+1] = (sum of row_loss, sum of w_y) over the valid rows of workgroup k <
+ *                 SIGMA_CE_BLOCKS, in the fixed order of the plain kernels.  'sum' = sum of partial[2k]; 'mean' = that over
+ *                 the sum of partial[2k+1] (the pixel count when there is no weight).
+ *           bwd : dlogits[r][c] = g_r [ (1 - eps) w_y (p_c - [c == y]) + (eps / classes) (W p_c - w_c) ]  for valid rows,
+ *                 exact zeros otherwise and in columns [classes, ld).  g_r = scale[0], a DEVICE scalar (upstream / sum of
+ *                 w_y for 'mean', upstream for 'sum'), or row_grad[r] ('none'): exactly one of the two is non-NULL.
+ *       Pitch, padding, alignment and the two regimes (row in registers up to 64 classes) are those of the _ld entry
+ *       points; the weight is read through the caches (4-byte aligned, `classes` floats), it gets no gradient.
+ *       SIGMA_OPS_ERR_ARG before any launch: classes < 1, ld % 4 != 0, ld < classes, rows < 0, label_smoothing outside
+ *       [0, 1], a misaligned pointer, a missing required pointer, both or neither of scale and row_grad.              */
+typedef struct sigma_ce_opt_params {
+    int64_t rows;
+    int32_t classes, ld;           /* ld % 4 == 0, ld >= classes >= 1                                      */
+    int64_t ignore_index;
+    float label_smoothing;         /* eps in [0, 1]                                                        */
+    int32_t reserved_;
+    const float *logits;           /* row r at logits + r * ld, 16-byte aligned                            */
+    const int64_t *labels;         /* (rows)                                                               */
+    const float *weight;           /* (classes) or NULL = all ones                                         */
+    float *lse;                    /* (rows): fwd out, bwd in                                              */
+    float *row_loss;               /* fwd out (rows), or NULL                                              */
+    float *partial;                /* fwd out: SIGMA_CE_BLOCKS pairs (sum of row_loss, sum of w_y)         */
+    const float *scale;            /* bwd in: device scalar g, or NULL                                     */
+    const float *row_grad;         /* bwd in: (rows) g_r, or NULL                                          */
+    float *dlogits;                /* bwd out: pitch ld, 16-byte aligned, fully written                    */
+} sigma_ce_opt_params;
+int sigma_softmax_ce_opt_fwd(const sigma_ce_opt_params *params, void *stream);
+int sigma_softmax_ce_opt_bwd(const sigma_ce_opt_params *params, void *stream);
+
 /*   sigma_colscale_bwd
- *       backward of  y = a + x * scale  with a per-channel `scale` on contiguous channels-last rows (rows, C): the residual
+ *       backward of  y = a + x * scale with a per-channel `scale` on contiguous channels-last rows (rows, C): the residual
  *       of the decoder block, x * scale1 + op(norm1(x)) and x * scale2 + conv_blk(norm2(x)) (vmamba.py:1800-1805):
  *           dx[r][c] = dy[r][c] * scale[c]          dscale[c] += sum_r dy[r][c] * x[r][c]
  *       in one pass over dy and x (the autograd formulation: two multiplies and a column reduction).  `dscale` is

@@ -161,6 +161,17 @@ class SegConfusionParams(ctypes.Structure):
     ]
 
 
+class CeOptParams(ctypes.Structure):
+    """mirror of sigma_ce_opt_params (include/sigma_ops.h)"""
+    _fields_ = [
+        ("rows", ctypes.c_int64), ("classes", ctypes.c_int32), ("ld", ctypes.c_int32), ("ignore_index", ctypes.c_int64),
+        ("label_smoothing", ctypes.c_float), ("reserved_", ctypes.c_int32),
+        ("logits", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("weight", ctypes.c_void_p),
+        ("lse", ctypes.c_void_p), ("row_loss", ctypes.c_void_p), ("partial", ctypes.c_void_p),
+        ("scale", ctypes.c_void_p), ("row_grad", ctypes.c_void_p), ("dlogits", ctypes.c_void_p),
+    ]
+
+
 SIGMA_CE_BLOCKS = 1024      # include/sigma_ops.h
 SIGMA_SEG_LDS_HIST_BYTES = 32768    # include/sigma_ops.h
 
@@ -177,7 +188,7 @@ OPS_SYMBOLS = ("sigma_dwconv3x3_silu_fwd", "sigma_dwconv3x3_silu_bwd", "sigma_cr
                "sigma_layernorm_fwd", "sigma_layernorm_bwd", "sigma_layernorm_bwd_partial_rows", "sigma_transpose2d",
                "sigma_pair_sum_add", "sigma_upsample2x_nhwc", "sigma_plane_pool", "sigma_plane_scale",
                "sigma_plane_dot", "sigma_plane_gate_bwd", "sigma_softmax_ce_fwd", "sigma_softmax_ce_bwd", "sigma_softmax_ce_fwd_ld",
-               "sigma_softmax_ce_bwd_ld", "sigma_colscale_bwd",
+               "sigma_softmax_ce_bwd_ld", "sigma_softmax_ce_opt_fwd", "sigma_softmax_ce_opt_bwd", "sigma_colscale_bwd",
                "sigma_colscale_bwd_ws", "sigma_seg_accumulate", "sigma_seg_argmax_confusion")
 # the size queries include/sigma_ops.h declares (int64_t results)
 OPS_AUX_SYMBOLS = ("sigma_dwconv3x3_silu_bwd_workspace_bytes", "sigma_colscale_bwd_workspace_bytes")
@@ -272,6 +283,8 @@ def load() -> ctypes.CDLL:
         elif name == "sigma_softmax_ce_bwd_ld":
             fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                            ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+        elif name in ("sigma_softmax_ce_opt_fwd", "sigma_softmax_ce_opt_bwd"):
+            fn.argtypes = [P(CeOptParams), ctypes.c_void_p]
         elif name == "sigma_seg_accumulate":
             fn.argtypes = [P(SegAccumulateParams), ctypes.c_void_p]
         elif name == "sigma_seg_argmax_confusion":

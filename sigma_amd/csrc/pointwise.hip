@@ -15,6 +15,8 @@
 //   softmax_ce_fwd  per pixel (a row of `classes` contiguous logits): log-sum-exp (kept for the backward) and
 //                   lse - logit[label]; per-workgroup partial (sum, count) in a fixed layout -> deterministic mean
 //   softmax_ce_bwd  dlogit = (exp(logit - lse) - [class == label]) * scale, zero rows for ignored pixels
+//   softmax_ce_opt_fwd / _bwd  the same two passes with class weights, label smoothing, a per-row loss ('none') and a
+//                   per-row upstream gradient: every option of nn.CrossEntropyLoss
 //
 // All of them are bound by HBM: bytes per element 4 (pool), 8 (scale, dot), 12 (gate_bwd), 4 / 8 (loss fwd / bwd).
 #include <hip/hip_runtime.h>
@@ -308,6 +310,205 @@ bool dispatch_nc4(int nc4, F&& f) {
 }
 
 bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+// ---- the same loss with the options of nn.CrossEntropyLoss: class weights w, label smoothing eps, a per-row loss and a
+// per-row upstream gradient (sigma_softmax_ce_opt_fwd / _bwd).  Kernels of their own: the four above keep their code.
+//   row_loss = (1 - eps) w_y (lse - x_y) + (eps / C) (W lse - sum_c w_c x_c),   W = sum_c w_c
+//   dlogit_c = g [ (1 - eps) w_y (p_c - [c == y]) + (eps / C) (W p_c - w_c) ]
+//            = (g ((1 - eps) w_y + (eps / C) W)) p_c - [c == y] g (1 - eps) w_y - (g eps / C) w_c
+// Same two regimes, same PAD rules.  w is read through the caches, not staged in LDS: w[c] in the unrolled loops has a
+// wave-uniform index (scalar loads, hoisted out of the row loop where the registers allow), w[y] is one gather per row
+// from a table of at most a few cache lines.  HAS_W = false: w = 1, W = C, no load.
+template <bool HAS_W>
+__device__ __forceinline__ float ce_w(const float* __restrict__ w, int c) { return HAS_W ? w[c] : 1.0f; }
+
+template <bool HAS_W>
+__device__ __forceinline__ float ce_weight_sum(const float* __restrict__ w, int nc) {
+    if (!HAS_W) return (float)nc;
+    float W = 0.0f;
+    for (int c = 0; c < nc; ++c) W += w[c];            // one fixed order for the forward and the backward
+    return W;
+}
+
+// sum of w_c x_c over the n in [1, 4] valid columns of the chunk that starts at column c0 (columns past n are not touched:
+// the pad may hold NaN and w ends at nc)
+template <bool HAS_W>
+__device__ __forceinline__ float ce_wx_chunk(const float* __restrict__ w, int c0, const float4& v, int n) {
+    if (n >= 4) return (ce_w<HAS_W>(w, c0) * v.x + ce_w<HAS_W>(w, c0 + 1) * v.y) + (ce_w<HAS_W>(w, c0 + 2) * v.z + ce_w<HAS_W>(w, c0 + 3) * v.w);
+    float t = ce_w<HAS_W>(w, c0) * v.x;
+    if (n > 1) t += ce_w<HAS_W>(w, c0 + 1) * v.y;
+    if (n > 2) t += ce_w<HAS_W>(w, c0 + 2) * v.z;
+    return t;
+}
+
+// the gradient of one chunk; n as above: w is not read past it (what lands in columns >= n is overwritten by the caller)
+template <bool HAS_W>
+__device__ __forceinline__ float4 ce_opt_grad_chunk(const float* __restrict__ w, int c0, const float4& v, int n, float l, long y,
+                                                    float fp, float fa, float fb) {
+    float4 o;
+    o.x = fp * __expf(v.x - l) - (y == c0 ? fa : 0.0f) - fb * ce_w<HAS_W>(w, c0);
+    o.y = fp * __expf(v.y - l) - (y == c0 + 1 ? fa : 0.0f) - fb * (n > 1 ? ce_w<HAS_W>(w, c0 + 1) : 0.0f);
+    o.z = fp * __expf(v.z - l) - (y == c0 + 2 ? fa : 0.0f) - fb * (n > 2 ? ce_w<HAS_W>(w, c0 + 2) : 0.0f);
+    o.w = fp * __expf(v.w - l) - (y == c0 + 3 ? fa : 0.0f) - fb * (n > 3 ? ce_w<HAS_W>(w, c0 + 3) : 0.0f);
+    return o;
+}
+
+__device__ __forceinline__ float ce_opt_row_loss(float eps, float inv_c, float wy, float W, float l, float xy, float sx) {
+    float rl = ((1.0f - eps) * wy) * (l - xy);
+    if (eps > 0.0f) rl += (eps * inv_c) * (W * l - sx);
+    return rl;
+}
+
+template <bool PAD, bool HAS_W>
+__global__ void __launch_bounds__(256)
+softmax_ce_opt_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w, long rows,
+                          int nc, int ld, long ignore, float eps, float* __restrict__ lse, float* __restrict__ row_loss,
+                          float* __restrict__ partial) {
+    __shared__ float sh[4];
+    float loss = 0.0f, den = 0.0f;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const int pitch = PAD ? ld : nc;
+    const float W = ce_weight_sum<HAS_W>(w, nc), inv_c = 1.0f / (float)nc;
+    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
+        const float* __restrict__ xr = logits + r * pitch;
+        float m = kNegInf, s = 0.0f, sx = 0.0f;
+        for (int c = 0; c < nc; c += 4) {
+            float4 v = *reinterpret_cast<const float4*>(xr + c);
+            if (eps > 0.0f) sx += ce_wx_chunk<HAS_W>(w, c, v, PAD ? nc - c : 4);
+            if (PAD) ce_mask_tail(v, nc - c, kNegInf);
+            const float vm = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+            if (vm > m) { s *= __expf(m - vm); m = vm; }
+            s += (__expf(v.x - m) + __expf(v.y - m)) + (__expf(v.z - m) + __expf(v.w - m));
+        }
+        const float l = m + __logf(s);
+        lse[r] = l;
+        const long y = labels[r];
+        float rl = 0.0f;
+        if (y != ignore && y >= 0 && y < nc) {
+            const float wy = ce_w<HAS_W>(w, (int)y);
+            rl = ce_opt_row_loss(eps, inv_c, wy, W, l, xr[y], sx);
+            loss += rl;
+            den += wy;
+        }
+        if (row_loss) row_loss[r] = rl;
+    }
+    const float tl = block_sum(loss, sh);
+    const float td = block_sum(den, sh);
+    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = td; }
+}
+
+template <bool PAD, bool HAS_W>
+__global__ void __launch_bounds__(256)
+softmax_ce_opt_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w,
+                          const float* __restrict__ lse, const float* __restrict__ scale, const float* __restrict__ row_grad, long rows,
+                          int nc, int ld, long ignore, float eps, float* __restrict__ dlogits) {
+    const float sc = scale ? scale[0] : 0.0f;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const int pitch = PAD ? ld : nc;
+    const float W = ce_weight_sum<HAS_W>(w, nc), b = eps * (1.0f / (float)nc);
+    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
+        const float* __restrict__ xr = logits + r * pitch;
+        float* __restrict__ dr = dlogits + r * pitch;
+        const long y = labels[r];
+        const bool on = y != ignore && y >= 0 && y < nc;
+        const float l = lse[r];
+        const float f = on ? (scale ? sc : row_grad[r]) : 0.0f;
+        const float a = (1.0f - eps) * (on ? ce_w<HAS_W>(w, (int)y) : 0.0f);
+        const float fp = f * (a + b * W), fa = f * a, fb = f * b;
+        int c = 0;
+        for (; c < nc; c += 4) {
+            const float4 v = *reinterpret_cast<const float4*>(xr + c);
+            float4 o = ce_opt_grad_chunk<HAS_W>(w, c, v, PAD ? nc - c : 4, l, y, fp, fa, fb);
+            if (PAD) ce_mask_tail(o, nc - c, 0.0f);
+            *reinterpret_cast<float4*>(dr + c) = o;
+        }
+        if (PAD)
+            for (; c < ld; c += 4) *reinterpret_cast<float4*>(dr + c) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
+
+template <int NC4, bool PAD, bool HAS_W>
+__global__ void __launch_bounds__(256)
+softmax_ce_opt_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w, long rows,
+                              int nc_, int ld, long ignore, float eps, float* __restrict__ lse, float* __restrict__ row_loss,
+                              float* __restrict__ partial) {
+    __shared__ float sh[4];
+    const int nc = PAD ? nc_ : NC4 * 4;
+    const int pitch = PAD ? ld : NC4 * 4;
+    float loss = 0.0f, den = 0.0f;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const float W = ce_weight_sum<HAS_W>(w, nc), inv_c = 1.0f / (float)nc;
+    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
+        const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * pitch);
+        float4 v[NC4];
+#pragma unroll
+        for (int c = 0; c < NC4; ++c) v[c] = xr[c];
+        const long y = labels[r];
+        float sx = 0.0f;
+        if (eps > 0.0f) {
+#pragma unroll
+            for (int c = 0; c < NC4; ++c) sx += ce_wx_chunk<HAS_W>(w, 4 * c, v[c], (PAD && c == NC4 - 1) ? nc - 4 * c : 4);
+        }
+        if (PAD) ce_mask_tail(v[NC4 - 1], nc - 4 * (NC4 - 1), kNegInf);
+        float m = kNegInf;
+#pragma unroll
+        for (int c = 0; c < NC4; ++c) m = fmaxf(m, fmaxf(fmaxf(v[c].x, v[c].y), fmaxf(v[c].z, v[c].w)));
+        float s = 0.0f, xy = 0.0f;
+#pragma unroll
+        for (int c = 0; c < NC4; ++c) {
+            s += (__expf(v[c].x - m) + __expf(v[c].y - m)) + (__expf(v[c].z - m) + __expf(v[c].w - m));
+            xy = (y == 4 * c) ? v[c].x : (y == 4 * c + 1) ? v[c].y : (y == 4 * c + 2) ? v[c].z : (y == 4 * c + 3) ? v[c].w : xy;
+        }
+        const float l = m + __logf(s);
+        lse[r] = l;
+        float rl = 0.0f;
+        if (y != ignore && y >= 0 && y < nc) {
+            const float wy = ce_w<HAS_W>(w, (int)y);
+            rl = ce_opt_row_loss(eps, inv_c, wy, W, l, xy, sx);
+            loss += rl;
+            den += wy;
+        }
+        if (row_loss) row_loss[r] = rl;
+    }
+    const float tl = block_sum(loss, sh);
+    const float td = block_sum(den, sh);
+    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = td; }
+}
+
+template <int NC4, bool PAD, bool HAS_W>
+__global__ void __launch_bounds__(256)
+softmax_ce_opt_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w,
+                              const float* __restrict__ lse, const float* __restrict__ scale, const float* __restrict__ row_grad, long rows,
+                              int nc_, int ld, long ignore, float eps, float* __restrict__ dlogits) {
+    const int nc = PAD ? nc_ : NC4 * 4;
+    const int pitch = PAD ? ld : NC4 * 4;
+    const float sc = scale ? scale[0] : 0.0f;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const float W = ce_weight_sum<HAS_W>(w, nc), b = eps * (1.0f / (float)nc);
+    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
+        const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * pitch);
+        float4* __restrict__ dr = reinterpret_cast<float4*>(dlogits + r * pitch);
+        float4 v[NC4];
+#pragma unroll
+        for (int c = 0; c < NC4; ++c) v[c] = xr[c];
+        const long y = labels[r];
+        const float l = lse[r];
+        const bool on = y != ignore && y >= 0 && y < nc;
+        const float f = on ? (scale ? sc : row_grad[r]) : 0.0f;
+        const float a = (1.0f - eps) * (on ? ce_w<HAS_W>(w, (int)y) : 0.0f);
+        const float fp = f * (a + b * W), fa = f * a, fb = f * b;
+#pragma unroll
+        for (int c = 0; c < NC4; ++c) {
+            const bool tail = PAD && c == NC4 - 1;
+            float4 o = ce_opt_grad_chunk<HAS_W>(w, 4 * c, v[c], tail ? nc - 4 * c : 4, l, y, fp, fa, fb);
+            if (tail) ce_mask_tail(o, nc - 4 * c, 0.0f);
+            dr[c] = o;
+        }
+        if (PAD)
+            for (int c = NC4; c < (ld >> 2); ++c) dr[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
 
 // ---- backward of  y = a + x * s  with a per-channel s on channels-last rows (CVSSDecoderBlock, vmamba.py:1800-1805) ------
 // dx = dy * s and ds += sum over rows of dy * x, one pass over dy and x.  A thread keeps ONE 16-byte column chunk for the
@@ -532,6 +733,76 @@ int sigma_softmax_ce_bwd_ld(const float* logits, const int64_t* labels, const fl
         if (pad) hipLaunchKernelGGL(sigma::softmax_ce_bwd_kernel<true>, grid, block, 0, s, logits, labels, lse, scale, nrows, nc, pitch, ignore, dlogits);
         else hipLaunchKernelGGL(sigma::softmax_ce_bwd_kernel<false>, grid, block, 0, s, logits, labels, lse, scale, nrows, nc, pitch, ignore, dlogits);
     }
+    return sigma::done();
+}
+
+// everything sigma_softmax_ce_opt_fwd and _bwd check alike, before any launch
+static int ce_opt_check(const sigma_ce_opt_params* p) {
+    if (!p || p->rows < 0 || p->classes < 1 || p->ld % 4 != 0 || p->ld < p->classes) return SIGMA_OPS_ERR_ARG;
+    if (!(p->label_smoothing >= 0.0f && p->label_smoothing <= 1.0f)) return SIGMA_OPS_ERR_ARG;      // NaN fails both
+    if (!sigma::al4(p->weight) || !sigma::al4(p->lse) || !sigma::al4(p->row_loss) || !sigma::al4(p->partial) ||
+        !sigma::al4(p->scale) || !sigma::al4(p->row_grad) || (reinterpret_cast<uintptr_t>(p->labels) & 7u) != 0)
+        return SIGMA_OPS_ERR_ARG;
+    return SIGMA_OPS_OK;
+}
+
+int sigma_softmax_ce_opt_fwd(const sigma_ce_opt_params* p, void* stream) {
+    if (const int rc = ce_opt_check(p)) return rc;
+    if (!p->partial) return SIGMA_OPS_ERR_ARG;
+    if (p->rows > 0 && (!p->logits || !p->labels || !p->lse || !sigma::al16(p->logits))) return SIGMA_OPS_ERR_ARG;
+    // every one of the SIGMA_CE_BLOCKS workgroups writes its (loss, weight) pair, rows or not: the caller adds them up
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid(SIGMA_CE_BLOCKS), block(256);
+    const long nrows = (long)p->rows, ignore = (long)p->ignore_index;
+    const int nc = (int)p->classes, pitch = (int)p->ld;
+    const bool pad = p->ld != p->classes, hw = p->weight != nullptr;
+    const float eps = p->label_smoothing;
+#define SIGMA_CE_OPT_FWD(K) hipLaunchKernelGGL(K, grid, block, 0, s, p->logits, p->labels, p->weight, nrows, nc, pitch, ignore, eps, \
+                                               p->lse, p->row_loss, p->partial)
+    const bool reg = sigma::dispatch_nc4((nc + 3) / 4, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        if (pad && hw) SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_reg_kernel<N, true, true>));
+        else if (pad) SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_reg_kernel<N, true, false>));
+        else if (hw) SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_reg_kernel<N, false, true>));
+        else SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_reg_kernel<N, false, false>));
+    });
+    if (!reg) {
+        if (pad && hw) SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_kernel<true, true>));
+        else if (pad) SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_kernel<true, false>));
+        else if (hw) SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_kernel<false, true>));
+        else SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_kernel<false, false>));
+    }
+#undef SIGMA_CE_OPT_FWD
+    return sigma::done();
+}
+
+int sigma_softmax_ce_opt_bwd(const sigma_ce_opt_params* p, void* stream) {
+    if (const int rc = ce_opt_check(p)) return rc;
+    if ((p->scale != nullptr) == (p->row_grad != nullptr)) return SIGMA_OPS_ERR_ARG;      // one of them, not both
+    if (p->rows == 0) return SIGMA_OPS_OK;
+    if (!p->logits || !p->labels || !p->lse || !p->dlogits || !sigma::al16(p->logits) || !sigma::al16(p->dlogits)) return SIGMA_OPS_ERR_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid(sigma::stream_grid(p->rows)), block(256);
+    const long nrows = (long)p->rows, ignore = (long)p->ignore_index;
+    const int nc = (int)p->classes, pitch = (int)p->ld;
+    const bool pad = p->ld != p->classes, hw = p->weight != nullptr;
+    const float eps = p->label_smoothing;
+#define SIGMA_CE_OPT_BWD(K) hipLaunchKernelGGL(K, grid, block, 0, s, p->logits, p->labels, p->weight, p->lse, p->scale, p->row_grad, nrows, \
+                                               nc, pitch, ignore, eps, p->dlogits)
+    const bool reg = sigma::dispatch_nc4((nc + 3) / 4, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        if (pad && hw) SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_reg_kernel<N, true, true>));
+        else if (pad) SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_reg_kernel<N, true, false>));
+        else if (hw) SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_reg_kernel<N, false, true>));
+        else SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_reg_kernel<N, false, false>));
+    });
+    if (!reg) {
+        if (pad && hw) SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_kernel<true, true>));
+        else if (pad) SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_kernel<true, false>));
+        else if (hw) SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_kernel<false, true>));
+        else SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_kernel<false, false>));
+    }
+#undef SIGMA_CE_OPT_BWD
     return sigma::done();
 }
 

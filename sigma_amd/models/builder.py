@@ -106,8 +106,9 @@ class EncoderDecoder(nn.Module):
     def forward(self, rgb, modal_x, label=None):
         out = self.encode_decode(rgb, modal_x)
         if label is not None:
-            # mean cross entropy straight from the channels-last logits of the classifier GEMM (csrc/pointwise.hip); any
-            # other criterion / layout: the criterion itself on the (B, nc, H, W) view
+            # cross entropy (any weight / label_smoothing / reduction; 'none' gives (B, H, W)) straight from the channels-last
+            # logits of the classifier GEMM (csrc/pointwise.hip); any other criterion / layout: the criterion itself on the
+            # (B, nc, H, W) view
             from ..pointwise import cross_entropy, cross_entropy_deterministic
             loss = cross_entropy(self.criterion, out, label) if out.is_cuda else None
             if loss is None and torch.are_deterministic_algorithms_enabled():

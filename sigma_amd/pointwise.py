@@ -6,7 +6,8 @@
                    that writes dx.
 ``cross_entropy``  nn.CrossEntropyLoss(reduction='mean', ignore_index) of models/builder.py:146-166 on the CHANNELS-LAST
                    logits the classifier GEMM produces (MambaDecoder.up_x4): log-sum-exp + loss in one pass, gradient in
-                   one pass, no (B, classes, H, W) copy.
+                   one pass, no (B, classes, H, W) copy.  Class weights, label smoothing and the reductions 'sum' /
+                   'none' run on kernels of their own (``SoftmaxCEOptFn``).
 
 GPU tensors only (no fallback); the callers keep the torch formulation for everything these kernels do not take.
 """
@@ -207,18 +208,113 @@ def _row_pitch(nhwc: torch.Tensor):
     return ld
 
 
+class SoftmaxCEOptFn(torch.autograd.Function):
+    """nn.CrossEntropyLoss with class weights, label smoothing and any reduction on the same rows as ``SoftmaxCEFn``
+    (sigma_softmax_ce_opt_fwd / _bwd, either pitch).  'mean' divides the summed row losses by the summed weights of the
+    labelled pixels ON THE DEVICE; 'sum' returns the sum; 'none' the per-pixel losses in `out_shape` (zeros at ignored
+    pixels).  The weight gets no gradient, as in torch.  A zero denominator ('mean' with nothing labelled, or only
+    zero-weight classes) gives a NaN loss (0 / 0), as ``SoftmaxCEFn`` does, and an all-zero gradient."""
+
+    @staticmethod
+    def _params(logits2, labels, weight, lse, ignore_index, ld, eps):
+        p = _capi.CeOptParams()
+        p.rows, p.classes, p.ld = logits2.shape[0], logits2.shape[1], ld
+        p.ignore_index, p.label_smoothing = int(ignore_index), float(eps)
+        p.logits, p.labels, p.lse = logits2.data_ptr(), labels.data_ptr(), lse.data_ptr()
+        p.weight = weight.data_ptr() if weight is not None else None
+        return p
+
+    @staticmethod
+    def forward(ctx, logits2, labels, weight, ignore_index, ld, eps, reduction, out_shape):
+        lib = _capi.load()
+        rows = logits2.shape[0]
+        dev = logits2.device
+        lse = torch.empty(rows, device=dev, dtype=torch.float32)
+        partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=dev, dtype=torch.float32)
+        row_loss = torch.empty(rows, device=dev, dtype=torch.float32) if reduction == "none" else None
+        p = SoftmaxCEOptFn._params(logits2, labels, weight, lse, ignore_index, ld, eps)
+        p.partial = partial.data_ptr()
+        p.row_loss = row_loss.data_ptr() if row_loss is not None else None
+        with torch.cuda.device(dev):
+            _capi.check(lib.sigma_softmax_ce_opt_fwd(ctypes.byref(p), _stream()), "softmax_ce_opt_fwd")
+        tot = partial.sum(0)
+        ctx.save_for_backward(logits2, labels, lse, tot, weight)
+        ctx.ignore_index, ctx.ld, ctx.eps, ctx.reduction = int(ignore_index), ld, float(eps), reduction
+        if reduction == "none":
+            return row_loss.view(out_shape)
+        return tot[0] / tot[1] if reduction == "mean" else tot[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _capi.load()
+        logits2, labels, lse, tot, weight = ctx.saved_tensors
+        rows, nc = logits2.shape
+        ld = ctx.ld
+        p = SoftmaxCEOptFn._params(logits2, labels, weight, lse, ctx.ignore_index, ld, ctx.eps)
+        if ctx.reduction == "none":
+            grad = g.float().contiguous().view(-1)
+            p.row_grad = grad.data_ptr()
+        else:
+            grad = g.float().reshape(1)
+            if ctx.reduction == "mean":
+                grad = torch.where(tot[1:2] > 0, grad / tot[1:2], torch.zeros_like(grad))      # zero denominator: zero gradient
+            grad = grad.contiguous()
+            p.scale = grad.data_ptr()
+        full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
+        p.dlogits = full.data_ptr()
+        with torch.cuda.device(logits2.device):
+            _capi.check(lib.sigma_softmax_ce_opt_bwd(ctypes.byref(p), _stream()), "softmax_ce_opt_bwd")
+        if ld != nc:
+            # as SoftmaxCEFn: the classifier's backward claims the whole padded buffer (_handoff.py)
+            offer_padded_grad_buffer(full)
+            full = full[:, :nc]
+        return full, None, None, None, None, None, None, None
+
+
+CE_REDUCTIONS = ("mean", "sum", "none")
+
+
+def criterion_route(criterion, device, classes, any_float_weight=False):
+    """Which Function takes `criterion` for logits of `classes` classes on `device`: "plain" (``SoftmaxCEFn``: mean, no
+    weight, no smoothing), "options" (``SoftmaxCEOptFn``: anything else an nn.CrossEntropyLoss can be told, with the weight
+    None or a 1-D fp32 tensor of `classes` elements on `device`), or None: a subclass or another criterion, a weight of
+    another dtype (unless `any_float_weight`: the element-wise formulation casts it), size or device."""
+    if type(criterion) is not nn.CrossEntropyLoss or criterion.reduction not in CE_REDUCTIONS:
+        return None
+    eps = float(getattr(criterion, "label_smoothing", 0.0))
+    w = criterion.weight
+    if criterion.reduction == "mean" and w is None and eps == 0.0:
+        return "plain"
+    if not 0.0 <= eps <= 1.0:
+        return None
+    if w is not None:
+        dtype_ok = w.is_floating_point() if any_float_weight else w.dtype == torch.float32
+        if not (dtype_ok and w.dim() == 1 and w.numel() == classes and w.device == torch.device(device)):
+            return None
+    return "options"
+
+
 def cross_entropy(criterion, logits: torch.Tensor, label: torch.Tensor):
-    """criterion(logits, label) for a plain mean-reduced nn.CrossEntropyLoss on channels-last logits -- logits is the
-    (B, classes, H, W) VIEW of a contiguous (B, H, W, classes) tensor with classes % 4 == 0, or of the first `classes`
-    columns of a (B, H, W, ld) buffer with ld % 4 == 0 (any class count: the padded classifier output of
-    MambaDecoder.up_x4) -- or None when this path does not apply.
+    """criterion(logits, label) for an nn.CrossEntropyLoss on channels-last logits -- logits is the (B, classes, H, W) VIEW
+    of a contiguous (B, H, W, classes) tensor with classes % 4 == 0, or of the first `classes` columns of a (B, H, W, ld)
+    buffer with ld % 4 == 0 (any class count: the padded classifier output of MambaDecoder.up_x4) -- or None when this
+    path does not apply.  The plain criterion (mean, no weight, no smoothing) takes ``SoftmaxCEFn`` as it always has;
+    ``weight`` (1-D fp32, on the logits' device), ``label_smoothing`` and ``reduction`` 'sum' / 'none' take
+    ``SoftmaxCEOptFn`` ('none' returns (B, H, W)); see ``criterion_route`` for what is declined.  One combination keeps
+    the answer it always had here, None: ``reduction='none'`` with neither a weight nor smoothing
+    (tests/test_pointwise_gpu.py pins it).  The caller then runs the criterion itself or, under the deterministic flag,
+    ``cross_entropy_deterministic``; the kernels take it (a NULL weight, eps = 0, a row loss), only this router does not.
     Labels outside [0, classes) that are not ``ignore_index`` are treated as ignored (csrc/pointwise.hip), where
     torch's kernel device-asserts: the reference's datasets map every unlabeled pixel to 255 = ignore_index
     (dataloader/RGBXDataset.py), so such labels do not occur on this path."""
-    if not (type(criterion) is nn.CrossEntropyLoss and criterion.reduction == "mean" and criterion.weight is None
-            and getattr(criterion, "label_smoothing", 0.0) == 0.0):
+    if not (logits.dim() == 4 and label.dim() == 3):
         return None
-    if not (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 4 and label.dim() == 3 and label.is_cuda):
+    route = criterion_route(criterion, logits.device, logits.shape[1])
+    if route is None:
+        return None
+    if criterion.reduction == "none" and criterion.weight is None and float(getattr(criterion, "label_smoothing", 0.0)) == 0.0:
+        return None                                        # declined before the option kernels existed, and still (see above)
+    if not (logits.is_cuda and logits.dtype == torch.float32 and label.is_cuda):
         return None
     nhwc = logits.permute(0, 2, 3, 1)
     nc = nhwc.shape[-1]
@@ -228,21 +324,51 @@ def cross_entropy(criterion, logits: torch.Tensor, label: torch.Tensor):
     if ld is None or ld % 4 != 0 or ld < nc:
         return None
     lab = label.long().contiguous()
-    return SoftmaxCEFn.apply(nhwc.reshape(-1, nc), lab.view(-1), criterion.ignore_index, ld)      # reshape: a view at either pitch
+    if route == "plain":
+        return SoftmaxCEFn.apply(nhwc.reshape(-1, nc), lab.view(-1), criterion.ignore_index, ld)      # reshape: a view at either pitch
+    w = criterion.weight
+    if w is not None:
+        w = w.detach().contiguous()
+        if w.data_ptr() % 4 != 0:
+            return None
+    return SoftmaxCEOptFn.apply(nhwc.reshape(-1, nc), lab.view(-1), w, criterion.ignore_index, ld, float(criterion.label_smoothing),
+                                criterion.reduction, tuple(label.shape))
 
 
 def cross_entropy_deterministic(criterion, logits: torch.Tensor, label: torch.Tensor):
-    """Deterministic mode only (sigma_amd/deterministic.py): criterion(logits, label) for a plain mean-reduced
-    nn.CrossEntropyLoss where ``cross_entropy`` above does not apply (a class count that is not a multiple of 4, as in
-    the small test models), or None.  torch's nll_loss2d raises under the deterministic flag; this formulation uses only
-    element-wise ops and fixed-order reductions: -sum(log_softmax * one_hot) over the non-ignored pixels / their count."""
-    if not (type(criterion) is nn.CrossEntropyLoss and criterion.reduction == "mean" and criterion.weight is None
-            and getattr(criterion, "label_smoothing", 0.0) == 0.0 and logits.dim() == 4 and label.dim() == 3):
+    """Deterministic mode only (sigma_amd/deterministic.py): criterion(logits, label) for an nn.CrossEntropyLoss -- class
+    weights, label smoothing and any reduction included -- where ``cross_entropy`` above declines on LAYOUT: contiguous
+    (B, classes, H, W) logits with classes % 4 != 0, i.e. SIGMA_GEMM=fp32 and the small test models; or None.  torch's
+    nll_loss2d raises under the deterministic flag; this formulation uses only element-wise ops and fixed-order
+    reductions: per pixel -(1 - eps) w_y log_softmax[y] - (eps / classes) sum_c w_c log_softmax[c], zero at ignored
+    pixels (labels outside [0, classes) count as ignored, as on the kernels); 'mean' divides the sum by the sum of w_y
+    over the labelled pixels (0 / 0 = NaN when there is none)."""
+    if not (logits.dim() == 4 and label.dim() == 3):
         return None
     nc = logits.shape[1]
+    route = criterion_route(criterion, logits.device, nc, any_float_weight=True)
+    if route is None:
+        return None
+    w = criterion.weight
     lab = label.long()
     valid = (lab != criterion.ignore_index) & (lab >= 0) & (lab < nc)
     onehot = F.one_hot(torch.where(valid, lab, torch.zeros_like(lab)), nc).permute(0, 3, 1, 2).to(logits.dtype)
-    per_pixel = -(F.log_softmax(logits, dim=1) * onehot).sum(dim=1)
     validf = valid.to(logits.dtype)
-    return (per_pixel * validf).sum() / validf.sum()
+    if route == "plain":
+        per_pixel = -(F.log_softmax(logits, dim=1) * onehot).sum(dim=1)
+        return (per_pixel * validf).sum() / validf.sum()
+    eps = float(criterion.label_smoothing)
+    lsm = F.log_softmax(logits, dim=1)
+    if w is not None:
+        wv = w.detach().to(logits.dtype).view(1, nc, 1, 1)
+        lsm_w = lsm * wv
+        wy = (onehot * wv).sum(dim=1) * validf
+    else:
+        lsm_w, wy = lsm, validf
+    per_pixel = -(lsm_w * onehot).sum(dim=1)
+    if eps > 0.0:
+        per_pixel = (1.0 - eps) * per_pixel - (eps / nc) * lsm_w.sum(dim=1)
+    per_pixel = per_pixel * validf
+    if criterion.reduction == "none":
+        return per_pixel
+    return per_pixel.sum() / wy.sum() if criterion.reduction == "mean" else per_pixel.sum()

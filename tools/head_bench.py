@@ -3,6 +3,7 @@
 counts that are and are not multiples of 4.
 
     python tools/head_bench.py [--reps 30] [--warmup 5] [--out profiles/head_classes_mi355x.jsonl]
+    python tools/head_bench.py --criterion weight weight_eps --out profiles/loss_options_mi355x.jsonl
 
 Route A: the formulation up to and including the commit before the padded head: ``gemm.linear`` against the (nc, C)
 weight, then ``pointwise.cross_entropy`` on the (B, nc, H, W) view, which declines rows of nc floats with nc % 4 != 0, so
@@ -13,6 +14,12 @@ floats) where ``classifier_ok``, and ``pointwise.cross_entropy`` on its view.  F
 A and B alternate inside one process on one seeded (B, H, W, C) input; each repetition is one forward + backward between
 two device events.  One JSON line per shape: median and spread (min, max, inter-quartile range) of each route in ms, and
 each route's algorithmic bytes (what an ideal implementation of that route's passes moves; see ``route_bytes``).
+
+``--criterion weight`` (class weights, seeded in [0.1, 2.1]) and ``weight_eps`` (the same weights and label smoothing 0.1)
+time the criterion's options on the same four shapes.  Route A there is the behaviour up to the commit before the option
+kernels: the head as in route B and the criterion itself, ``crit(out, label)``, on the (B, nc, H, W) view.  Route B is
+``pointwise.cross_entropy`` (sigma_softmax_ce_opt_fwd / _bwd).  A third route P, the PLAIN criterion on route B's code,
+alternates with them: option and plain kernels move the same algorithmic bytes, so B / P is what the options cost.
 """
 import argparse
 import json
@@ -49,6 +56,24 @@ def route_b(x, w, label, crit):
     return loss if loss is not None else crit(out, label)
 
 
+def route_a_criterion(x, w, label, crit):
+    """the head of route B, then the criterion itself on the view (what EncoderDecoder.forward fell through to)"""
+    from sigma_amd import gemm
+    if gemm.classifier_ok(x.reshape(-1, x.shape[-1]), w):
+        out = gemm.classifier(x, w).permute(0, 3, 1, 2)
+    else:
+        out = gemm.linear(x, w.view(w.shape[0], -1)).permute(0, 3, 1, 2)
+    return crit(out, label)
+
+
+def criterion_bytes(M, C, nc):
+    """route A of the option criteria: the GEMMs at the padded pitch, the criterion's passes on rows of nc floats (as in
+    ``route_bytes``; the smoothing term's extra passes are not counted) and the copy of the gradient into padded rows"""
+    ld = (nc + 3) // 4 * 4
+    x, lab, z, zp = 4 * M * C, 8 * M, 4 * M * nc, 4 * M * ld
+    return (x + zp) + 2 * z + 2 * z + (lab + 4 * M) + (z + lab) + 3 * z + (z + zp) + (zp + x) + (zp + x)
+
+
 def route_bytes(M, C, nc):
     """algorithmic bytes of one forward + backward: every pass reads its inputs and writes its outputs once (fp32, int64
     labels, per-pixel log-sum-exp)
@@ -78,28 +103,35 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default="")
+    ap.add_argument("--criterion", nargs="+", default=["plain"], choices=["plain", "weight", "weight_eps"])
     a = ap.parse_args()
     if a.reps < 30:
         ap.error("at least 30 repetitions")
     dev = torch.device("cuda", 0)
-    crit = nn.CrossEntropyLoss(reduction="mean", ignore_index=IGNORE)
+    plain = nn.CrossEntropyLoss(reduction="mean", ignore_index=IGNORE)
     lines = []
-    for B, H, W, C, nc in SHAPES:
+    for B, H, W, C, nc, kind in [(*shape, kind) for kind in a.criterion for shape in SHAPES]:
         g = torch.Generator().manual_seed(1234)
         x = torch.randn(B, H, W, C, generator=g).to(dev).requires_grad_()
         w = nn.Parameter((torch.randn(nc, C, 1, 1, generator=g) / C ** 0.5).to(dev))
         label = torch.randint(0, nc, (B, H, W), generator=g)
         label[torch.rand(B, H, W, generator=g) < 0.1] = IGNORE
         label = label.to(dev)
-        routes = {"A": route_a, "B": route_b}
+        if kind == "plain":
+            crit = plain
+            routes = {"A": (route_a, crit), "B": (route_b, crit)}
+        else:
+            cw = (torch.rand(nc, generator=torch.Generator().manual_seed(4321)) * 2.0 + 0.1).to(dev)
+            crit = nn.CrossEntropyLoss(weight=cw, reduction="mean", ignore_index=IGNORE, label_smoothing=0.1 if kind == "weight_eps" else 0.0)
+            routes = {"A": (route_a_criterion, crit), "B": (route_b, crit), "P": (route_b, plain)}
         times = {k: [] for k in routes}
         losses = {}
         for i in range(a.warmup + a.reps):
-            for k, fn in routes.items():
+            for k, (fn, c) in routes.items():
                 x.grad = w.grad = None
                 t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 t0.record()
-                loss = fn(x, w, label, crit)
+                loss = fn(x, w, label, c)
                 loss.backward()
                 t1.record()
                 t1.synchronize()
@@ -110,6 +142,11 @@ def main():
         line = {"shape": [B, H, W, C], "classes": nc, "reps": a.reps, "warmup": a.warmup, "A": sa, "B": sb,
                 "B_over_A": round(sb["median_ms"] / sa["median_ms"], 4), "loss_A": losses["A"], "loss_B": losses["B"],
                 "algorithmic_bytes": route_bytes(B * H * W, C, nc), "device": torch.cuda.get_device_name(0)}
+        if kind != "plain":
+            sp = spread(times["P"])
+            kern = route_bytes(B * H * W, C, nc)["B"]
+            line.update({"criterion": kind, "P": sp, "B_over_P": round(sb["median_ms"] / sp["median_ms"], 4), "loss_P": losses["P"],
+                         "algorithmic_bytes": {"A": criterion_bytes(B * H * W, C, nc), "B": kern, "P": kern}})
         print(json.dumps(line), flush=True)
         lines.append(line)
         del x, w, label
