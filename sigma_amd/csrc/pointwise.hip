@@ -15,8 +15,8 @@
 //   softmax_ce_fwd  per pixel (a row of `classes` contiguous logits): log-sum-exp (kept for the backward) and
 //                   lse - logit[label]; per-workgroup partial (sum, count) in a fixed layout -> deterministic mean
 //   softmax_ce_bwd  dlogit = (exp(logit - lse) - [class == label]) * scale, zero rows for ignored pixels
-//   softmax_ce_opt_fwd / _bwd  the same two passes with class weights, label smoothing, a per-row loss ('none') and a
-//                   per-row upstream gradient: every option of nn.CrossEntropyLoss
+//                   Both as OPT instantiations too, for the sigma_softmax_ce_opt entry points: class weights, label
+//                   smoothing, a per-row loss ('none') and a per-row upstream gradient, every option of nn.CrossEntropyLoss
 //
 // All of them are bound by HBM: bytes per element 4 (pool), 8 (scale, dot), 12 (gate_bwd), 4 / 8 (loss fwd / bwd).
 #include <hip/hip_runtime.h>
@@ -160,8 +160,8 @@ __global__ void __launch_bounds__(256) plane_gate_bwd_kernel(const GateBwdArgs a
 }
 
 // ---- softmax cross entropy over rows of `nc` logits at a pitch of `ld` floats (ld % 4 == 0, ld >= nc), one thread per row
-// PAD = false: nc % 4 == 0 and ld == nc, the contiguous rows of sigma_softmax_ce_fwd / _bwd.  PAD = true (the _ld entry
-// points): only columns < nc count.  The forward reads the last 16-byte chunk that holds a valid column whole and puts
+// PAD = false: nc % 4 == 0 and ld == nc, the contiguous rows of sigma_softmax_ce_fwd / _bwd.  PAD = true (ld != nc):
+// only columns < nc count.  The forward reads the last 16-byte chunk that holds a valid column whole and puts
 // -inf over its tail, later chunks are not read; the backward writes exact zeros over [nc, ld), chosen by index (the pad
 // of the input may hold NaN, and the GEMMs that read dlogits take whole rows of ld).
 __device__ __forceinline__ void ce_mask_tail(float4& v, int n, float fill) {      // n in [1, 4] columns of v are valid
@@ -170,156 +170,23 @@ __device__ __forceinline__ void ce_mask_tail(float4& v, int n, float fill) {    
     if (n < 4) v.w = fill;
 }
 
-template <bool PAD>
-__global__ void __launch_bounds__(256)
-softmax_ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, long rows, int nc, int ld, long ignore,
-                      float* __restrict__ lse, float* __restrict__ partial) {
-    __shared__ float sh[4];
-    float loss = 0.0f, count = 0.0f;
-    const long stride = (long)gridDim.x * blockDim.x;
-    const int pitch = PAD ? ld : nc;
-    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
-        const float* __restrict__ xr = logits + r * pitch;
-        float m = kNegInf, s = 0.0f;                   // running max and sum of exp(x - m)
-        for (int c = 0; c < nc; c += 4) {
-            float4 v = *reinterpret_cast<const float4*>(xr + c);
-            if (PAD) ce_mask_tail(v, nc - c, kNegInf);
-            const float vm = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
-            if (vm > m) { s *= __expf(m - vm); m = vm; }
-            s += (__expf(v.x - m) + __expf(v.y - m)) + (__expf(v.z - m) + __expf(v.w - m));
-        }
-        const float l = m + __logf(s);
-        lse[r] = l;
-        const long y = labels[r];
-        if (y != ignore && y >= 0 && y < nc) { loss += l - xr[y]; count += 1.0f; }
-    }
-    const float tl = block_sum(loss, sh);
-    const float tc = block_sum(count, sh);
-    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = tc; }
-}
-
-template <bool PAD>
-__global__ void __launch_bounds__(256)
-softmax_ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ lse,
-                      const float* __restrict__ scale, long rows, int nc, int ld, long ignore, float* __restrict__ dlogits) {
-    const float sc = scale[0];
-    const long stride = (long)gridDim.x * blockDim.x;
-    const int pitch = PAD ? ld : nc;
-    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
-        const float* __restrict__ xr = logits + r * pitch;
-        float* __restrict__ dr = dlogits + r * pitch;
-        const long y = labels[r];
-        const bool on = y != ignore && y >= 0 && y < nc;
-        const float l = lse[r];
-        const float f = on ? sc : 0.0f;
-        int c = 0;
-        for (; c < nc; c += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(xr + c);
-            float4 o;
-            o.x = (__expf(v.x - l) - (y == c ? 1.0f : 0.0f)) * f;
-            o.y = (__expf(v.y - l) - (y == c + 1 ? 1.0f : 0.0f)) * f;
-            o.z = (__expf(v.z - l) - (y == c + 2 ? 1.0f : 0.0f)) * f;
-            o.w = (__expf(v.w - l) - (y == c + 3 ? 1.0f : 0.0f)) * f;
-            if (PAD) ce_mask_tail(o, nc - c, 0.0f);
-            *reinterpret_cast<float4*>(dr + c) = o;
-        }
-        if (PAD)
-            for (; c < ld; c += 4) *reinterpret_cast<float4*>(dr + c) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-}
-
-// Same kernels with the row (NC4 float4) held in registers: every load of a row is issued before the first use.  The
-// generic kernels above walk the row with one load in flight per thread (1.2 TB/s on 8 x 480 x 640 x 40).  PAD = true:
-// NC4 = ceil(nc / 4) chunks hold the valid columns.
-template <int NC4, bool PAD>
-__global__ void __launch_bounds__(256)
-softmax_ce_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, long rows, int nc_, int ld, long ignore,
-                          float* __restrict__ lse, float* __restrict__ partial) {
-    __shared__ float sh[4];
-    const int nc = PAD ? nc_ : NC4 * 4;
-    const int pitch = PAD ? ld : NC4 * 4;
-    float loss = 0.0f, count = 0.0f;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
-        const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * pitch);
-        float4 v[NC4];
-#pragma unroll
-        for (int c = 0; c < NC4; ++c) v[c] = xr[c];
-        if (PAD) ce_mask_tail(v[NC4 - 1], nc - 4 * (NC4 - 1), kNegInf);
-        const long y = labels[r];
-        float m = kNegInf;
-#pragma unroll
-        for (int c = 0; c < NC4; ++c) m = fmaxf(m, fmaxf(fmaxf(v[c].x, v[c].y), fmaxf(v[c].z, v[c].w)));
-        float s = 0.0f, xy = 0.0f;
-#pragma unroll
-        for (int c = 0; c < NC4; ++c) {
-            s += (__expf(v[c].x - m) + __expf(v[c].y - m)) + (__expf(v[c].z - m) + __expf(v[c].w - m));
-            xy = (y == 4 * c) ? v[c].x : (y == 4 * c + 1) ? v[c].y : (y == 4 * c + 2) ? v[c].z : (y == 4 * c + 3) ? v[c].w : xy;
-        }
-        const float l = m + __logf(s);
-        lse[r] = l;
-        if (y != ignore && y >= 0 && y < nc) { loss += l - xy; count += 1.0f; }
-    }
-    const float tl = block_sum(loss, sh);
-    const float tc = block_sum(count, sh);
-    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = tc; }
-}
-
-template <int NC4, bool PAD>
-__global__ void __launch_bounds__(256)
-softmax_ce_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ lse,
-                          const float* __restrict__ scale, long rows, int nc_, int ld, long ignore, float* __restrict__ dlogits) {
-    const int nc = PAD ? nc_ : NC4 * 4;
-    const int pitch = PAD ? ld : NC4 * 4;
-    const float sc = scale[0];
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
-        const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * pitch);
-        float4* __restrict__ dr = reinterpret_cast<float4*>(dlogits + r * pitch);
-        float4 v[NC4];
-#pragma unroll
-        for (int c = 0; c < NC4; ++c) v[c] = xr[c];
-        const long y = labels[r];
-        const float l = lse[r];
-        const float f = (y != ignore && y >= 0 && y < nc) ? sc : 0.0f;
-#pragma unroll
-        for (int c = 0; c < NC4; ++c) {
-            float4 o;
-            o.x = (__expf(v[c].x - l) - (y == 4 * c ? 1.0f : 0.0f)) * f;
-            o.y = (__expf(v[c].y - l) - (y == 4 * c + 1 ? 1.0f : 0.0f)) * f;
-            o.z = (__expf(v[c].z - l) - (y == 4 * c + 2 ? 1.0f : 0.0f)) * f;
-            o.w = (__expf(v[c].w - l) - (y == 4 * c + 3 ? 1.0f : 0.0f)) * f;
-            if (PAD && c == NC4 - 1) ce_mask_tail(o, nc - 4 * (NC4 - 1), 0.0f);
-            dr[c] = o;
-        }
-        if (PAD)
-            for (int c = NC4; c < (ld >> 2); ++c) dr[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-}
-
-// NC4 = ceil(classes / 4) chunks held in registers up to 64 classes
-template <typename F>
-bool dispatch_nc4(int nc4, F&& f) {
-    switch (nc4) {
-#define SIGMA_NC4(N) case N: f(std::integral_constant<int, N>()); return true;
-        SIGMA_NC4(1) SIGMA_NC4(2) SIGMA_NC4(3) SIGMA_NC4(4) SIGMA_NC4(5) SIGMA_NC4(6) SIGMA_NC4(7) SIGMA_NC4(8)
-        SIGMA_NC4(9) SIGMA_NC4(10) SIGMA_NC4(11) SIGMA_NC4(12) SIGMA_NC4(13) SIGMA_NC4(14) SIGMA_NC4(15) SIGMA_NC4(16)
-#undef SIGMA_NC4
-        default: return false;
-    }
-}
-
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
-// ---- the same loss with the options of nn.CrossEntropyLoss: class weights w, label smoothing eps, a per-row loss and a
-// per-row upstream gradient (sigma_softmax_ce_opt_fwd / _bwd).  Kernels of their own: the four above keep their code.
+// OPT = true: the options of nn.CrossEntropyLoss (sigma_softmax_ce_opt_fwd / _bwd): class weights w, label smoothing eps,
+// a per-row loss and a per-row upstream gradient.
 //   row_loss = (1 - eps) w_y (lse - x_y) + (eps / C) (W lse - sum_c w_c x_c),   W = sum_c w_c
 //   dlogit_c = g [ (1 - eps) w_y (p_c - [c == y]) + (eps / C) (W p_c - w_c) ]
 //            = (g ((1 - eps) w_y + (eps / C) W)) p_c - [c == y] g (1 - eps) w_y - (g eps / C) w_c
-// Same two regimes, same PAD rules.  w is read through the caches, not staged in LDS: w[c] in the unrolled loops has a
-// wave-uniform index (scalar loads, hoisted out of the row loop where the registers allow), w[y] is one gather per row
-// from a table of at most a few cache lines.  HAS_W = false: w = 1, W = C, no load.
+// OPT = false (sigma_softmax_ce_fwd / _bwd and their _ld forms; the launchers pair it with HAS_W = false alone) is the
+// plain mean loss,   row_loss = lse - x_y        dlogit_c = (p_c - [c == y]) g
+// which reads none of w, eps, row_loss, row_grad.  The same four kernels serve both: the row loop, the loads, the tail
+// mask, the online max / sum, the test of the label and the zero fill exist once.  Only the two formulas are kept apart:
+// the plain one is the option one at w = 1, eps = 0 in exact arithmetic alone -- (e - 1) f and f e - f round differently
+// -- and the plain loss keeps its bits.  The backward kernels write the plain one out instead of calling a helper, and
+// take the option-only parameters last: with either changed the compiler schedules the plain kernels differently (at 40
+// and 48 classes with more registers and fewer waves).  Every pointer is a __restrict__ kernel parameter of its own:
+// as members of a struct passed by value they lose the qualifier, and the w[c] become vector loads inside the row loop.
+// w is read through the caches, not staged in LDS: w[c] in the unrolled loops has a wave-uniform index (scalar loads,
+// hoisted out of the row loop where the registers allow), w[y] is one gather per row from a table of at most a few cache
+// lines.  HAS_W = false: w = 1, W = C, no load.
 template <bool HAS_W>
 __device__ __forceinline__ float ce_w(const float* __restrict__ w, int c) { return HAS_W ? w[c] : 1.0f; }
 
@@ -342,7 +209,15 @@ __device__ __forceinline__ float ce_wx_chunk(const float* __restrict__ w, int c0
     return t;
 }
 
-// the gradient of one chunk; n as above: w is not read past it (what lands in columns >= n is overwritten by the caller)
+// the option loss of a valid row (wy = w_y, W = sum of w, inv_c = 1 / C, sx = sum of w_c x_c)
+__device__ __forceinline__ float ce_opt_row_loss(float eps, float inv_c, float wy, float W, float l, float xy, float sx) {
+    float rl = ((1.0f - eps) * wy) * (l - xy);
+    if (eps > 0.0f) rl += (eps * inv_c) * (W * l - sx);
+    return rl;
+}
+
+// the option gradient of one chunk (fp, fa, fb = the three coefficients of the last line of the formula above); n as
+// above: w is not read past it (what lands in columns >= n is overwritten by the caller)
 template <bool HAS_W>
 __device__ __forceinline__ float4 ce_opt_grad_chunk(const float* __restrict__ w, int c0, const float4& v, int n, float l, long y,
                                                     float fp, float fa, float fb) {
@@ -354,17 +229,11 @@ __device__ __forceinline__ float4 ce_opt_grad_chunk(const float* __restrict__ w,
     return o;
 }
 
-__device__ __forceinline__ float ce_opt_row_loss(float eps, float inv_c, float wy, float W, float l, float xy, float sx) {
-    float rl = ((1.0f - eps) * wy) * (l - xy);
-    if (eps > 0.0f) rl += (eps * inv_c) * (W * l - sx);
-    return rl;
-}
-
-template <bool PAD, bool HAS_W>
+template <bool PAD, bool OPT, bool HAS_W>
 __global__ void __launch_bounds__(256)
-softmax_ce_opt_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w, long rows,
-                          int nc, int ld, long ignore, float eps, float* __restrict__ lse, float* __restrict__ row_loss,
-                          float* __restrict__ partial) {
+softmax_ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w, long rows,
+                      int nc, int ld, long ignore, float eps, float* __restrict__ lse, float* __restrict__ row_loss,
+                      float* __restrict__ partial) {
     __shared__ float sh[4];
     float loss = 0.0f, den = 0.0f;
     const long stride = (long)gridDim.x * blockDim.x;
@@ -372,10 +241,10 @@ softmax_ce_opt_fwd_kernel(const float* __restrict__ logits, const int64_t* __res
     const float W = ce_weight_sum<HAS_W>(w, nc), inv_c = 1.0f / (float)nc;
     for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
         const float* __restrict__ xr = logits + r * pitch;
-        float m = kNegInf, s = 0.0f, sx = 0.0f;
+        float m = kNegInf, s = 0.0f, sx = 0.0f;        // running max and sum of exp(x - m); sum of w_c x_c
         for (int c = 0; c < nc; c += 4) {
             float4 v = *reinterpret_cast<const float4*>(xr + c);
-            if (eps > 0.0f) sx += ce_wx_chunk<HAS_W>(w, c, v, PAD ? nc - c : 4);
+            if (OPT && eps > 0.0f) sx += ce_wx_chunk<HAS_W>(w, c, v, PAD ? nc - c : 4);
             if (PAD) ce_mask_tail(v, nc - c, kNegInf);
             const float vm = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
             if (vm > m) { s *= __expf(m - vm); m = vm; }
@@ -386,24 +255,25 @@ softmax_ce_opt_fwd_kernel(const float* __restrict__ logits, const int64_t* __res
         const long y = labels[r];
         float rl = 0.0f;
         if (y != ignore && y >= 0 && y < nc) {
-            const float wy = ce_w<HAS_W>(w, (int)y);
-            rl = ce_opt_row_loss(eps, inv_c, wy, W, l, xr[y], sx);
+            const float wy = ce_w<HAS_W>(w, (int)y);   // 1 without weights: den counts the rows
+            const float xy = xr[y];
+            rl = OPT ? ce_opt_row_loss(eps, inv_c, wy, W, l, xy, sx) : l - xy;
             loss += rl;
             den += wy;
         }
-        if (row_loss) row_loss[r] = rl;
+        if (OPT && row_loss) row_loss[r] = rl;
     }
     const float tl = block_sum(loss, sh);
     const float td = block_sum(den, sh);
     if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = td; }
 }
 
-template <bool PAD, bool HAS_W>
+template <bool PAD, bool OPT, bool HAS_W>
 __global__ void __launch_bounds__(256)
-softmax_ce_opt_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w,
-                          const float* __restrict__ lse, const float* __restrict__ scale, const float* __restrict__ row_grad, long rows,
-                          int nc, int ld, long ignore, float eps, float* __restrict__ dlogits) {
-    const float sc = scale ? scale[0] : 0.0f;
+softmax_ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ lse,
+                      const float* __restrict__ scale, long rows, int nc, int ld, long ignore, float* __restrict__ dlogits,
+                      const float* __restrict__ w, const float* __restrict__ row_grad, float eps) {
+    const float sc = (!OPT || scale) ? scale[0] : 0.0f;
     const long stride = (long)gridDim.x * blockDim.x;
     const int pitch = PAD ? ld : nc;
     const float W = ce_weight_sum<HAS_W>(w, nc), b = eps * (1.0f / (float)nc);
@@ -413,13 +283,21 @@ softmax_ce_opt_bwd_kernel(const float* __restrict__ logits, const int64_t* __res
         const long y = labels[r];
         const bool on = y != ignore && y >= 0 && y < nc;
         const float l = lse[r];
-        const float f = on ? (scale ? sc : row_grad[r]) : 0.0f;
+        const float g = on ? ((!OPT || scale) ? sc : row_grad[r]) : 0.0f;          // the row's upstream gradient
         const float a = (1.0f - eps) * (on ? ce_w<HAS_W>(w, (int)y) : 0.0f);
-        const float fp = f * (a + b * W), fa = f * a, fb = f * b;
+        const float fp = g * (a + b * W), fa = g * a, fb = g * b;          // OPT only
         int c = 0;
         for (; c < nc; c += 4) {
             const float4 v = *reinterpret_cast<const float4*>(xr + c);
-            float4 o = ce_opt_grad_chunk<HAS_W>(w, c, v, PAD ? nc - c : 4, l, y, fp, fa, fb);
+            float4 o;
+            if constexpr (OPT) {
+                o = ce_opt_grad_chunk<HAS_W>(w, c, v, PAD ? nc - c : 4, l, y, fp, fa, fb);
+            } else {
+                o.x = (__expf(v.x - l) - (y == c ? 1.0f : 0.0f)) * g;
+                o.y = (__expf(v.y - l) - (y == c + 1 ? 1.0f : 0.0f)) * g;
+                o.z = (__expf(v.z - l) - (y == c + 2 ? 1.0f : 0.0f)) * g;
+                o.w = (__expf(v.w - l) - (y == c + 3 ? 1.0f : 0.0f)) * g;
+            }
             if (PAD) ce_mask_tail(o, nc - c, 0.0f);
             *reinterpret_cast<float4*>(dr + c) = o;
         }
@@ -428,11 +306,14 @@ softmax_ce_opt_bwd_kernel(const float* __restrict__ logits, const int64_t* __res
     }
 }
 
-template <int NC4, bool PAD, bool HAS_W>
+// Same kernels with the row (NC4 float4) held in registers: every load of a row is issued before the first use.  The
+// generic kernels above walk the row with one load in flight per thread (1.2 TB/s on 8 x 480 x 640 x 40).  PAD = true:
+// NC4 = ceil(nc / 4) chunks hold the valid columns.
+template <int NC4, bool PAD, bool OPT, bool HAS_W>
 __global__ void __launch_bounds__(256)
-softmax_ce_opt_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w, long rows,
-                              int nc_, int ld, long ignore, float eps, float* __restrict__ lse, float* __restrict__ row_loss,
-                              float* __restrict__ partial) {
+softmax_ce_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w, long rows,
+                          int nc_, int ld, long ignore, float eps, float* __restrict__ lse, float* __restrict__ row_loss,
+                          float* __restrict__ partial) {
     __shared__ float sh[4];
     const int nc = PAD ? nc_ : NC4 * 4;
     const int pitch = PAD ? ld : NC4 * 4;
@@ -446,7 +327,7 @@ softmax_ce_opt_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* _
         for (int c = 0; c < NC4; ++c) v[c] = xr[c];
         const long y = labels[r];
         float sx = 0.0f;
-        if (eps > 0.0f) {
+        if (OPT && eps > 0.0f) {
 #pragma unroll
             for (int c = 0; c < NC4; ++c) sx += ce_wx_chunk<HAS_W>(w, 4 * c, v[c], (PAD && c == NC4 - 1) ? nc - 4 * c : 4);
         }
@@ -464,26 +345,26 @@ softmax_ce_opt_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* _
         lse[r] = l;
         float rl = 0.0f;
         if (y != ignore && y >= 0 && y < nc) {
-            const float wy = ce_w<HAS_W>(w, (int)y);
-            rl = ce_opt_row_loss(eps, inv_c, wy, W, l, xy, sx);
+            const float wy = ce_w<HAS_W>(w, (int)y);   // 1 without weights: den counts the rows
+            rl = OPT ? ce_opt_row_loss(eps, inv_c, wy, W, l, xy, sx) : l - xy;
             loss += rl;
             den += wy;
         }
-        if (row_loss) row_loss[r] = rl;
+        if (OPT && row_loss) row_loss[r] = rl;
     }
     const float tl = block_sum(loss, sh);
     const float td = block_sum(den, sh);
     if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = td; }
 }
 
-template <int NC4, bool PAD, bool HAS_W>
+template <int NC4, bool PAD, bool OPT, bool HAS_W>
 __global__ void __launch_bounds__(256)
-softmax_ce_opt_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w,
-                              const float* __restrict__ lse, const float* __restrict__ scale, const float* __restrict__ row_grad, long rows,
-                              int nc_, int ld, long ignore, float eps, float* __restrict__ dlogits) {
+softmax_ce_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ lse,
+                          const float* __restrict__ scale, long rows, int nc_, int ld, long ignore, float* __restrict__ dlogits,
+                          const float* __restrict__ w, const float* __restrict__ row_grad, float eps) {
     const int nc = PAD ? nc_ : NC4 * 4;
     const int pitch = PAD ? ld : NC4 * 4;
-    const float sc = scale ? scale[0] : 0.0f;
+    const float sc = (!OPT || scale) ? scale[0] : 0.0f;
     const long stride = (long)gridDim.x * blockDim.x;
     const float W = ce_weight_sum<HAS_W>(w, nc), b = eps * (1.0f / (float)nc);
     for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
@@ -495,13 +376,21 @@ softmax_ce_opt_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* _
         const long y = labels[r];
         const float l = lse[r];
         const bool on = y != ignore && y >= 0 && y < nc;
-        const float f = on ? (scale ? sc : row_grad[r]) : 0.0f;
+        const float g = on ? ((!OPT || scale) ? sc : row_grad[r]) : 0.0f;          // the row's upstream gradient
         const float a = (1.0f - eps) * (on ? ce_w<HAS_W>(w, (int)y) : 0.0f);
-        const float fp = f * (a + b * W), fa = f * a, fb = f * b;
+        const float fp = g * (a + b * W), fa = g * a, fb = g * b;          // OPT only
 #pragma unroll
         for (int c = 0; c < NC4; ++c) {
             const bool tail = PAD && c == NC4 - 1;
-            float4 o = ce_opt_grad_chunk<HAS_W>(w, 4 * c, v[c], tail ? nc - 4 * c : 4, l, y, fp, fa, fb);
+            float4 o;
+            if constexpr (OPT) {
+                o = ce_opt_grad_chunk<HAS_W>(w, 4 * c, v[c], tail ? nc - 4 * c : 4, l, y, fp, fa, fb);
+            } else {
+                o.x = (__expf(v[c].x - l) - (y == 4 * c ? 1.0f : 0.0f)) * g;
+                o.y = (__expf(v[c].y - l) - (y == 4 * c + 1 ? 1.0f : 0.0f)) * g;
+                o.z = (__expf(v[c].z - l) - (y == 4 * c + 2 ? 1.0f : 0.0f)) * g;
+                o.w = (__expf(v[c].w - l) - (y == 4 * c + 3 ? 1.0f : 0.0f)) * g;
+            }
             if (tail) ce_mask_tail(o, nc - 4 * c, 0.0f);
             dr[c] = o;
         }
@@ -509,6 +398,30 @@ softmax_ce_opt_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* _
             for (int c = NC4; c < (ld >> 2); ++c) dr[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
 }
+
+// NC4 = ceil(classes / 4) chunks held in registers up to 64 classes
+template <typename F>
+bool dispatch_nc4(int nc4, F&& f) {
+    switch (nc4) {
+#define SIGMA_NC4(N) case N: f(std::integral_constant<int, N>()); return true;
+        SIGMA_NC4(1) SIGMA_NC4(2) SIGMA_NC4(3) SIGMA_NC4(4) SIGMA_NC4(5) SIGMA_NC4(6) SIGMA_NC4(7) SIGMA_NC4(8)
+        SIGMA_NC4(9) SIGMA_NC4(10) SIGMA_NC4(11) SIGMA_NC4(12) SIGMA_NC4(13) SIGMA_NC4(14) SIGMA_NC4(15) SIGMA_NC4(16)
+#undef SIGMA_NC4
+        default: return false;
+    }
+}
+
+// the two flags of a loss launch as types
+template <typename F>
+void dispatch_flags(bool pad, bool has_w, F&& f) {
+    if (pad && has_w) f(std::true_type(), std::true_type());
+    else if (pad) f(std::true_type(), std::false_type());
+    else if (has_w) f(std::false_type(), std::true_type());
+    else f(std::false_type(), std::false_type());
+}
+
+bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // ---- backward of  y = a + x * s  with a per-channel s on channels-last rows (CVSSDecoderBlock, vmamba.py:1800-1805) ------
 // dx = dy * s and ds += sum over rows of dy * x, one pass over dy and x.  A thread keeps ONE 16-byte column chunk for the
@@ -593,6 +506,49 @@ unsigned stream_grid(long work_items) {
 
 int done() { return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH; }
 
+// the arguments of the plain loss as the launchers take them: no option set (the backward only reads lse)
+sigma_ce_opt_params ce_plain(const float* logits, const int64_t* labels, int64_t rows, int32_t classes, int32_t ld, int64_t ignore_index,
+                             const float* lse, float* partial, const float* scale, float* dlogits) {
+    sigma_ce_opt_params p = {};
+    p.rows = rows; p.classes = classes; p.ld = ld; p.ignore_index = ignore_index;
+    p.logits = logits; p.labels = labels; p.lse = const_cast<float*>(lse);
+    p.partial = partial; p.scale = scale; p.dlogits = dlogits;
+    return p;
+}
+
+// One launcher per direction for the plain (OPT = false: weight, row_loss, row_grad NULL and label_smoothing 0 in `p`) and
+// the option loss; the arguments are checked by the entry points.  Rows of up to 64 classes go to the register kernels.
+template <bool OPT>
+int ce_launch_fwd(const sigma_ce_opt_params& p, void* stream) {
+    // every one of the SIGMA_CE_BLOCKS workgroups writes its (loss, weight or count) pair, rows or not: the caller adds them up
+    const dim3 grid(SIGMA_CE_BLOCKS), block(256);
+    dispatch_flags(p.ld != p.classes, OPT && p.weight != nullptr, [&](auto pad, auto has_w) {
+        constexpr bool PAD = decltype(pad)::value, HAS_W = OPT && decltype(has_w)::value;
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, static_cast<hipStream_t>(stream), p.logits, p.labels, p.weight, (long)p.rows,
+                               (int)p.classes, (int)p.ld, (long)p.ignore_index, p.label_smoothing, p.lse, p.row_loss, p.partial);
+        };
+        if (!dispatch_nc4((p.classes + 3) / 4, [&](auto n) { launch(softmax_ce_fwd_reg_kernel<decltype(n)::value, PAD, OPT, HAS_W>); }))
+            launch(softmax_ce_fwd_kernel<PAD, OPT, HAS_W>);
+    });
+    return done();
+}
+
+template <bool OPT>
+int ce_launch_bwd(const sigma_ce_opt_params& p, void* stream) {
+    const dim3 grid(stream_grid(p.rows)), block(256);
+    dispatch_flags(p.ld != p.classes, OPT && p.weight != nullptr, [&](auto pad, auto has_w) {
+        constexpr bool PAD = decltype(pad)::value, HAS_W = OPT && decltype(has_w)::value;
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, static_cast<hipStream_t>(stream), p.logits, p.labels, p.lse, p.scale, (long)p.rows,
+                               (int)p.classes, (int)p.ld, (long)p.ignore_index, p.dlogits, p.weight, p.row_grad, p.label_smoothing);
+        };
+        if (!dispatch_nc4((p.classes + 3) / 4, [&](auto n) { launch(softmax_ce_bwd_reg_kernel<decltype(n)::value, PAD, OPT, HAS_W>); }))
+            launch(softmax_ce_bwd_kernel<PAD, OPT, HAS_W>);
+    });
+    return done();
+}
+
 }  // namespace
 }  // namespace sigma
 
@@ -635,8 +591,7 @@ int sigma_colscale_bwd(const float* dy, const float* x, const float* scale, floa
     if (!dy || !x || !scale || !dx || !dscale) return SIGMA_OPS_ERR_ARG;
     if (!sigma::al16(dy) || !sigma::al16(x) || !sigma::al16(scale) || !sigma::al16(dx)) return SIGMA_OPS_ERR_ARG;
     const int slots = 256 / (channels / 4);
-    long grid = (rows + slots - 1) / slots;
-    if (grid > 512) grid = 512;                       // two workgroups per CU: every block ends with C atomics on the same C addresses
+    const long grid = sigma::colscale_grid((long)rows, channels);
     hipLaunchKernelGGL(sigma::colscale_bwd_kernel, dim3((unsigned)grid), dim3(256), (size_t)slots * channels * sizeof(float),
                        static_cast<hipStream_t>(stream), dy, x, scale, dx, dscale, (long)rows, (int)channels);
     return sigma::done();
@@ -696,22 +651,8 @@ int sigma_softmax_ce_fwd_ld(const float* logits, const int64_t* labels, int64_t 
     if (rows < 0 || classes < 1 || ld % 4 != 0 || ld < classes) return SIGMA_OPS_ERR_ARG;
     if (!partial) return SIGMA_OPS_ERR_ARG;
     if (rows > 0 && (!logits || !labels || !lse || !sigma::al16(logits))) return SIGMA_OPS_ERR_ARG;
-    // every one of the SIGMA_CE_BLOCKS workgroups writes its (sum, count) pair, rows or not: the caller adds them up
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid(SIGMA_CE_BLOCKS), block(256);
-    const long nrows = (long)rows, ignore = (long)ignore_index;
-    const int nc = (int)classes, pitch = (int)ld;
-    const bool pad = ld != classes;
-    const bool reg = sigma::dispatch_nc4((classes + 3) / 4, [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        if (pad) hipLaunchKernelGGL((sigma::softmax_ce_fwd_reg_kernel<N, true>), grid, block, 0, s, logits, labels, nrows, nc, pitch, ignore, lse, partial);
-        else hipLaunchKernelGGL((sigma::softmax_ce_fwd_reg_kernel<N, false>), grid, block, 0, s, logits, labels, nrows, nc, pitch, ignore, lse, partial);
-    });
-    if (!reg) {
-        if (pad) hipLaunchKernelGGL(sigma::softmax_ce_fwd_kernel<true>, grid, block, 0, s, logits, labels, nrows, nc, pitch, ignore, lse, partial);
-        else hipLaunchKernelGGL(sigma::softmax_ce_fwd_kernel<false>, grid, block, 0, s, logits, labels, nrows, nc, pitch, ignore, lse, partial);
-    }
-    return sigma::done();
+    const sigma_ce_opt_params p = sigma::ce_plain(logits, labels, rows, classes, ld, ignore_index, lse, partial, nullptr, nullptr);
+    return sigma::ce_launch_fwd<false>(p, stream);
 }
 
 int sigma_softmax_ce_bwd_ld(const float* logits, const int64_t* labels, const float* lse, const float* scale, int64_t rows, int32_t classes,
@@ -719,21 +660,8 @@ int sigma_softmax_ce_bwd_ld(const float* logits, const int64_t* labels, const fl
     if (rows < 0 || classes < 1 || ld % 4 != 0 || ld < classes) return SIGMA_OPS_ERR_ARG;
     if (rows == 0) return SIGMA_OPS_OK;
     if (!logits || !labels || !lse || !scale || !dlogits || !sigma::al16(logits) || !sigma::al16(dlogits)) return SIGMA_OPS_ERR_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid(sigma::stream_grid(rows)), block(256);
-    const long nrows = (long)rows, ignore = (long)ignore_index;
-    const int nc = (int)classes, pitch = (int)ld;
-    const bool pad = ld != classes;
-    const bool reg = sigma::dispatch_nc4((classes + 3) / 4, [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        if (pad) hipLaunchKernelGGL((sigma::softmax_ce_bwd_reg_kernel<N, true>), grid, block, 0, s, logits, labels, lse, scale, nrows, nc, pitch, ignore, dlogits);
-        else hipLaunchKernelGGL((sigma::softmax_ce_bwd_reg_kernel<N, false>), grid, block, 0, s, logits, labels, lse, scale, nrows, nc, pitch, ignore, dlogits);
-    });
-    if (!reg) {
-        if (pad) hipLaunchKernelGGL(sigma::softmax_ce_bwd_kernel<true>, grid, block, 0, s, logits, labels, lse, scale, nrows, nc, pitch, ignore, dlogits);
-        else hipLaunchKernelGGL(sigma::softmax_ce_bwd_kernel<false>, grid, block, 0, s, logits, labels, lse, scale, nrows, nc, pitch, ignore, dlogits);
-    }
-    return sigma::done();
+    const sigma_ce_opt_params p = sigma::ce_plain(logits, labels, rows, classes, ld, ignore_index, lse, nullptr, scale, dlogits);
+    return sigma::ce_launch_bwd<false>(p, stream);
 }
 
 // everything sigma_softmax_ce_opt_fwd and _bwd check alike, before any launch
@@ -750,30 +678,7 @@ int sigma_softmax_ce_opt_fwd(const sigma_ce_opt_params* p, void* stream) {
     if (const int rc = ce_opt_check(p)) return rc;
     if (!p->partial) return SIGMA_OPS_ERR_ARG;
     if (p->rows > 0 && (!p->logits || !p->labels || !p->lse || !sigma::al16(p->logits))) return SIGMA_OPS_ERR_ARG;
-    // every one of the SIGMA_CE_BLOCKS workgroups writes its (loss, weight) pair, rows or not: the caller adds them up
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid(SIGMA_CE_BLOCKS), block(256);
-    const long nrows = (long)p->rows, ignore = (long)p->ignore_index;
-    const int nc = (int)p->classes, pitch = (int)p->ld;
-    const bool pad = p->ld != p->classes, hw = p->weight != nullptr;
-    const float eps = p->label_smoothing;
-#define SIGMA_CE_OPT_FWD(K) hipLaunchKernelGGL(K, grid, block, 0, s, p->logits, p->labels, p->weight, nrows, nc, pitch, ignore, eps, \
-                                               p->lse, p->row_loss, p->partial)
-    const bool reg = sigma::dispatch_nc4((nc + 3) / 4, [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        if (pad && hw) SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_reg_kernel<N, true, true>));
-        else if (pad) SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_reg_kernel<N, true, false>));
-        else if (hw) SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_reg_kernel<N, false, true>));
-        else SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_reg_kernel<N, false, false>));
-    });
-    if (!reg) {
-        if (pad && hw) SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_kernel<true, true>));
-        else if (pad) SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_kernel<true, false>));
-        else if (hw) SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_kernel<false, true>));
-        else SIGMA_CE_OPT_FWD((sigma::softmax_ce_opt_fwd_kernel<false, false>));
-    }
-#undef SIGMA_CE_OPT_FWD
-    return sigma::done();
+    return sigma::ce_launch_fwd<true>(*p, stream);
 }
 
 int sigma_softmax_ce_opt_bwd(const sigma_ce_opt_params* p, void* stream) {
@@ -781,29 +686,7 @@ int sigma_softmax_ce_opt_bwd(const sigma_ce_opt_params* p, void* stream) {
     if ((p->scale != nullptr) == (p->row_grad != nullptr)) return SIGMA_OPS_ERR_ARG;      // one of them, not both
     if (p->rows == 0) return SIGMA_OPS_OK;
     if (!p->logits || !p->labels || !p->lse || !p->dlogits || !sigma::al16(p->logits) || !sigma::al16(p->dlogits)) return SIGMA_OPS_ERR_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid(sigma::stream_grid(p->rows)), block(256);
-    const long nrows = (long)p->rows, ignore = (long)p->ignore_index;
-    const int nc = (int)p->classes, pitch = (int)p->ld;
-    const bool pad = p->ld != p->classes, hw = p->weight != nullptr;
-    const float eps = p->label_smoothing;
-#define SIGMA_CE_OPT_BWD(K) hipLaunchKernelGGL(K, grid, block, 0, s, p->logits, p->labels, p->weight, p->lse, p->scale, p->row_grad, nrows, \
-                                               nc, pitch, ignore, eps, p->dlogits)
-    const bool reg = sigma::dispatch_nc4((nc + 3) / 4, [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        if (pad && hw) SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_reg_kernel<N, true, true>));
-        else if (pad) SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_reg_kernel<N, true, false>));
-        else if (hw) SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_reg_kernel<N, false, true>));
-        else SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_reg_kernel<N, false, false>));
-    });
-    if (!reg) {
-        if (pad && hw) SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_kernel<true, true>));
-        else if (pad) SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_kernel<true, false>));
-        else if (hw) SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_kernel<false, true>));
-        else SIGMA_CE_OPT_BWD((sigma::softmax_ce_opt_bwd_kernel<false, false>));
-    }
-#undef SIGMA_CE_OPT_BWD
-    return sigma::done();
+    return sigma::ce_launch_bwd<true>(*p, stream);
 }
 
 }  // extern "C"

@@ -7,7 +7,8 @@
 ``cross_entropy``  nn.CrossEntropyLoss(reduction='mean', ignore_index) of models/builder.py:146-166 on the CHANNELS-LAST
                    logits the classifier GEMM produces (MambaDecoder.up_x4): log-sum-exp + loss in one pass, gradient in
                    one pass, no (B, classes, H, W) copy.  Class weights, label smoothing and the reductions 'sum' /
-                   'none' run on kernels of their own (``SoftmaxCEOptFn``).
+                   'none' run on the OPT instantiations of the same kernels, through entry points of their own
+                   (``SoftmaxCEOptFn``).
 
 GPU tensors only (no fallback); the callers keep the torch formulation for everything these kernels do not take.
 """
