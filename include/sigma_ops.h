@@ -44,8 +44,9 @@ typedef struct sigma_dwconv_params {
                               image in column-major order (index w*H + h)                          */
     /* backward */
     const float *g2;       /* (B, n_orders, d, H*W) gradient of out2                                      */
-    float *gpre;           /* (B, d, H, W) scratch: gradient w.r.t. the pre-activation (planes that fit
-                              LDS keep it there: then not written)                                  */
+    float *gpre;           /* (B, d, H, W) scratch: gradient w.r.t. the pre-activation, fully written -- except for
+                              planes with 2 (H + 2) ((W + 2) | 1) 4 <= 48 KiB: one workgroup owns such a plane and
+                              keeps gpre in LDS between its two stencils, gpre is then not touched        */
     float *dweight;        /* (d, 1, 3, 3) ACCUMULATED into (caller zeroes); WRITTEN with
                               SIGMA_DWCONV_DETERMINISTIC                                            */
     float *dbias;          /* (d) ACCUMULATED into, or NULL; WRITTEN with SIGMA_DWCONV_DETERMINISTIC */
@@ -68,7 +69,9 @@ typedef struct sigma_dwconv_params {
 int sigma_dwconv3x3_silu_fwd(const sigma_dwconv_params *params, void *stream);
 int sigma_dwconv3x3_silu_bwd(const sigma_dwconv_params *params, void *stream);
 /* Scratch bytes of sigma_dwconv3x3_silu_bwd: 0 without SIGMA_DWCONV_DETERMINISTIC, else 40 bytes per channel and
- * workgroup slot (batch x 32x32 tiles, or batch when a plane fits LDS); negative = invalid params. */
+ * workgroup slot (batch x 32x32 tiles, or batch for a plane below the 48 KiB line of gpre); negative = invalid params.
+ * The kernels work on strips of <= 32 rows x <= 128 columns (csrc/dwconv.hip), never more of them than 32x32 tiles: they
+ * fill the first batch x strips slots and the fixed-order pass reads only those. */
 int64_t sigma_dwconv3x3_silu_bwd_workspace_bytes(const sigma_dwconv_params *params);
 
 /*   sigma_cross_merge_nhwc / sigma_cross_split_nhwc
