@@ -218,6 +218,51 @@ typedef struct sigma_ce_opt_params {
 int sigma_softmax_ce_opt_fwd(const sigma_ce_opt_params *params, void *stream);
 int sigma_softmax_ce_opt_bwd(const sigma_ce_opt_params *params, void *stream);
 
+/*   sigma_ohem_select / sigma_ohem_workspace_bytes  (csrc/ohem.hip; additions only, the ABI version stays 13)
+ *       the pixel selection of ProbOhemCrossEntropy2d (utils/loss_opr.py:137-187) on the device, in the negative-log
+ *       domain.  `nll` holds lse - x_y per row, as sigma_softmax_ce_opt_fwd writes it to row_loss with weight = NULL and
+ *       label_smoothing = 0 (0 at ignored rows).  A row is VALID when label != ignore_index and 0 <= label < classes.
+ *         no mining   min_kept <= 0, num_valid == 0 or min_kept > num_valid:  tau = -inf, every valid row is kept
+ *                     (thresh is not applied, as in the reference)
+ *         mining      tau = min((float)(0.0 - log((double)thresh)), the min_kept-th LARGEST nll of the valid rows);
+ *                     a valid row is kept unless nll < tau: ties at tau are all kept, and so is a NaN key
+ *       Out:  tau[0];  counts[0] = num_valid, counts[1] = kept rows;  mined[r] = labels[r] if the row is kept, else
+ *       ignore_index.  With `weight` / `row_loss` / `partial` (each optional) also what sigma_softmax_ce_opt_fwd would
+ *       give for (mined, weight, label_smoothing = 0) without reading the logits again: row_loss[r] = w_y nll[r] at kept
+ *       rows and 0 elsewhere, partial = SIGMA_CE_BLOCKS pairs (sum of row_loss, sum of w_y) in that kernel's row order --
+ *       the same bits.
+ *       The k-th value comes from a radix select, four 8-bit digits of the order-preserving unsigned image of the keys:
+ *       per pass up to SIGMA_OHEM_HIST_BLOCKS workgroups count into LDS and add their non-empty bins to a global
+ *       histogram with integer atomics (exact in any order: the result is bitwise reproducible), one workgroup picks the
+ *       digit.  Ten kernels, all launched unconditionally; nothing is read back, so the call can be
+ *       captured into a graph and the branch taken at replay is the data's.  The logits are not touched: each pass
+ *       reads 4-byte keys and 8-byte labels.
+ *       rows == 0 is a success that writes tau = -inf and counts = (0, 0) (nll, labels, mined may be NULL then).
+ *       SIGMA_OPS_ERR_ARG before any launch: a NULL params, tau, counts or workspace, a NULL nll / labels / mined with
+ *       rows > 0, a misaligned pointer (floats 4, labels / mined / counts 8, workspace 16 bytes), workspace_bytes below
+ *       sigma_ohem_workspace_bytes(rows), thresh outside (0, 1] (NaN included), classes < 1, rows < 0 or above 2^31 - 1.
+ *       The size query answers a multiple of 16 that does not shrink as rows grow, and -1 for rows it refuses.         */
+#define SIGMA_OHEM_HIST_BLOCKS 512
+typedef struct sigma_ohem_params {
+    int64_t rows;
+    int64_t ignore_index;
+    int32_t classes;               /* labels outside [0, classes) count as ignored                           */
+    float thresh;                  /* in (0, 1]                                                              */
+    int64_t min_kept;
+    const float *nll;              /* (rows) keys                                                            */
+    const int64_t *labels;         /* (rows)                                                                 */
+    int64_t *mined;                /* out (rows)                                                             */
+    float *tau;                    /* out (1)                                                                */
+    int64_t *counts;               /* out (2): num_valid, kept                                               */
+    void *workspace;               /* 16-byte aligned scratch; its contents on entry do not matter           */
+    int64_t workspace_bytes;
+    const float *weight;           /* (classes) or NULL = all ones                                           */
+    float *row_loss;               /* out (rows), or NULL                                                    */
+    float *partial;                /* out: SIGMA_CE_BLOCKS pairs, or NULL                                    */
+} sigma_ohem_params;
+int sigma_ohem_select(const sigma_ohem_params *params, void *stream);
+int64_t sigma_ohem_workspace_bytes(int64_t rows);
+
 /*   sigma_colscale_bwd
  *       backward of  y = a + x * scale with a per-channel `scale` on contiguous channels-last rows (rows, C): the residual
  *       of the decoder block, x * scale1 + op(norm1(x)) and x * scale2 + conv_blk(norm2(x)) (vmamba.py:1800-1805):

@@ -172,7 +172,19 @@ class CeOptParams(ctypes.Structure):
     ]
 
 
+class OhemParams(ctypes.Structure):
+    """mirror of sigma_ohem_params (include/sigma_ops.h)"""
+    _fields_ = [
+        ("rows", ctypes.c_int64), ("ignore_index", ctypes.c_int64), ("classes", ctypes.c_int32), ("thresh", ctypes.c_float),
+        ("min_kept", ctypes.c_int64),
+        ("nll", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("mined", ctypes.c_void_p), ("tau", ctypes.c_void_p),
+        ("counts", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
+        ("weight", ctypes.c_void_p), ("row_loss", ctypes.c_void_p), ("partial", ctypes.c_void_p),
+    ]
+
+
 SIGMA_CE_BLOCKS = 1024      # include/sigma_ops.h
+SIGMA_OHEM_HIST_BLOCKS = 512        # include/sigma_ops.h
 SIGMA_SEG_LDS_HIST_BYTES = 32768    # include/sigma_ops.h
 
 # every symbol include/sigma_gemm.h declares
@@ -189,9 +201,9 @@ OPS_SYMBOLS = ("sigma_dwconv3x3_silu_fwd", "sigma_dwconv3x3_silu_bwd", "sigma_cr
                "sigma_pair_sum_add", "sigma_upsample2x_nhwc", "sigma_plane_pool", "sigma_plane_scale",
                "sigma_plane_dot", "sigma_plane_gate_bwd", "sigma_softmax_ce_fwd", "sigma_softmax_ce_bwd", "sigma_softmax_ce_fwd_ld",
                "sigma_softmax_ce_bwd_ld", "sigma_softmax_ce_opt_fwd", "sigma_softmax_ce_opt_bwd", "sigma_colscale_bwd",
-               "sigma_colscale_bwd_ws", "sigma_seg_accumulate", "sigma_seg_argmax_confusion")
+               "sigma_colscale_bwd_ws", "sigma_seg_accumulate", "sigma_seg_argmax_confusion", "sigma_ohem_select")
 # the size queries include/sigma_ops.h declares (int64_t results)
-OPS_AUX_SYMBOLS = ("sigma_dwconv3x3_silu_bwd_workspace_bytes", "sigma_colscale_bwd_workspace_bytes")
+OPS_AUX_SYMBOLS = ("sigma_dwconv3x3_silu_bwd_workspace_bytes", "sigma_colscale_bwd_workspace_bytes", "sigma_ohem_workspace_bytes")
 
 # every symbol include/sigma_scan.h declares; tests check the library exports all of them
 EXPORTED_SYMBOLS = (
@@ -285,6 +297,8 @@ def load() -> ctypes.CDLL:
                            ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
         elif name in ("sigma_softmax_ce_opt_fwd", "sigma_softmax_ce_opt_bwd"):
             fn.argtypes = [P(CeOptParams), ctypes.c_void_p]
+        elif name == "sigma_ohem_select":
+            fn.argtypes = [P(OhemParams), ctypes.c_void_p]
         elif name == "sigma_seg_accumulate":
             fn.argtypes = [P(SegAccumulateParams), ctypes.c_void_p]
         elif name == "sigma_seg_argmax_confusion":
@@ -298,6 +312,8 @@ def load() -> ctypes.CDLL:
     lib.sigma_dwconv3x3_silu_bwd_workspace_bytes.restype = ctypes.c_int64
     lib.sigma_colscale_bwd_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32]
     lib.sigma_colscale_bwd_workspace_bytes.restype = ctypes.c_int64
+    lib.sigma_ohem_workspace_bytes.argtypes = [ctypes.c_int64]
+    lib.sigma_ohem_workspace_bytes.restype = ctypes.c_int64
     for name in GEMM_SYMBOLS:
         fn = getattr(lib, name)
         fn.argtypes = [P(GemmParams), ctypes.c_void_p]

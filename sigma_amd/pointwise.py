@@ -9,6 +9,10 @@
                    one pass, no (B, classes, H, W) copy.  Class weights, label smoothing and the reductions 'sum' /
                    'none' run on the OPT instantiations of the same kernels, through entry points of their own
                    (``SoftmaxCEOptFn``).
+``ohem_cross_entropy``  ProbOhemCrossEntropy2d (utils/loss_opr.py:137-187) on the same logits: the forward of the option
+                   kernels writes the per-pixel loss, csrc/ohem.hip selects the hard pixels on the device (a radix select
+                   of the min_kept-th largest loss; no host round trip) and the backward of the option kernels runs on
+                   the mined labels (``OhemCEFn``).
 
 GPU tensors only (no fallback); the callers keep the torch formulation for everything these kernels do not take.
 """
@@ -247,6 +251,11 @@ class SoftmaxCEOptFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        return (SoftmaxCEOptFn._dlogits(ctx, g),) + (None,) * 7
+
+    @staticmethod
+    def _dlogits(ctx, g):
+        """sigma_softmax_ce_opt_bwd on what the forward saved (``OhemCEFn`` saves its mined labels in the labels' place)"""
         lib = _capi.load()
         logits2, labels, lse, tot, weight = ctx.saved_tensors
         rows, nc = logits2.shape
@@ -269,10 +278,81 @@ class SoftmaxCEOptFn(torch.autograd.Function):
             # as SoftmaxCEFn: the classifier's backward claims the whole padded buffer (_handoff.py)
             offer_padded_grad_buffer(full)
             full = full[:, :nc]
-        return full, None, None, None, None, None, None, None
+        return full
+
+
+def ohem_stages(logits2, labels, weight, ignore_index, ld, thresh, min_kept, want_row_loss=False):
+    """The forward of the OHEM route on (rows, classes) logits at pitch `ld`, no autograd: (1) the unweighted
+    sigma_softmax_ce_opt_fwd with a row loss -- lse and nll = lse - x_y, the one pass over the logits; (2) sigma_ohem_select
+    on nll: tau, (num_valid, kept), the mined labels and, from nll, `weight` and the mined labels alone, the row losses
+    and the SIGMA_CE_BLOCKS partial pairs of the weighted cross entropy on them.  Returns a dict of device tensors;
+    nothing is read back."""
+    lib = _capi.load()
+    rows, nc = logits2.shape
+    dev = logits2.device
+    f32 = dict(device=dev, dtype=torch.float32)
+    lse, nll = torch.empty(rows, **f32), torch.empty(rows, **f32)
+    partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, **f32)
+    mined = torch.empty(rows, device=dev, dtype=torch.int64)
+    tau = torch.empty(1, **f32)
+    counts = torch.empty(2, device=dev, dtype=torch.int64)
+    row_loss = torch.empty(rows, **f32) if want_row_loss else None
+    ws_bytes = int(lib.sigma_ohem_workspace_bytes(rows))
+    if ws_bytes < 0:
+        raise RuntimeError(f"ohem: {rows} rows are more than the selection takes (2^31 - 1)")
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    p = SoftmaxCEOptFn._params(logits2, labels, None, lse, ignore_index, ld, 0.0)
+    p.row_loss, p.partial = nll.data_ptr(), partial.data_ptr()
+    q = _capi.OhemParams()
+    q.rows, q.ignore_index, q.classes, q.thresh, q.min_kept = rows, int(ignore_index), nc, float(thresh), int(min_kept)
+    q.nll, q.labels, q.mined, q.tau, q.counts = nll.data_ptr(), labels.data_ptr(), mined.data_ptr(), tau.data_ptr(), counts.data_ptr()
+    q.workspace, q.workspace_bytes = ws.data_ptr(), ws_bytes
+    q.weight = weight.data_ptr() if weight is not None else None
+    q.row_loss = row_loss.data_ptr() if row_loss is not None else None
+    q.partial = partial.data_ptr()                          # overwritten: the unweighted sums of stage 1 are not used
+    with torch.cuda.device(dev):
+        _capi.check(lib.sigma_softmax_ce_opt_fwd(ctypes.byref(p), _stream()), "softmax_ce_opt_fwd (ohem nll)")
+        _capi.check(lib.sigma_ohem_select(ctypes.byref(q), _stream()), "ohem_select")
+    return dict(lse=lse, nll=nll, mined=mined, tau=tau, counts=counts, partial=partial, row_loss=row_loss)
+
+
+class OhemCEFn(torch.autograd.Function):
+    """ProbOhemCrossEntropy2d on the rows of ``SoftmaxCEOptFn``: ``ohem_stages`` in the forward (the logits are read once;
+    the selection carries no gradient), sigma_softmax_ce_opt_bwd on the mined labels with the saved lse in the backward.
+    Reductions and the zero denominator as in ``SoftmaxCEOptFn``."""
+
+    @staticmethod
+    def forward(ctx, logits2, labels, weight, ignore_index, ld, thresh, min_kept, reduction, out_shape):
+        r = ohem_stages(logits2, labels, weight, ignore_index, ld, thresh, min_kept, want_row_loss=reduction == "none")
+        tot = r["partial"].sum(0)
+        ctx.save_for_backward(logits2, r["mined"], r["lse"], tot, weight)
+        ctx.ignore_index, ctx.ld, ctx.eps, ctx.reduction = int(ignore_index), ld, 0.0, reduction
+        if reduction == "none":
+            return r["row_loss"].view(out_shape)
+        return tot[0] / tot[1] if reduction == "mean" else tot[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return (SoftmaxCEOptFn._dlogits(ctx, g),) + (None,) * 8
 
 
 CE_REDUCTIONS = ("mean", "sum", "none")
+
+
+def _channels_last_rows(logits, label):
+    """(nhwc, classes, ld) when `logits` (B, classes, H, W) is the view of fp32 channels-last rows on the GPU that the loss
+    kernels take -- contiguous (B, H, W, classes) with classes % 4 == 0, or the first `classes` columns of a (B, H, W, ld)
+    buffer with ld % 4 == 0 -- and `label` is a GPU tensor of its (B, H, W); else None"""
+    if not (logits.is_cuda and logits.dtype == torch.float32 and label.is_cuda):
+        return None
+    nhwc = logits.permute(0, 2, 3, 1)
+    nc = nhwc.shape[-1]
+    if nhwc.data_ptr() % 16 != 0 or tuple(label.shape) != tuple(nhwc.shape[:3]):
+        return None
+    ld = nc if nhwc.is_contiguous() else _row_pitch(nhwc)
+    if ld is None or ld % 4 != 0 or ld < nc:
+        return None
+    return nhwc, nc, ld
 
 
 def criterion_route(criterion, device, classes, any_float_weight=False):
@@ -315,15 +395,10 @@ def cross_entropy(criterion, logits: torch.Tensor, label: torch.Tensor):
         return None
     if criterion.reduction == "none" and criterion.weight is None and float(getattr(criterion, "label_smoothing", 0.0)) == 0.0:
         return None                                        # declined before the option kernels existed, and still (see above)
-    if not (logits.is_cuda and logits.dtype == torch.float32 and label.is_cuda):
+    rows_view = _channels_last_rows(logits, label)
+    if rows_view is None:
         return None
-    nhwc = logits.permute(0, 2, 3, 1)
-    nc = nhwc.shape[-1]
-    if nhwc.data_ptr() % 16 != 0 or tuple(label.shape) != tuple(nhwc.shape[:3]):
-        return None
-    ld = nc if nhwc.is_contiguous() else _row_pitch(nhwc)
-    if ld is None or ld % 4 != 0 or ld < nc:
-        return None
+    nhwc, nc, ld = rows_view
     lab = label.long().contiguous()
     if route == "plain":
         return SoftmaxCEFn.apply(nhwc.reshape(-1, nc), lab.view(-1), criterion.ignore_index, ld)      # reshape: a view at either pitch
@@ -334,6 +409,33 @@ def cross_entropy(criterion, logits: torch.Tensor, label: torch.Tensor):
             return None
     return SoftmaxCEOptFn.apply(nhwc.reshape(-1, nc), lab.view(-1), w, criterion.ignore_index, ld, float(criterion.label_smoothing),
                                 criterion.reduction, tuple(label.shape))
+
+
+def ohem_cross_entropy(logits: torch.Tensor, label: torch.Tensor, ignore_index, thresh, min_kept, weight=None, reduction="mean"):
+    """ProbOhemCrossEntropy2d(ignore_index, reduction, thresh, min_kept) with optional class weights on the channels-last
+    logits ``cross_entropy`` takes (same layouts, same treatment of labels outside [0, classes)), or None when this path
+    does not apply: another layout, dtype or device, a weight that is not a 1-D fp32 tensor of `classes` elements on the
+    logits' device, a thresh outside (0, 1].  The hard pixels are selected on the device (sigma_ohem_select): no host
+    synchronisation, so the step can be captured into a graph whichever branch the data take.  'none' returns (B, H, W)
+    with zeros at dropped pixels; 'mean' divides by the summed weights of the KEPT pixels."""
+    if not (logits.dim() == 4 and label.dim() == 3) or reduction not in CE_REDUCTIONS:
+        return None
+    if not 0.0 < float(thresh) <= 1.0:
+        return None
+    rows_view = _channels_last_rows(logits, label)
+    if rows_view is None:
+        return None
+    nhwc, nc, ld = rows_view
+    w = weight
+    if w is not None:
+        if not (torch.is_tensor(w) and w.dtype == torch.float32 and w.dim() == 1 and w.numel() == nc and w.device == logits.device):
+            return None
+        w = w.detach().contiguous()
+        if w.data_ptr() % 4 != 0:
+            return None
+    lab = label.long().contiguous()
+    return OhemCEFn.apply(nhwc.reshape(-1, nc), lab.view(-1), w, int(ignore_index), ld, float(thresh), int(min_kept), reduction,
+                          tuple(label.shape))
 
 
 def cross_entropy_deterministic(criterion, logits: torch.Tensor, label: torch.Tensor):

@@ -1,0 +1,2 @@
+"""Stand-ins for pieces of the reference's ``utils/`` that do not run as they are on the torch this project uses:
+``loss_opr.ProbOhemCrossEntropy2d``."""

@@ -20,6 +20,17 @@ time the criterion's options on the same four shapes.  Route A there is the beha
 kernels: the head as in route B and the criterion itself, ``crit(out, label)``, on the (B, nc, H, W) view.  Route B is
 ``pointwise.cross_entropy`` (sigma_softmax_ce_opt_fwd / _bwd).  A third route P, the PLAIN criterion on route B's code,
 alternates with them: option and plain kernels move the same algorithmic bytes, so B / P is what the options cost.
+
+    python tools/head_bench.py --ohem --out profiles/loss_ohem_mi355x.jsonl
+
+``--ohem`` times the LOSS alone (forward + backward on given channels-last logits, no classifier) at 8 x 480 x 640 pixels
+for (classes, pitch) = (40, 40) and (9, 12), min_kept = pixels / 16, thresh = 0.7, three routes alternating in one process:
+a  the plain mean cross entropy on the kernels (``pointwise.cross_entropy``, the code of the commit before OHEM);
+b  ``utils.loss_opr.ProbOhemCrossEntropy2d`` on the kernel route (``pointwise.ohem_cross_entropy``: one forward pass over
+   the logits that also writes the per-pixel loss, the radix select, the backward on the mined labels);
+c  the torch composition a user would otherwise write on the (B, nc, H, W) view: softmax, gather, sort, masked labels,
+   F.cross_entropy.
+b - a is what the selection costs; ``ohem_rows_bytes`` is what its rows-sized passes move, next to the logits' traffic of a.
 """
 import argparse
 import json
@@ -92,6 +103,77 @@ def route_bytes(M, C, nc):
     return {"A": kern if nc % 4 == 0 else crit, "B": kern}
 
 
+OHEM_SHAPES = [(8, 480, 640, 40, 40), (8, 480, 640, 9, 12)]
+
+
+def ohem_torch_composition(out, label, thresh, min_kept):
+    """route c: ProbOhemCrossEntropy2d written with torch ops on the (B, nc, H, W) view"""
+    import torch.nn.functional as F
+    with torch.no_grad():
+        valid = label != IGNORE
+        safe = torch.where(valid, label, torch.zeros_like(label))
+        p = F.softmax(out, dim=1).gather(1, safe.unsqueeze(1)).squeeze(1)
+        p = torch.where(valid, p, torch.ones_like(p))
+        q = torch.sort(p.reshape(-1)).values[min_kept - 1]
+        keep = valid & (p <= torch.clamp(q, min=thresh))
+        mined = torch.where(keep, label, torch.full_like(label, IGNORE))
+    return F.cross_entropy(out, mined, ignore_index=IGNORE)
+
+
+def ohem_rows_bytes(M):
+    """bytes of the rows-sized passes route b adds to route a: the per-pixel loss written by the forward (4), four counting
+    passes reading keys and labels (4 x 12), the final pass reading both and writing the mined labels (12 + 8)"""
+    return M * (4 + 4 * 12 + 20)
+
+
+def ohem_main(a, dev):
+    from sigma_amd.pointwise import cross_entropy
+    from sigma_amd.utils.loss_opr import ProbOhemCrossEntropy2d
+    plain = nn.CrossEntropyLoss(reduction="mean", ignore_index=IGNORE)
+    lines = []
+    for B, H, W, nc, ld in OHEM_SHAPES:
+        M = B * H * W
+        thresh, min_kept = 0.7, M // 16
+        g = torch.Generator().manual_seed(1234)
+        buf = torch.zeros(B, H, W, ld)
+        buf[..., :nc] = torch.randn(B, H, W, nc, generator=g) * 3.0
+        buf = buf.to(dev).requires_grad_()
+        label = torch.randint(0, nc, (B, H, W), generator=g)
+        label[torch.rand(B, H, W, generator=g) < 0.1] = IGNORE
+        label = label.to(dev)
+        ohem = ProbOhemCrossEntropy2d(IGNORE, "mean", thresh, min_kept)
+        view = lambda: buf[..., :nc].permute(0, 3, 1, 2)
+        routes = {"a": lambda: cross_entropy(plain, view(), label), "b": lambda: ohem(view(), label),
+                  "c": lambda: ohem_torch_composition(view(), label, thresh, min_kept)}
+        times = {k: [] for k in routes}
+        losses = {}
+        for i in range(a.warmup + a.reps):
+            for k, fn in routes.items():
+                buf.grad = None
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                loss = fn()
+                loss.backward()
+                t1.record()
+                t1.synchronize()
+                if i >= a.warmup:
+                    times[k].append(t0.elapsed_time(t1))
+                losses[k] = float(loss.detach())
+        assert type(ohem(view(), label).grad_fn).__name__.startswith("OhemCEFn")
+        sp = {k: spread(v) for k, v in times.items()}
+        line = {"mode": "ohem", "shape": [B, H, W], "classes": nc, "ld": ld, "thresh": thresh, "min_kept": min_kept, "reps": a.reps,
+                "warmup": a.warmup, "a_plain_kernels": sp["a"], "b_ohem_kernels": sp["b"], "c_ohem_torch": sp["c"],
+                "b_minus_a_ms": round(sp["b"]["median_ms"] - sp["a"]["median_ms"], 4),
+                "b_over_c": round(sp["b"]["median_ms"] / sp["c"]["median_ms"], 4), "loss_a": losses["a"], "loss_b": losses["b"],
+                "loss_c": losses["c"], "ohem_rows_bytes": ohem_rows_bytes(M), "logits_bytes_a": 3 * 4 * M * ld,
+                "device": torch.cuda.get_device_name(0)}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del buf, label
+        torch.cuda.empty_cache()
+    return lines
+
+
 def spread(ts):
     q = statistics.quantiles(ts, n=4)
     return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4),
@@ -104,10 +186,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default="")
     ap.add_argument("--criterion", nargs="+", default=["plain"], choices=["plain", "weight", "weight_eps"])
+    ap.add_argument("--ohem", action="store_true", help="time the OHEM loss against the plain loss and a torch composition")
     a = ap.parse_args()
     if a.reps < 30:
         ap.error("at least 30 repetitions")
     dev = torch.device("cuda", 0)
+    if a.ohem:
+        lines = ohem_main(a, dev)
+        if a.out:
+            with open(a.out, "w") as f:
+                for line in lines:
+                    f.write(json.dumps(line) + "\n")
+        return
     plain = nn.CrossEntropyLoss(reduction="mean", ignore_index=IGNORE)
     lines = []
     for B, H, W, C, nc, kind in [(*shape, kind) for kind in a.criterion for shape in SHAPES]:
