@@ -218,6 +218,25 @@ typedef struct sigma_ce_opt_params {
 int sigma_softmax_ce_opt_fwd(const sigma_ce_opt_params *params, void *stream);
 int sigma_softmax_ce_opt_bwd(const sigma_ce_opt_params *params, void *stream);
 
+/*   sigma_softmax_focal_fwd / sigma_softmax_focal_bwd  (additions only: the struct above as it is, the ABI version stays 13)
+ *       The focal loss of FocalLoss2d (utils/loss_opr.py:12-23) on the same rows, with a run-time exponent `gamma`.  With
+ *       p = softmax(logits[r]), y = labels[r], q = 1 - p_y, nll = lse - x_y and "valid" as above:
+ *           fwd : lse[r] as above;
+ *                 row_loss[r] = w_y q^gamma nll  for valid rows, 0 otherwise (written when row_loss != NULL);
+ *                 partial = SIGMA_CE_BLOCKS pairs (sum of row_loss, sum of w_y), workgroups and row order of the option
+ *                 kernels.  'mean' = sum of partial[2k] over sum of partial[2k+1], what nn.NLLLoss(weight, 'mean') gives.
+ *           bwd : dlogits[r][c] = g_r w_y m (p_c - [c == y]),   m = q^gamma + gamma q^(gamma - 1) p_y nll,
+ *                 for valid rows, exact zeros otherwise and in columns [classes, ld); q, nll and m are formed again from
+ *                 the row and the saved lse.  g_r = scale[0] or row_grad[r] as above.  No atomics, nothing read back.
+ *       gamma is 0 (the cross entropy) or >= 1; gamma = 2, the reference's fixed exponent, is a plain square.  For
+ *       0 < gamma < 1 the factor q^(gamma - 1) is unbounded as p_y -> 1 and fp32 rows cannot bound the error of m: refused.
+ *       Where q = 0 in fp32 (the label's logit dominates) the row's loss is exactly 0 and, for gamma > 0, its gradient row
+ *       is exact zeros; for gamma = 0 it is the cross-entropy row.
+ *       SIGMA_OPS_ERR_ARG before any launch: everything the option entry points refuse, label_smoothing != 0, gamma NaN,
+ *       infinite, negative or in (0, 1).                                                                            */
+int sigma_softmax_focal_fwd(const sigma_ce_opt_params *params, float gamma, void *stream);
+int sigma_softmax_focal_bwd(const sigma_ce_opt_params *params, float gamma, void *stream);
+
 /*   sigma_ohem_select / sigma_ohem_workspace_bytes  (csrc/ohem.hip; additions only, the ABI version stays 13)
  *       the pixel selection of ProbOhemCrossEntropy2d (utils/loss_opr.py:137-187) on the device, in the negative-log
  *       domain.  `nll` holds lse - x_y per row, as sigma_softmax_ce_opt_fwd writes it to row_loss with weight = NULL and

@@ -201,7 +201,8 @@ OPS_SYMBOLS = ("sigma_dwconv3x3_silu_fwd", "sigma_dwconv3x3_silu_bwd", "sigma_cr
                "sigma_pair_sum_add", "sigma_upsample2x_nhwc", "sigma_plane_pool", "sigma_plane_scale",
                "sigma_plane_dot", "sigma_plane_gate_bwd", "sigma_softmax_ce_fwd", "sigma_softmax_ce_bwd", "sigma_softmax_ce_fwd_ld",
                "sigma_softmax_ce_bwd_ld", "sigma_softmax_ce_opt_fwd", "sigma_softmax_ce_opt_bwd", "sigma_colscale_bwd",
-               "sigma_colscale_bwd_ws", "sigma_seg_accumulate", "sigma_seg_argmax_confusion", "sigma_ohem_select")
+               "sigma_colscale_bwd_ws", "sigma_seg_accumulate", "sigma_seg_argmax_confusion", "sigma_ohem_select",
+               "sigma_softmax_focal_fwd", "sigma_softmax_focal_bwd")
 # the size queries include/sigma_ops.h declares (int64_t results)
 OPS_AUX_SYMBOLS = ("sigma_dwconv3x3_silu_bwd_workspace_bytes", "sigma_colscale_bwd_workspace_bytes", "sigma_ohem_workspace_bytes")
 
@@ -297,6 +298,8 @@ def load() -> ctypes.CDLL:
                            ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
         elif name in ("sigma_softmax_ce_opt_fwd", "sigma_softmax_ce_opt_bwd"):
             fn.argtypes = [P(CeOptParams), ctypes.c_void_p]
+        elif name in ("sigma_softmax_focal_fwd", "sigma_softmax_focal_bwd"):
+            fn.argtypes = [P(CeOptParams), ctypes.c_float, ctypes.c_void_p]
         elif name == "sigma_ohem_select":
             fn.argtypes = [P(OhemParams), ctypes.c_void_p]
         elif name == "sigma_seg_accumulate":

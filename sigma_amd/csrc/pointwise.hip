@@ -17,6 +17,8 @@
 //   softmax_ce_bwd  dlogit = (exp(logit - lse) - [class == label]) * scale, zero rows for ignored pixels
 //                   Both as OPT instantiations too, for the sigma_softmax_ce_opt entry points: class weights, label
 //                   smoothing, a per-row loss ('none') and a per-row upstream gradient, every option of nn.CrossEntropyLoss
+//   softmax_focal_fwd / _bwd   the focal loss w_y (1 - p_y)^gamma (lse - x_y) of FocalLoss2d (utils/loss_opr.py:12-23) on
+//                   the same rows: the cross-entropy passes with one per-row factor, kernels of their own
 //
 // All of them are bound by HBM: bytes per element 4 (pool), 8 (scale, dot), 12 (gate_bwd), 4 / 8 (loss fwd / bwd).
 #include <hip/hip_runtime.h>
@@ -399,6 +401,183 @@ softmax_ce_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* __res
     }
 }
 
+// ---- focal loss (FocalLoss2d, utils/loss_opr.py:12-23) on the same rows: sigma_softmax_focal_fwd / _bwd ---------------
+// With d = x_y - lse <= 0, nll = -d, p_y = exp(d), q = 1 - p_y and the exponent gamma (0 or >= 1, a run-time float):
+//   row_loss = w_y q^gamma nll
+//   dlogit_c = g w_y m (p_c - [c == y]),     m = q^gamma + gamma q^(gamma - 1) p_y nll
+// i.e. the plain gradient with g w_y m in the place of g: m is formed per row from the row the kernel holds anyway.
+// Kernels of their own, not one more flag on the kernels above (their parameter lists are not touched, see there).
+// gamma = 2 is a square, gamma = 1 needs no power, anything else one exp(log) per row for t = q^(gamma - 1); q^gamma is
+// t q throughout.  q = 0 (p_y rounds to 1): gamma > 0 gives loss 0 and m = 0 by a branch, never 0 * inf; gamma = 0 is the
+// cross-entropy row (q^0 = 1, m = 1).  The forward and the backward form d, q and t with the same code from the same lse.
+struct FocalRow { float qg, m; };          // q^gamma and m
+
+__device__ __forceinline__ FocalRow focal_row(float d, float gamma) {
+    FocalRow f;
+    if (gamma == 0.0f) { f.qg = 1.0f; f.m = 1.0f; return f; }
+    const float py = __expf(d);
+    const float q = fmaxf(1.0f - py, 0.0f);
+    if (!(q > 0.0f)) { f.qg = 0.0f; f.m = 0.0f; return f; }
+    const float t = gamma == 2.0f ? q : gamma == 1.0f ? 1.0f : __expf((gamma - 1.0f) * __logf(q));
+    f.qg = t * q;
+    f.m = f.qg + ((gamma * t) * py) * (0.0f - d);
+    return f;
+}
+
+template <bool PAD, bool HAS_W>
+__global__ void __launch_bounds__(256)
+softmax_focal_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w, long rows,
+                         int nc, int ld, long ignore, float gamma, float* __restrict__ lse, float* __restrict__ row_loss,
+                         float* __restrict__ partial) {
+    __shared__ float sh[4];
+    float loss = 0.0f, den = 0.0f;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const int pitch = PAD ? ld : nc;
+    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
+        const float* __restrict__ xr = logits + r * pitch;
+        float m = kNegInf, s = 0.0f;
+        for (int c = 0; c < nc; c += 4) {
+            float4 v = *reinterpret_cast<const float4*>(xr + c);
+            if (PAD) ce_mask_tail(v, nc - c, kNegInf);
+            const float vm = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+            if (vm > m) { s *= __expf(m - vm); m = vm; }
+            s += (__expf(v.x - m) + __expf(v.y - m)) + (__expf(v.z - m) + __expf(v.w - m));
+        }
+        const float l = m + __logf(s);
+        lse[r] = l;
+        const long y = labels[r];
+        float rl = 0.0f;
+        if (y != ignore && y >= 0 && y < nc) {
+            const float wy = ce_w<HAS_W>(w, (int)y);
+            const float d = fminf(xr[y] - l, 0.0f);
+            rl = wy * (focal_row(d, gamma).qg * (0.0f - d));
+            loss += rl;
+            den += wy;
+        }
+        if (row_loss) row_loss[r] = rl;
+    }
+    const float tl = block_sum(loss, sh);
+    const float td = block_sum(den, sh);
+    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = td; }
+}
+
+template <bool PAD, bool HAS_W>
+__global__ void __launch_bounds__(256)
+softmax_focal_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ lse,
+                         const float* __restrict__ scale, const float* __restrict__ row_grad, const float* __restrict__ w, long rows,
+                         int nc, int ld, long ignore, float gamma, float* __restrict__ dlogits) {
+    const float sc = scale ? scale[0] : 0.0f;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const int pitch = PAD ? ld : nc;
+    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
+        const float* __restrict__ xr = logits + r * pitch;
+        float* __restrict__ dr = dlogits + r * pitch;
+        const long y = labels[r];
+        const bool on = y != ignore && y >= 0 && y < nc;
+        const float l = lse[r];
+        float f = 0.0f;                                    // g w_y m, zero for ignored rows
+        if (on) f = ((scale ? sc : row_grad[r]) * ce_w<HAS_W>(w, (int)y)) * focal_row(fminf(xr[y] - l, 0.0f), gamma).m;
+        int c = 0;
+        for (; c < nc; c += 4) {
+            const float4 v = *reinterpret_cast<const float4*>(xr + c);
+            float4 o;
+            o.x = (__expf(v.x - l) - (y == c ? 1.0f : 0.0f)) * f;
+            o.y = (__expf(v.y - l) - (y == c + 1 ? 1.0f : 0.0f)) * f;
+            o.z = (__expf(v.z - l) - (y == c + 2 ? 1.0f : 0.0f)) * f;
+            o.w = (__expf(v.w - l) - (y == c + 3 ? 1.0f : 0.0f)) * f;
+            if (PAD) ce_mask_tail(o, nc - c, 0.0f);
+            *reinterpret_cast<float4*>(dr + c) = o;
+        }
+        if (PAD)
+            for (; c < ld; c += 4) *reinterpret_cast<float4*>(dr + c) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
+
+// the label's logit out of a row held in registers (0 where y is no column of it: the caller tests the label)
+template <int NC4>
+__device__ __forceinline__ float ce_pick(const float4 (&v)[NC4], long y) {
+    float xy = 0.0f;
+#pragma unroll
+    for (int c = 0; c < NC4; ++c)
+        xy = (y == 4 * c) ? v[c].x : (y == 4 * c + 1) ? v[c].y : (y == 4 * c + 2) ? v[c].z : (y == 4 * c + 3) ? v[c].w : xy;
+    return xy;
+}
+
+template <int NC4, bool PAD, bool HAS_W>
+__global__ void __launch_bounds__(256)
+softmax_focal_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w, long rows,
+                             int nc_, int ld, long ignore, float gamma, float* __restrict__ lse, float* __restrict__ row_loss,
+                             float* __restrict__ partial) {
+    __shared__ float sh[4];
+    const int nc = PAD ? nc_ : NC4 * 4;
+    const int pitch = PAD ? ld : NC4 * 4;
+    float loss = 0.0f, den = 0.0f;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
+        const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * pitch);
+        float4 v[NC4];
+#pragma unroll
+        for (int c = 0; c < NC4; ++c) v[c] = xr[c];
+        const long y = labels[r];
+        if (PAD) ce_mask_tail(v[NC4 - 1], nc - 4 * (NC4 - 1), kNegInf);
+        float m = kNegInf;
+#pragma unroll
+        for (int c = 0; c < NC4; ++c) m = fmaxf(m, fmaxf(fmaxf(v[c].x, v[c].y), fmaxf(v[c].z, v[c].w)));
+        float s = 0.0f;
+#pragma unroll
+        for (int c = 0; c < NC4; ++c) s += (__expf(v[c].x - m) + __expf(v[c].y - m)) + (__expf(v[c].z - m) + __expf(v[c].w - m));
+        const float l = m + __logf(s);
+        lse[r] = l;
+        float rl = 0.0f;
+        if (y != ignore && y >= 0 && y < nc) {
+            const float wy = ce_w<HAS_W>(w, (int)y);
+            const float d = fminf(ce_pick<NC4>(v, y) - l, 0.0f);
+            rl = wy * (focal_row(d, gamma).qg * (0.0f - d));
+            loss += rl;
+            den += wy;
+        }
+        if (row_loss) row_loss[r] = rl;
+    }
+    const float tl = block_sum(loss, sh);
+    const float td = block_sum(den, sh);
+    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = td; }
+}
+
+template <int NC4, bool PAD, bool HAS_W>
+__global__ void __launch_bounds__(256)
+softmax_focal_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ lse,
+                             const float* __restrict__ scale, const float* __restrict__ row_grad, const float* __restrict__ w, long rows,
+                             int nc_, int ld, long ignore, float gamma, float* __restrict__ dlogits) {
+    const int nc = PAD ? nc_ : NC4 * 4;
+    const int pitch = PAD ? ld : NC4 * 4;
+    const float sc = scale ? scale[0] : 0.0f;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
+        const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * pitch);
+        float4* __restrict__ dr = reinterpret_cast<float4*>(dlogits + r * pitch);
+        float4 v[NC4];
+#pragma unroll
+        for (int c = 0; c < NC4; ++c) v[c] = xr[c];
+        const long y = labels[r];
+        const float l = lse[r];
+        const bool on = y != ignore && y >= 0 && y < nc;
+        float f = 0.0f;                                    // g w_y m, zero for ignored rows
+        if (on) f = ((scale ? sc : row_grad[r]) * ce_w<HAS_W>(w, (int)y)) * focal_row(fminf(ce_pick<NC4>(v, y) - l, 0.0f), gamma).m;
+#pragma unroll
+        for (int c = 0; c < NC4; ++c) {
+            float4 o;
+            o.x = (__expf(v[c].x - l) - (y == 4 * c ? 1.0f : 0.0f)) * f;
+            o.y = (__expf(v[c].y - l) - (y == 4 * c + 1 ? 1.0f : 0.0f)) * f;
+            o.z = (__expf(v[c].z - l) - (y == 4 * c + 2 ? 1.0f : 0.0f)) * f;
+            o.w = (__expf(v[c].w - l) - (y == 4 * c + 3 ? 1.0f : 0.0f)) * f;
+            if (PAD && c == NC4 - 1) ce_mask_tail(o, nc - 4 * c, 0.0f);
+            dr[c] = o;
+        }
+        if (PAD)
+            for (int c = NC4; c < (ld >> 2); ++c) dr[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
+
 // NC4 = ceil(classes / 4) chunks held in registers up to 64 classes
 template <typename F>
 bool dispatch_nc4(int nc4, F&& f) {
@@ -549,6 +728,35 @@ int ce_launch_bwd(const sigma_ce_opt_params& p, void* stream) {
     return done();
 }
 
+// the focal launchers: grids, flags and regimes of the launchers above
+int focal_launch_fwd(const sigma_ce_opt_params& p, float gamma, void* stream) {
+    const dim3 grid(SIGMA_CE_BLOCKS), block(256);
+    dispatch_flags(p.ld != p.classes, p.weight != nullptr, [&](auto pad, auto has_w) {
+        constexpr bool PAD = decltype(pad)::value, HAS_W = decltype(has_w)::value;
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, static_cast<hipStream_t>(stream), p.logits, p.labels, p.weight, (long)p.rows,
+                               (int)p.classes, (int)p.ld, (long)p.ignore_index, gamma, p.lse, p.row_loss, p.partial);
+        };
+        if (!dispatch_nc4((p.classes + 3) / 4, [&](auto n) { launch(softmax_focal_fwd_reg_kernel<decltype(n)::value, PAD, HAS_W>); }))
+            launch(softmax_focal_fwd_kernel<PAD, HAS_W>);
+    });
+    return done();
+}
+
+int focal_launch_bwd(const sigma_ce_opt_params& p, float gamma, void* stream) {
+    const dim3 grid(stream_grid(p.rows)), block(256);
+    dispatch_flags(p.ld != p.classes, p.weight != nullptr, [&](auto pad, auto has_w) {
+        constexpr bool PAD = decltype(pad)::value, HAS_W = decltype(has_w)::value;
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, static_cast<hipStream_t>(stream), p.logits, p.labels, p.lse, p.scale, p.row_grad,
+                               p.weight, (long)p.rows, (int)p.classes, (int)p.ld, (long)p.ignore_index, gamma, p.dlogits);
+        };
+        if (!dispatch_nc4((p.classes + 3) / 4, [&](auto n) { launch(softmax_focal_bwd_reg_kernel<decltype(n)::value, PAD, HAS_W>); }))
+            launch(softmax_focal_bwd_kernel<PAD, HAS_W>);
+    });
+    return done();
+}
+
 }  // namespace
 }  // namespace sigma
 
@@ -687,6 +895,29 @@ int sigma_softmax_ce_opt_bwd(const sigma_ce_opt_params* p, void* stream) {
     if (p->rows == 0) return SIGMA_OPS_OK;
     if (!p->logits || !p->labels || !p->lse || !p->dlogits || !sigma::al16(p->logits) || !sigma::al16(p->dlogits)) return SIGMA_OPS_ERR_ARG;
     return sigma::ce_launch_bwd<true>(*p, stream);
+}
+
+// what the focal entry points refuse on top of ce_opt_check: smoothing, and an exponent that is NaN, negative or in (0, 1)
+static int focal_check(const sigma_ce_opt_params* p, float gamma) {
+    if (const int rc = ce_opt_check(p)) return rc;
+    if (p->label_smoothing != 0.0f) return SIGMA_OPS_ERR_ARG;
+    if (!(gamma == 0.0f || (gamma >= 1.0f && gamma <= 3.0e38f))) return SIGMA_OPS_ERR_ARG;      // NaN and inf fail both
+    return SIGMA_OPS_OK;
+}
+
+int sigma_softmax_focal_fwd(const sigma_ce_opt_params* p, float gamma, void* stream) {
+    if (const int rc = focal_check(p, gamma)) return rc;
+    if (!p->partial) return SIGMA_OPS_ERR_ARG;
+    if (p->rows > 0 && (!p->logits || !p->labels || !p->lse || !sigma::al16(p->logits))) return SIGMA_OPS_ERR_ARG;
+    return sigma::focal_launch_fwd(*p, gamma, stream);
+}
+
+int sigma_softmax_focal_bwd(const sigma_ce_opt_params* p, float gamma, void* stream) {
+    if (const int rc = focal_check(p, gamma)) return rc;
+    if ((p->scale != nullptr) == (p->row_grad != nullptr)) return SIGMA_OPS_ERR_ARG;      // one of them, not both
+    if (p->rows == 0) return SIGMA_OPS_OK;
+    if (!p->logits || !p->labels || !p->lse || !p->dlogits || !sigma::al16(p->logits) || !sigma::al16(p->dlogits)) return SIGMA_OPS_ERR_ARG;
+    return sigma::focal_launch_bwd(*p, gamma, stream);
 }
 
 }  // extern "C"

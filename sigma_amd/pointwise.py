@@ -14,6 +14,9 @@
                    of the min_kept-th largest loss; no host round trip) and the backward of the option kernels runs on
                    the mined labels (``OhemCEFn``).
 
+``focal_cross_entropy``  FocalLoss2d (utils/loss_opr.py:12-23) with a run-time exponent on the same logits: the two
+                   cross-entropy passes with one per-row factor (``SoftmaxFocalFn``, sigma_softmax_focal_fwd / _bwd).
+
 GPU tensors only (no fallback); the callers keep the torch formulation for everything these kernels do not take.
 """
 from __future__ import annotations
@@ -254,8 +257,9 @@ class SoftmaxCEOptFn(torch.autograd.Function):
         return (SoftmaxCEOptFn._dlogits(ctx, g),) + (None,) * 7
 
     @staticmethod
-    def _dlogits(ctx, g):
-        """sigma_softmax_ce_opt_bwd on what the forward saved (``OhemCEFn`` saves its mined labels in the labels' place)"""
+    def _dlogits(ctx, g, focal_gamma=None):
+        """sigma_softmax_ce_opt_bwd on what the forward saved (``OhemCEFn`` saves its mined labels in the labels' place);
+        with `focal_gamma` sigma_softmax_focal_bwd (``SoftmaxFocalFn``: same arguments, same buffers)"""
         lib = _capi.load()
         logits2, labels, lse, tot, weight = ctx.saved_tensors
         rows, nc = logits2.shape
@@ -273,7 +277,10 @@ class SoftmaxCEOptFn(torch.autograd.Function):
         full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
         p.dlogits = full.data_ptr()
         with torch.cuda.device(logits2.device):
-            _capi.check(lib.sigma_softmax_ce_opt_bwd(ctypes.byref(p), _stream()), "softmax_ce_opt_bwd")
+            if focal_gamma is None:
+                _capi.check(lib.sigma_softmax_ce_opt_bwd(ctypes.byref(p), _stream()), "softmax_ce_opt_bwd")
+            else:
+                _capi.check(lib.sigma_softmax_focal_bwd(ctypes.byref(p), focal_gamma, _stream()), "softmax_focal_bwd")
         if ld != nc:
             # as SoftmaxCEFn: the classifier's backward claims the whole padded buffer (_handoff.py)
             offer_padded_grad_buffer(full)
@@ -334,6 +341,36 @@ class OhemCEFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return (SoftmaxCEOptFn._dlogits(ctx, g),) + (None,) * 8
+
+
+class SoftmaxFocalFn(torch.autograd.Function):
+    """FocalLoss2d on the rows of ``SoftmaxCEOptFn``: w_y (1 - p_y)^gamma (lse - x_y) per pixel (sigma_softmax_focal_fwd /
+    _bwd, either pitch; gamma = 0 or >= 1).  Reductions, the device-side 'mean', the zero denominator and the hand-off of
+    the padded gradient buffer as in ``SoftmaxCEOptFn``."""
+
+    @staticmethod
+    def forward(ctx, logits2, labels, weight, ignore_index, ld, gamma, reduction, out_shape):
+        lib = _capi.load()
+        rows = logits2.shape[0]
+        dev = logits2.device
+        lse = torch.empty(rows, device=dev, dtype=torch.float32)
+        partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=dev, dtype=torch.float32)
+        row_loss = torch.empty(rows, device=dev, dtype=torch.float32) if reduction == "none" else None
+        p = SoftmaxCEOptFn._params(logits2, labels, weight, lse, ignore_index, ld, 0.0)
+        p.partial = partial.data_ptr()
+        p.row_loss = row_loss.data_ptr() if row_loss is not None else None
+        with torch.cuda.device(dev):
+            _capi.check(lib.sigma_softmax_focal_fwd(ctypes.byref(p), float(gamma), _stream()), "softmax_focal_fwd")
+        tot = partial.sum(0)
+        ctx.save_for_backward(logits2, labels, lse, tot, weight)
+        ctx.ignore_index, ctx.ld, ctx.eps, ctx.gamma, ctx.reduction = int(ignore_index), ld, 0.0, float(gamma), reduction
+        if reduction == "none":
+            return row_loss.view(out_shape)
+        return tot[0] / tot[1] if reduction == "mean" else tot[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return (SoftmaxCEOptFn._dlogits(ctx, g, focal_gamma=ctx.gamma),) + (None,) * 7
 
 
 CE_REDUCTIONS = ("mean", "sum", "none")
@@ -411,6 +448,18 @@ def cross_entropy(criterion, logits: torch.Tensor, label: torch.Tensor):
                                 criterion.reduction, tuple(label.shape))
 
 
+def _class_weight(weight, nc, device):
+    """(True, w) with w None or the detached, contiguous weight the kernels read, or (False, None) for a weight they do
+    not take: anything but a 1-D fp32 tensor of `nc` elements on `device`, 4-byte aligned"""
+    if weight is None:
+        return True, None
+    if not (torch.is_tensor(weight) and weight.dtype == torch.float32 and weight.dim() == 1 and weight.numel() == nc
+            and weight.device == device):
+        return False, None
+    w = weight.detach().contiguous()
+    return (True, w) if w.data_ptr() % 4 == 0 else (False, None)
+
+
 def ohem_cross_entropy(logits: torch.Tensor, label: torch.Tensor, ignore_index, thresh, min_kept, weight=None, reduction="mean"):
     """ProbOhemCrossEntropy2d(ignore_index, reduction, thresh, min_kept) with optional class weights on the channels-last
     logits ``cross_entropy`` takes (same layouts, same treatment of labels outside [0, classes)), or None when this path
@@ -426,16 +475,54 @@ def ohem_cross_entropy(logits: torch.Tensor, label: torch.Tensor, ignore_index, 
     if rows_view is None:
         return None
     nhwc, nc, ld = rows_view
-    w = weight
-    if w is not None:
-        if not (torch.is_tensor(w) and w.dtype == torch.float32 and w.dim() == 1 and w.numel() == nc and w.device == logits.device):
-            return None
-        w = w.detach().contiguous()
-        if w.data_ptr() % 4 != 0:
-            return None
+    ok, w = _class_weight(weight, nc, logits.device)
+    if not ok:
+        return None
     lab = label.long().contiguous()
     return OhemCEFn.apply(nhwc.reshape(-1, nc), lab.view(-1), w, int(ignore_index), ld, float(thresh), int(min_kept), reduction,
                           tuple(label.shape))
+
+
+def focal_cross_entropy(logits: torch.Tensor, label: torch.Tensor, ignore_index, gamma, weight=None, reduction="mean"):
+    """FocalLoss2d (utils/loss_opr.py:12-23) with the exponent `gamma` -- nn.NLLLoss(weight, reduction, ignore_index) of
+    (1 - softmax)^gamma * log_softmax, i.e. w_y (1 - p_y)^gamma (lse - x_y) per pixel -- on the channels-last logits
+    ``cross_entropy`` takes (same layouts, same treatment of labels outside [0, classes)), or None when this path does not
+    apply: another layout, dtype or device, a weight the OHEM route would decline, or an exponent the kernels do not
+    take: 0 < gamma < 1 (q^(gamma - 1) is unbounded as p_y -> 1; see include/sigma_ops.h), negative, NaN or infinite.
+    'mean' divides by the summed weights of the labelled pixels on the device; 'none' returns (B, H, W)."""
+    if not (logits.dim() == 4 and label.dim() == 3) or reduction not in CE_REDUCTIONS:
+        return None
+    gamma = float(gamma)
+    if not (gamma == 0.0 or 1.0 <= gamma < float("inf")):
+        return None
+    rows_view = _channels_last_rows(logits, label)
+    if rows_view is None:
+        return None
+    nhwc, nc, ld = rows_view
+    ok, w = _class_weight(weight, nc, logits.device)
+    if not ok:
+        return None
+    lab = label.long().contiguous()
+    return SoftmaxFocalFn.apply(nhwc.reshape(-1, nc), lab.view(-1), w, int(ignore_index), ld, gamma, reduction, tuple(label.shape))
+
+
+def focal_deterministic(logits: torch.Tensor, label: torch.Tensor, ignore_index, gamma, weight=None, reduction="mean"):
+    """The focal loss where ``focal_cross_entropy`` declines and torch's nll_loss2d may not run (the deterministic flag
+    on GPU tensors): element-wise ops and fixed-order reductions only, as ``cross_entropy_deterministic`` below.  Per
+    pixel -w_y (1 - p_y)^gamma log p_y, zero at ignored pixels (labels outside [0, classes) count as ignored); 'mean'
+    divides the sum by the sum of w_y over the labelled pixels (0 / 0 = NaN when there is none).  Any gamma >= 0."""
+    nc = logits.shape[1]
+    lab = label.long()
+    valid = (lab != ignore_index) & (lab >= 0) & (lab < nc)
+    onehot = F.one_hot(torch.where(valid, lab, torch.zeros_like(lab)), nc).permute(0, 3, 1, 2).to(logits.dtype)
+    validf = valid.to(logits.dtype)
+    lsm = F.log_softmax(logits, dim=1)
+    focal = lsm if float(gamma) == 0.0 else (1.0 - F.softmax(logits, dim=1)) ** float(gamma) * lsm
+    wy = validf if weight is None else (onehot * weight.detach().to(logits.dtype).view(1, nc, 1, 1)).sum(dim=1) * validf
+    per_pixel = -(focal * onehot).sum(dim=1) * wy
+    if reduction == "none":
+        return per_pixel
+    return per_pixel.sum() / wy.sum() if reduction == "mean" else per_pixel.sum()
 
 
 def cross_entropy_deterministic(criterion, logits: torch.Tensor, label: torch.Tensor):

@@ -11,12 +11,53 @@ pixels, 1 elsewhere):
      p <= threshold: ties at the threshold are all kept.
   3. the result is nn.CrossEntropyLoss(weight, reduction, ignore_index) on the labels with every other pixel set to
      ignore_label; the selection carries no gradient.
+
+``FocalLoss2d`` under the same import name (utils/loss_opr.py:12-23): nn.NLLLoss(weight, reduction, ignore_index) of
+(1 - softmax)^e * log_softmax, per pixel w_y (1 - p_y)^e (lse - x_y).  The reference's class stores ``gamma`` and never
+reads it: its exponent is the literal 2.  Here ``exponent=None`` keeps that, a float ``exponent`` selects another one; on
+the classifier's channels-last logits the loss runs on sigma_softmax_focal_fwd / _bwd (``pointwise.focal_cross_entropy``)
+for e = 0 or e >= 1, anything else -- 0 < e < 1 included -- takes the torch formulation.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+
+class FocalLoss2d(nn.Module):
+    """``FocalLoss2d(gamma=0, weight=None, reduction='mean', ignore_index=255)`` of the reference, plus ``exponent``.
+
+    ``gamma`` is accepted and unused, as in the reference (whatever is passed, the reference raises 1 - softmax to the
+    power 2).  ``exponent=None`` reproduces that; ``exponent=<float>`` is the focal exponent actually applied.  ``weight``
+    (a list, an array or a tensor of per-class weights) is held as the reference holds it, as the fp32 weight of
+    ``self.loss = nn.NLLLoss(...)``: the state-dict key is ``loss.weight`` and ``.to(device)`` moves it."""
+
+    def __init__(self, gamma=0, weight=None, reduction='mean', ignore_index=255, exponent=None):
+        super().__init__()
+        self.gamma = gamma                      # accepted and unused, as in the reference
+        self.exponent = 2.0 if exponent is None else float(exponent)
+        if not self.exponent >= 0.0:
+            raise ValueError(f"FocalLoss2d: exponent {exponent!r} is negative or NaN")
+        if weight is not None and not torch.is_tensor(weight) and len(weight) == 0:
+            weight = None                       # the reference's `if weight:` on an empty list
+        if weight is not None:
+            weight = weight.detach().cpu() if torch.is_tensor(weight) else torch.from_numpy(np.array(weight))
+            weight = weight.float()
+        self.loss = nn.NLLLoss(weight=weight, reduction=reduction, ignore_index=ignore_index)
+
+    def forward(self, input, target):
+        from ..pointwise import focal_cross_entropy, focal_deterministic
+        target = target.long()
+        crit = self.loss
+        if input.is_cuda:
+            loss = focal_cross_entropy(input, target, crit.ignore_index, self.exponent, weight=crit.weight, reduction=crit.reduction)
+            if loss is not None:
+                return loss
+            if torch.are_deterministic_algorithms_enabled():
+                return focal_deterministic(input, target, crit.ignore_index, self.exponent, weight=crit.weight, reduction=crit.reduction)
+        return crit((1 - F.softmax(input, 1)) ** self.exponent * F.log_softmax(input, 1), target)
 
 
 class ProbOhemCrossEntropy2d(nn.Module):

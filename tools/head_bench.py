@@ -31,6 +31,16 @@ b  ``utils.loss_opr.ProbOhemCrossEntropy2d`` on the kernel route (``pointwise.oh
 c  the torch composition a user would otherwise write on the (B, nc, H, W) view: softmax, gather, sort, masked labels,
    F.cross_entropy.
 b - a is what the selection costs; ``ohem_rows_bytes`` is what its rows-sized passes move, next to the logits' traffic of a.
+
+    python tools/head_bench.py --focal --out profiles/loss_focal_mi355x.jsonl
+
+``--focal`` times the LOSS alone in the same way, on the same two shapes, three routes alternating in one process:
+a  the plain mean cross entropy on the kernels, as above;
+b  ``utils.loss_opr.FocalLoss2d`` (exponent 2) on the kernel route (``pointwise.focal_cross_entropy``: the two passes of a,
+   with one per-row factor);
+c  the torch formulation of the class on the (B, nc, H, W) view: softmax, log_softmax, the product, nll_loss.
+a and b move the same bytes, so b / a is what the per-row transcendentals cost.  Gate: b / a <= 1.10 at (40, 40), unless the
+inter-quartile range of a is itself above 10 % of its median -- then the line says so and reports the spread instead.
 """
 import argparse
 import json
@@ -174,6 +184,60 @@ def ohem_main(a, dev):
     return lines
 
 
+def focal_torch_formulation(out, label, crit):
+    """route c: FocalLoss2d.forward of the reference, exponent 2, on the (B, nc, H, W) view"""
+    import torch.nn.functional as F
+    return crit.loss((1 - F.softmax(out, 1)) ** 2 * F.log_softmax(out, 1), label)
+
+
+def focal_main(a, dev):
+    from sigma_amd.pointwise import cross_entropy
+    from sigma_amd.utils.loss_opr import FocalLoss2d
+    plain = nn.CrossEntropyLoss(reduction="mean", ignore_index=IGNORE)
+    lines = []
+    for B, H, W, nc, ld in OHEM_SHAPES:
+        g = torch.Generator().manual_seed(1234)
+        buf = torch.zeros(B, H, W, ld)
+        buf[..., :nc] = torch.randn(B, H, W, nc, generator=g) * 3.0
+        buf = buf.to(dev).requires_grad_()
+        label = torch.randint(0, nc, (B, H, W), generator=g)
+        label[torch.rand(B, H, W, generator=g) < 0.1] = IGNORE
+        label = label.to(dev)
+        focal = FocalLoss2d(ignore_index=IGNORE).to(dev)
+        view = lambda: buf[..., :nc].permute(0, 3, 1, 2)
+        routes = {"a": lambda: cross_entropy(plain, view(), label), "b": lambda: focal(view(), label),
+                  "c": lambda: focal_torch_formulation(view(), label, focal)}
+        times = {k: [] for k in routes}
+        losses = {}
+        for i in range(a.warmup + a.reps):
+            for k, fn in routes.items():
+                buf.grad = None
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                loss = fn()
+                loss.backward()
+                t1.record()
+                t1.synchronize()
+                if i >= a.warmup:
+                    times[k].append(t0.elapsed_time(t1))
+                losses[k] = float(loss.detach())
+        assert type(focal(view(), label).grad_fn).__name__.startswith("SoftmaxFocalFn")
+        sp = {k: spread(v) for k, v in times.items()}
+        ratio = sp["b"]["median_ms"] / sp["a"]["median_ms"]
+        noisy = sp["a"]["iqr_ms"] > 0.10 * sp["a"]["median_ms"]
+        line = {"mode": "focal", "shape": [B, H, W], "classes": nc, "ld": ld, "exponent": 2.0, "reps": a.reps, "warmup": a.warmup,
+                "a_plain_kernels": sp["a"], "b_focal_kernels": sp["b"], "c_focal_torch": sp["c"], "b_over_a": round(ratio, 4),
+                "b_over_c": round(sp["b"]["median_ms"] / sp["c"]["median_ms"], 4),
+                "gate_b_over_a_1p10": ("plain route too noisy: spread reported" if noisy else "pass" if ratio <= 1.10 else "above")
+                if (nc, ld) == (40, 40) else "not gated", "loss_a": losses["a"], "loss_b": losses["b"], "loss_c": losses["c"],
+                "logits_bytes": 3 * 4 * B * H * W * ld, "device": torch.cuda.get_device_name(0)}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del buf, label
+        torch.cuda.empty_cache()
+    return lines
+
+
 def spread(ts):
     q = statistics.quantiles(ts, n=4)
     return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4),
@@ -187,12 +251,13 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--criterion", nargs="+", default=["plain"], choices=["plain", "weight", "weight_eps"])
     ap.add_argument("--ohem", action="store_true", help="time the OHEM loss against the plain loss and a torch composition")
+    ap.add_argument("--focal", action="store_true", help="time the focal loss against the plain loss and the torch formulation")
     a = ap.parse_args()
     if a.reps < 30:
         ap.error("at least 30 repetitions")
     dev = torch.device("cuda", 0)
-    if a.ohem:
-        lines = ohem_main(a, dev)
+    if a.ohem or a.focal:
+        lines = ohem_main(a, dev) if a.ohem else focal_main(a, dev)
         if a.out:
             with open(a.out, "w") as f:
                 for line in lines:
