@@ -16,7 +16,7 @@
 //                counts[0] = num_valid, counts[1] = 0 to the final kernel
 //   ohem_final   tau from the full prefix; mined[r] = label or ignore_index; optionally the weighted row losses and the
 //                SIGMA_CE_BLOCKS partial (loss, weight) pairs of the cross entropy ON the mined labels, in the row -> thread
-//                order and with the block sum of softmax_ce_fwd_*kernel (pointwise.hip), so that the bits are those a second
+//                order and with the block_sum of softmax_ce_fwd_*kernel (pointwise.hip), so that the bits are those a second
 //                forward over the logits would give; the kept rows are counted with one integer atomic per workgroup
 //
 // Four counting passes over 4-byte keys and 8-byte labels and one final pass; the logits are not read.  Only integer atomics:
@@ -113,18 +113,6 @@ ohem_pick_kernel(const uint32_t* __restrict__ hist, OhemState* __restrict__ st, 
     if (pass == kOhemPasses - 1) { counts[0] = (int64_t)st->num_valid; counts[1] = 0; }
 }
 
-// block-wide sum as in pointwise.hip (result valid in thread 0)
-__device__ __forceinline__ float ohem_block_sum(float s, float* sh) {
-    s = wave_sum(s);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[w] = s;
-    __syncthreads();
-    float t = 0.0f;
-    if (threadIdx.x == 0) for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-    __syncthreads();
-    return t;
-}
-
 __global__ void __launch_bounds__(256)
 ohem_final_kernel(const float* __restrict__ nll, const int64_t* __restrict__ labels, const float* __restrict__ w, long rows, int nc,
                   long ignore, float nl_thresh, const OhemState* __restrict__ st, int64_t* __restrict__ mined,
@@ -153,8 +141,8 @@ ohem_final_kernel(const float* __restrict__ nll, const int64_t* __restrict__ lab
         if (row_loss) row_loss[r] = rl;
     }
     if (partial) {
-        const float tl = ohem_block_sum(loss, sh);
-        const float td = ohem_block_sum(den, sh);
+        const float tl = block_sum(loss, sh);
+        const float td = block_sum(den, sh);
         if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = td; }
     }
     for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o);

@@ -12,13 +12,13 @@
 //   plane_scale     y = x * s[plane]
 //   plane_dot       sum over the plane of g * x                       (gradient of the gate's pre-sigmoid input)
 //   plane_gate_bwd  dx = g * s + dmean / HW + (x == max ? dmax / count : 0)   (amax backward: ties share the gradient)
-//   softmax_ce_fwd  per pixel (a row of `classes` contiguous logits): log-sum-exp (kept for the backward) and
-//                   lse - logit[label]; per-workgroup partial (sum, count) in a fixed layout -> deterministic mean
-//   softmax_ce_bwd  dlogit = (exp(logit - lse) - [class == label]) * scale, zero rows for ignored pixels
-//                   Both as OPT instantiations too, for the sigma_softmax_ce_opt entry points: class weights, label
-//                   smoothing, a per-row loss ('none') and a per-row upstream gradient, every option of nn.CrossEntropyLoss
-//   softmax_focal_fwd / _bwd   the focal loss w_y (1 - p_y)^gamma (lse - x_y) of FocalLoss2d (utils/loss_opr.py:12-23) on
-//                   the same rows: the cross-entropy passes with one per-row factor, kernels of their own
+//   softmax_ce_fwd  per pixel (a row of `classes` contiguous logits): log-sum-exp (kept for the backward) and the row's
+//                   loss; per-workgroup partial (sum, weight or count) in a fixed layout -> deterministic mean
+//   softmax_ce_bwd  dlogit from the logits and the kept log-sum-exp, zero rows for ignored pixels
+//                   One family for three kinds of loss (enum Loss): the plain mean cross entropy lse - logit[label]; every
+//                   option of nn.CrossEntropyLoss (class weights, label smoothing, a per-row loss ('none') and a per-row
+//                   upstream gradient: the sigma_softmax_ce_opt entry points); and the focal loss w_y (1 - p_y)^gamma
+//                   (lse - x_y) of FocalLoss2d (utils/loss_opr.py:12-23: the sigma_softmax_focal entry points)
 //
 // All of them are bound by HBM: bytes per element 4 (pool), 8 (scale, dot), 12 (gate_bwd), 4 / 8 (loss fwd / bwd).
 #include <hip/hip_runtime.h>
@@ -43,18 +43,6 @@ __device__ __forceinline__ float wave_max_all(float v) {
 __device__ __forceinline__ void max_count(float v, float& m, float& c) {
     if (v > m) { m = v; c = 1.0f; }
     else if (v == m) c += 1.0f;
-}
-
-// block-wide sum of `s` (result valid in thread 0)
-__device__ __forceinline__ float block_sum(float s, float* sh) {
-    s = wave_sum(s);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[w] = s;
-    __syncthreads();
-    float t = 0.0f;
-    if (threadIdx.x == 0) for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-    __syncthreads();
-    return t;
 }
 
 __global__ void __launch_bounds__(256)
@@ -161,7 +149,7 @@ __global__ void __launch_bounds__(256) plane_gate_bwd_kernel(const GateBwdArgs a
     }
 }
 
-// ---- softmax cross entropy over rows of `nc` logits at a pitch of `ld` floats (ld % 4 == 0, ld >= nc), one thread per row
+// ---- the segmentation losses over rows of `nc` logits at a pitch of `ld` floats (ld % 4 == 0, ld >= nc), one thread per row
 // PAD = false: nc % 4 == 0 and ld == nc, the contiguous rows of sigma_softmax_ce_fwd / _bwd.  PAD = true (ld != nc):
 // only columns < nc count.  The forward reads the last 16-byte chunk that holds a valid column whole and puts
 // -inf over its tail, later chunks are not read; the backward writes exact zeros over [nc, ld), chosen by index (the pad
@@ -172,23 +160,35 @@ __device__ __forceinline__ void ce_mask_tail(float4& v, int n, float fill) {    
     if (n < 4) v.w = fill;
 }
 
-// OPT = true: the options of nn.CrossEntropyLoss (sigma_softmax_ce_opt_fwd / _bwd): class weights w, label smoothing eps,
-// a per-row loss and a per-row upstream gradient.
-//   row_loss = (1 - eps) w_y (lse - x_y) + (eps / C) (W lse - sum_c w_c x_c),   W = sum_c w_c
-//   dlogit_c = g [ (1 - eps) w_y (p_c - [c == y]) + (eps / C) (W p_c - w_c) ]
-//            = (g ((1 - eps) w_y + (eps / C) W)) p_c - [c == y] g (1 - eps) w_y - (g eps / C) w_c
-// OPT = false (sigma_softmax_ce_fwd / _bwd and their _ld forms; the launchers pair it with HAS_W = false alone) is the
-// plain mean loss,   row_loss = lse - x_y        dlogit_c = (p_c - [c == y]) g
-// which reads none of w, eps, row_loss, row_grad.  The same four kernels serve both: the row loop, the loads, the tail
-// mask, the online max / sum, the test of the label and the zero fill exist once.  Only the two formulas are kept apart:
-// the plain one is the option one at w = 1, eps = 0 in exact arithmetic alone -- (e - 1) f and f e - f round differently
-// -- and the plain loss keeps its bits.  The backward kernels write the plain one out instead of calling a helper, and
-// take the option-only parameters last: with either changed the compiler schedules the plain kernels differently (at 40
-// and 48 classes with more registers and fewer waves).  Every pointer is a __restrict__ kernel parameter of its own:
-// as members of a struct passed by value they lose the qualifier, and the w[c] become vector loads inside the row loop.
-// w is read through the caches, not staged in LDS: w[c] in the unrolled loops has a wave-uniform index (scalar loads,
-// hoisted out of the row loop where the registers allow), w[y] is one gather per row from a table of at most a few cache
-// lines.  HAS_W = false: w = 1, W = C, no load.
+// One family of four kernels -- forward / backward, walking the row or holding it in registers -- for three kinds of loss.
+// The row loop, the loads, the tail mask, the online max / sum, the test of the label, the zero fill of the pad, the
+// block sums and the partial pair exist once; a kind is the formula of a row's loss and of its gradient:
+//   kPlain  (sigma_softmax_ce_fwd / _bwd and their _ld forms; HAS_W = false alone) the mean cross entropy,
+//             row_loss = lse - x_y        dlogit_c = (p_c - [c == y]) g
+//           which reads none of w, row_loss, row_grad and the float parameter.
+//   kOpt    (sigma_softmax_ce_opt_fwd / _bwd) the options of nn.CrossEntropyLoss: class weights w, label smoothing eps,
+//           a per-row loss and a per-row upstream gradient,
+//             row_loss = (1 - eps) w_y (lse - x_y) + (eps / C) (W lse - sum_c w_c x_c),   W = sum_c w_c
+//             dlogit_c = g [ (1 - eps) w_y (p_c - [c == y]) + (eps / C) (W p_c - w_c) ]
+//                      = (g ((1 - eps) w_y + (eps / C) W)) p_c - [c == y] g (1 - eps) w_y - (g eps / C) w_c
+//   kFocal  (sigma_softmax_focal_fwd / _bwd) FocalLoss2d (utils/loss_opr.py:12-23), weights and the per-row loss and
+//           gradient as kOpt, no smoothing.  With d = x_y - lse <= 0, nll = -d, p_y = exp(d), q = 1 - p_y and the exponent
+//           gamma (0 or >= 1, a run-time float):
+//             row_loss = w_y q^gamma nll
+//             dlogit_c = g w_y m (p_c - [c == y]),     m = q^gamma + gamma q^(gamma - 1) p_y nll
+//           i.e. the plain gradient with g w_y m in the place of g: m is formed per row from the row the kernel holds anyway.
+// The kernels' one float parameter `x` is eps for kOpt and gamma for kFocal.  The formulas are kept apart where they
+// round differently: the plain one is the option one at w = 1, eps = 0 in exact arithmetic alone -- (e - 1) f and
+// f e - f round differently -- and every kind keeps its bits.  The parameter lists are those the plain kernels have always
+// had, the option-only parameters last in the backward, and the backward kernels write the plain formula out instead of
+// calling a helper: with either changed the compiler schedules the plain kernels differently (at 40 and 48 classes with
+// more registers and fewer waves).  Every pointer is a __restrict__ kernel parameter of its own: as members of a struct
+// passed by value they lose the qualifier, and the w[c] become vector loads inside the row loop.  w is read through the
+// caches, not staged in LDS: w[c] in the unrolled loops has a wave-uniform index (scalar loads, hoisted out of the row
+// loop where the registers allow), w[y] is one gather per row from a table of at most a few cache lines.
+// HAS_W = false: w = 1, W = C, no load.
+enum Loss { kPlain, kOpt, kFocal };
+
 template <bool HAS_W>
 __device__ __forceinline__ float ce_w(const float* __restrict__ w, int c) { return HAS_W ? w[c] : 1.0f; }
 
@@ -231,22 +231,67 @@ __device__ __forceinline__ float4 ce_opt_grad_chunk(const float* __restrict__ w,
     return o;
 }
 
-template <bool PAD, bool OPT, bool HAS_W>
+// the label's logit out of a row held in registers (0 where y is no column of it: the caller tests the label).  One
+// chunk's step is a macro, not a function: the plain and option forward take it inside their sum loop, and through a
+// helper the compiler lays the one-chunk kernels out differently.
+#define SIGMA_CE_PICK(v, c0, y, xy) \
+    ((y) == (c0)) ? (v).x : ((y) == (c0) + 1) ? (v).y : ((y) == (c0) + 2) ? (v).z : ((y) == (c0) + 3) ? (v).w : (xy)
+
+template <int NC4>
+__device__ __forceinline__ float ce_pick(const float4 (&v)[NC4], long y) {
+    float xy = 0.0f;
+#pragma unroll
+    for (int c = 0; c < NC4; ++c) xy = SIGMA_CE_PICK(v[c], 4 * c, y, xy);
+    return xy;
+}
+
+// The focal factors of a valid row from xy = x_y and l = lse.  gamma = 2 is a square, gamma = 1 needs no power, anything
+// else one exp(log) per row for t = q^(gamma - 1); q^gamma is t q throughout.  q = 0 (p_y rounds to 1): gamma > 0 gives
+// loss 0 and m = 0 by a branch, never 0 * inf; gamma = 0 is the cross-entropy row (q^0 = 1, m = 1).  The forward and the
+// backward form d, q and t with this code from the same lse.
+struct FocalRow { float d, qg, m; };          // min(x_y - lse, 0), q^gamma and m
+
+__device__ __forceinline__ FocalRow focal_row(float xy, float l, float gamma) {
+    FocalRow f;
+    const float d = f.d = fminf(xy - l, 0.0f);
+    if (gamma == 0.0f) { f.qg = 1.0f; f.m = 1.0f; return f; }
+    const float py = __expf(d);
+    const float q = fmaxf(1.0f - py, 0.0f);
+    if (!(q > 0.0f)) { f.qg = 0.0f; f.m = 0.0f; return f; }
+    const float t = gamma == 2.0f ? q : gamma == 1.0f ? 1.0f : __expf((gamma - 1.0f) * __logf(q));
+    f.qg = t * q;
+    f.m = f.qg + ((gamma * t) * py) * (0.0f - d);
+    return f;
+}
+
+__device__ __forceinline__ float focal_row_loss(float wy, float xy, float l, float gamma) {
+    const FocalRow f = focal_row(xy, l, gamma);
+    return wy * (f.qg * (0.0f - f.d));
+}
+
+// g w_y m of a valid row, g = the row's upstream gradient: what the plain gradient formula takes in the place of g
+__device__ __forceinline__ float focal_row_grad(const float* __restrict__ scale, float sc, const float* __restrict__ row_grad, long r,
+                                                float wy, float xy, float l, float gamma) {
+    return ((scale ? sc : row_grad[r]) * wy) * focal_row(xy, l, gamma).m;
+}
+
+template <bool PAD, Loss KIND, bool HAS_W>
 __global__ void __launch_bounds__(256)
 softmax_ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w, long rows,
-                      int nc, int ld, long ignore, float eps, float* __restrict__ lse, float* __restrict__ row_loss,
+                      int nc, int ld, long ignore, float x, float* __restrict__ lse, float* __restrict__ row_loss,
                       float* __restrict__ partial) {
+    constexpr bool OPT = KIND == kOpt;
     __shared__ float sh[4];
     float loss = 0.0f, den = 0.0f;
     const long stride = (long)gridDim.x * blockDim.x;
     const int pitch = PAD ? ld : nc;
-    const float W = ce_weight_sum<HAS_W>(w, nc), inv_c = 1.0f / (float)nc;
+    const float W = ce_weight_sum<OPT && HAS_W>(w, nc), inv_c = 1.0f / (float)nc;        // kOpt only
     for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
         const float* __restrict__ xr = logits + r * pitch;
         float m = kNegInf, s = 0.0f, sx = 0.0f;        // running max and sum of exp(x - m); sum of w_c x_c
         for (int c = 0; c < nc; c += 4) {
             float4 v = *reinterpret_cast<const float4*>(xr + c);
-            if (OPT && eps > 0.0f) sx += ce_wx_chunk<HAS_W>(w, c, v, PAD ? nc - c : 4);
+            if (OPT && x > 0.0f) sx += ce_wx_chunk<HAS_W>(w, c, v, PAD ? nc - c : 4);
             if (PAD) ce_mask_tail(v, nc - c, kNegInf);
             const float vm = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
             if (vm > m) { s *= __expf(m - vm); m = vm; }
@@ -259,35 +304,41 @@ softmax_ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restric
         if (y != ignore && y >= 0 && y < nc) {
             const float wy = ce_w<HAS_W>(w, (int)y);   // 1 without weights: den counts the rows
             const float xy = xr[y];
-            rl = OPT ? ce_opt_row_loss(eps, inv_c, wy, W, l, xy, sx) : l - xy;
+            rl = KIND == kFocal ? focal_row_loss(wy, xy, l, x) : OPT ? ce_opt_row_loss(x, inv_c, wy, W, l, xy, sx) : l - xy;
             loss += rl;
             den += wy;
         }
-        if (OPT && row_loss) row_loss[r] = rl;
+        if (KIND != kPlain && row_loss) row_loss[r] = rl;
     }
     const float tl = block_sum(loss, sh);
     const float td = block_sum(den, sh);
     if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = td; }
 }
 
-template <bool PAD, bool OPT, bool HAS_W>
+template <bool PAD, Loss KIND, bool HAS_W>
 __global__ void __launch_bounds__(256)
 softmax_ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ lse,
                       const float* __restrict__ scale, long rows, int nc, int ld, long ignore, float* __restrict__ dlogits,
-                      const float* __restrict__ w, const float* __restrict__ row_grad, float eps) {
-    const float sc = (!OPT || scale) ? scale[0] : 0.0f;
+                      const float* __restrict__ w, const float* __restrict__ row_grad, float x) {
+    constexpr bool OPT = KIND == kOpt;
+    const float sc = (KIND == kPlain || scale) ? scale[0] : 0.0f;
     const long stride = (long)gridDim.x * blockDim.x;
     const int pitch = PAD ? ld : nc;
-    const float W = ce_weight_sum<HAS_W>(w, nc), b = eps * (1.0f / (float)nc);
+    const float W = ce_weight_sum<OPT && HAS_W>(w, nc), b = x * (1.0f / (float)nc);        // kOpt only
     for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
         const float* __restrict__ xr = logits + r * pitch;
         float* __restrict__ dr = dlogits + r * pitch;
         const long y = labels[r];
         const bool on = y != ignore && y >= 0 && y < nc;
         const float l = lse[r];
-        const float g = on ? ((!OPT || scale) ? sc : row_grad[r]) : 0.0f;          // the row's upstream gradient
-        const float a = (1.0f - eps) * (on ? ce_w<HAS_W>(w, (int)y) : 0.0f);
-        const float fp = g * (a + b * W), fa = g * a, fb = g * b;          // OPT only
+        float g = 0.0f;                                    // the row's upstream gradient, g w_y m for kFocal; zero for ignored rows
+        if constexpr (KIND == kFocal) {
+            if (on) g = focal_row_grad(scale, sc, row_grad, r, ce_w<HAS_W>(w, (int)y), xr[y], l, x);
+        } else {
+            g = on ? ((!OPT || scale) ? sc : row_grad[r]) : 0.0f;
+        }
+        const float a = (1.0f - x) * (on ? ce_w<HAS_W>(w, (int)y) : 0.0f);
+        const float fp = g * (a + b * W), fa = g * a, fb = g * b;          // kOpt only
         int c = 0;
         for (; c < nc; c += 4) {
             const float4 v = *reinterpret_cast<const float4*>(xr + c);
@@ -311,17 +362,18 @@ softmax_ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restric
 // Same kernels with the row (NC4 float4) held in registers: every load of a row is issued before the first use.  The
 // generic kernels above walk the row with one load in flight per thread (1.2 TB/s on 8 x 480 x 640 x 40).  PAD = true:
 // NC4 = ceil(nc / 4) chunks hold the valid columns.
-template <int NC4, bool PAD, bool OPT, bool HAS_W>
+template <int NC4, bool PAD, Loss KIND, bool HAS_W>
 __global__ void __launch_bounds__(256)
 softmax_ce_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w, long rows,
-                          int nc_, int ld, long ignore, float eps, float* __restrict__ lse, float* __restrict__ row_loss,
+                          int nc_, int ld, long ignore, float x, float* __restrict__ lse, float* __restrict__ row_loss,
                           float* __restrict__ partial) {
+    constexpr bool OPT = KIND == kOpt;
     __shared__ float sh[4];
     const int nc = PAD ? nc_ : NC4 * 4;
     const int pitch = PAD ? ld : NC4 * 4;
     float loss = 0.0f, den = 0.0f;
     const long stride = (long)gridDim.x * blockDim.x;
-    const float W = ce_weight_sum<HAS_W>(w, nc), inv_c = 1.0f / (float)nc;
+    const float W = ce_weight_sum<OPT && HAS_W>(w, nc), inv_c = 1.0f / (float)nc;        // kOpt only
     for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
         const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * pitch);
         float4 v[NC4];
@@ -329,7 +381,7 @@ softmax_ce_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* __res
         for (int c = 0; c < NC4; ++c) v[c] = xr[c];
         const long y = labels[r];
         float sx = 0.0f;
-        if (OPT && eps > 0.0f) {
+        if (OPT && x > 0.0f) {
 #pragma unroll
             for (int c = 0; c < NC4; ++c) sx += ce_wx_chunk<HAS_W>(w, 4 * c, v[c], (PAD && c == NC4 - 1) ? nc - 4 * c : 4);
         }
@@ -341,34 +393,35 @@ softmax_ce_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* __res
 #pragma unroll
         for (int c = 0; c < NC4; ++c) {
             s += (__expf(v[c].x - m) + __expf(v[c].y - m)) + (__expf(v[c].z - m) + __expf(v[c].w - m));
-            xy = (y == 4 * c) ? v[c].x : (y == 4 * c + 1) ? v[c].y : (y == 4 * c + 2) ? v[c].z : (y == 4 * c + 3) ? v[c].w : xy;
+            if (KIND != kFocal) xy = SIGMA_CE_PICK(v[c], 4 * c, y, xy);      // kFocal picks under the label test: fewer registers
         }
         const float l = m + __logf(s);
         lse[r] = l;
         float rl = 0.0f;
         if (y != ignore && y >= 0 && y < nc) {
             const float wy = ce_w<HAS_W>(w, (int)y);   // 1 without weights: den counts the rows
-            rl = OPT ? ce_opt_row_loss(eps, inv_c, wy, W, l, xy, sx) : l - xy;
+            rl = KIND == kFocal ? focal_row_loss(wy, ce_pick<NC4>(v, y), l, x) : OPT ? ce_opt_row_loss(x, inv_c, wy, W, l, xy, sx) : l - xy;
             loss += rl;
             den += wy;
         }
-        if (OPT && row_loss) row_loss[r] = rl;
+        if (KIND != kPlain && row_loss) row_loss[r] = rl;
     }
     const float tl = block_sum(loss, sh);
     const float td = block_sum(den, sh);
     if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = td; }
 }
 
-template <int NC4, bool PAD, bool OPT, bool HAS_W>
+template <int NC4, bool PAD, Loss KIND, bool HAS_W>
 __global__ void __launch_bounds__(256)
 softmax_ce_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ lse,
                           const float* __restrict__ scale, long rows, int nc_, int ld, long ignore, float* __restrict__ dlogits,
-                          const float* __restrict__ w, const float* __restrict__ row_grad, float eps) {
+                          const float* __restrict__ w, const float* __restrict__ row_grad, float x) {
+    constexpr bool OPT = KIND == kOpt;
     const int nc = PAD ? nc_ : NC4 * 4;
     const int pitch = PAD ? ld : NC4 * 4;
-    const float sc = (!OPT || scale) ? scale[0] : 0.0f;
+    const float sc = (KIND == kPlain || scale) ? scale[0] : 0.0f;
     const long stride = (long)gridDim.x * blockDim.x;
-    const float W = ce_weight_sum<HAS_W>(w, nc), b = eps * (1.0f / (float)nc);
+    const float W = ce_weight_sum<OPT && HAS_W>(w, nc), b = x * (1.0f / (float)nc);        // kOpt only
     for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
         const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * pitch);
         float4* __restrict__ dr = reinterpret_cast<float4*>(dlogits + r * pitch);
@@ -378,9 +431,14 @@ softmax_ce_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* __res
         const long y = labels[r];
         const float l = lse[r];
         const bool on = y != ignore && y >= 0 && y < nc;
-        const float g = on ? ((!OPT || scale) ? sc : row_grad[r]) : 0.0f;          // the row's upstream gradient
-        const float a = (1.0f - eps) * (on ? ce_w<HAS_W>(w, (int)y) : 0.0f);
-        const float fp = g * (a + b * W), fa = g * a, fb = g * b;          // OPT only
+        float g = 0.0f;                                    // the row's upstream gradient, g w_y m for kFocal; zero for ignored rows
+        if constexpr (KIND == kFocal) {
+            if (on) g = focal_row_grad(scale, sc, row_grad, r, ce_w<HAS_W>(w, (int)y), ce_pick<NC4>(v, y), l, x);
+        } else {
+            g = on ? ((!OPT || scale) ? sc : row_grad[r]) : 0.0f;
+        }
+        const float a = (1.0f - x) * (on ? ce_w<HAS_W>(w, (int)y) : 0.0f);
+        const float fp = g * (a + b * W), fa = g * a, fb = g * b;          // kOpt only
 #pragma unroll
         for (int c = 0; c < NC4; ++c) {
             const bool tail = PAD && c == NC4 - 1;
@@ -401,182 +459,7 @@ softmax_ce_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* __res
     }
 }
 
-// ---- focal loss (FocalLoss2d, utils/loss_opr.py:12-23) on the same rows: sigma_softmax_focal_fwd / _bwd ---------------
-// With d = x_y - lse <= 0, nll = -d, p_y = exp(d), q = 1 - p_y and the exponent gamma (0 or >= 1, a run-time float):
-//   row_loss = w_y q^gamma nll
-//   dlogit_c = g w_y m (p_c - [c == y]),     m = q^gamma + gamma q^(gamma - 1) p_y nll
-// i.e. the plain gradient with g w_y m in the place of g: m is formed per row from the row the kernel holds anyway.
-// Kernels of their own, not one more flag on the kernels above (their parameter lists are not touched, see there).
-// gamma = 2 is a square, gamma = 1 needs no power, anything else one exp(log) per row for t = q^(gamma - 1); q^gamma is
-// t q throughout.  q = 0 (p_y rounds to 1): gamma > 0 gives loss 0 and m = 0 by a branch, never 0 * inf; gamma = 0 is the
-// cross-entropy row (q^0 = 1, m = 1).  The forward and the backward form d, q and t with the same code from the same lse.
-struct FocalRow { float qg, m; };          // q^gamma and m
-
-__device__ __forceinline__ FocalRow focal_row(float d, float gamma) {
-    FocalRow f;
-    if (gamma == 0.0f) { f.qg = 1.0f; f.m = 1.0f; return f; }
-    const float py = __expf(d);
-    const float q = fmaxf(1.0f - py, 0.0f);
-    if (!(q > 0.0f)) { f.qg = 0.0f; f.m = 0.0f; return f; }
-    const float t = gamma == 2.0f ? q : gamma == 1.0f ? 1.0f : __expf((gamma - 1.0f) * __logf(q));
-    f.qg = t * q;
-    f.m = f.qg + ((gamma * t) * py) * (0.0f - d);
-    return f;
-}
-
-template <bool PAD, bool HAS_W>
-__global__ void __launch_bounds__(256)
-softmax_focal_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w, long rows,
-                         int nc, int ld, long ignore, float gamma, float* __restrict__ lse, float* __restrict__ row_loss,
-                         float* __restrict__ partial) {
-    __shared__ float sh[4];
-    float loss = 0.0f, den = 0.0f;
-    const long stride = (long)gridDim.x * blockDim.x;
-    const int pitch = PAD ? ld : nc;
-    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
-        const float* __restrict__ xr = logits + r * pitch;
-        float m = kNegInf, s = 0.0f;
-        for (int c = 0; c < nc; c += 4) {
-            float4 v = *reinterpret_cast<const float4*>(xr + c);
-            if (PAD) ce_mask_tail(v, nc - c, kNegInf);
-            const float vm = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
-            if (vm > m) { s *= __expf(m - vm); m = vm; }
-            s += (__expf(v.x - m) + __expf(v.y - m)) + (__expf(v.z - m) + __expf(v.w - m));
-        }
-        const float l = m + __logf(s);
-        lse[r] = l;
-        const long y = labels[r];
-        float rl = 0.0f;
-        if (y != ignore && y >= 0 && y < nc) {
-            const float wy = ce_w<HAS_W>(w, (int)y);
-            const float d = fminf(xr[y] - l, 0.0f);
-            rl = wy * (focal_row(d, gamma).qg * (0.0f - d));
-            loss += rl;
-            den += wy;
-        }
-        if (row_loss) row_loss[r] = rl;
-    }
-    const float tl = block_sum(loss, sh);
-    const float td = block_sum(den, sh);
-    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = td; }
-}
-
-template <bool PAD, bool HAS_W>
-__global__ void __launch_bounds__(256)
-softmax_focal_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ lse,
-                         const float* __restrict__ scale, const float* __restrict__ row_grad, const float* __restrict__ w, long rows,
-                         int nc, int ld, long ignore, float gamma, float* __restrict__ dlogits) {
-    const float sc = scale ? scale[0] : 0.0f;
-    const long stride = (long)gridDim.x * blockDim.x;
-    const int pitch = PAD ? ld : nc;
-    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
-        const float* __restrict__ xr = logits + r * pitch;
-        float* __restrict__ dr = dlogits + r * pitch;
-        const long y = labels[r];
-        const bool on = y != ignore && y >= 0 && y < nc;
-        const float l = lse[r];
-        float f = 0.0f;                                    // g w_y m, zero for ignored rows
-        if (on) f = ((scale ? sc : row_grad[r]) * ce_w<HAS_W>(w, (int)y)) * focal_row(fminf(xr[y] - l, 0.0f), gamma).m;
-        int c = 0;
-        for (; c < nc; c += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(xr + c);
-            float4 o;
-            o.x = (__expf(v.x - l) - (y == c ? 1.0f : 0.0f)) * f;
-            o.y = (__expf(v.y - l) - (y == c + 1 ? 1.0f : 0.0f)) * f;
-            o.z = (__expf(v.z - l) - (y == c + 2 ? 1.0f : 0.0f)) * f;
-            o.w = (__expf(v.w - l) - (y == c + 3 ? 1.0f : 0.0f)) * f;
-            if (PAD) ce_mask_tail(o, nc - c, 0.0f);
-            *reinterpret_cast<float4*>(dr + c) = o;
-        }
-        if (PAD)
-            for (; c < ld; c += 4) *reinterpret_cast<float4*>(dr + c) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-}
-
-// the label's logit out of a row held in registers (0 where y is no column of it: the caller tests the label)
-template <int NC4>
-__device__ __forceinline__ float ce_pick(const float4 (&v)[NC4], long y) {
-    float xy = 0.0f;
-#pragma unroll
-    for (int c = 0; c < NC4; ++c)
-        xy = (y == 4 * c) ? v[c].x : (y == 4 * c + 1) ? v[c].y : (y == 4 * c + 2) ? v[c].z : (y == 4 * c + 3) ? v[c].w : xy;
-    return xy;
-}
-
-template <int NC4, bool PAD, bool HAS_W>
-__global__ void __launch_bounds__(256)
-softmax_focal_fwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ w, long rows,
-                             int nc_, int ld, long ignore, float gamma, float* __restrict__ lse, float* __restrict__ row_loss,
-                             float* __restrict__ partial) {
-    __shared__ float sh[4];
-    const int nc = PAD ? nc_ : NC4 * 4;
-    const int pitch = PAD ? ld : NC4 * 4;
-    float loss = 0.0f, den = 0.0f;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
-        const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * pitch);
-        float4 v[NC4];
-#pragma unroll
-        for (int c = 0; c < NC4; ++c) v[c] = xr[c];
-        const long y = labels[r];
-        if (PAD) ce_mask_tail(v[NC4 - 1], nc - 4 * (NC4 - 1), kNegInf);
-        float m = kNegInf;
-#pragma unroll
-        for (int c = 0; c < NC4; ++c) m = fmaxf(m, fmaxf(fmaxf(v[c].x, v[c].y), fmaxf(v[c].z, v[c].w)));
-        float s = 0.0f;
-#pragma unroll
-        for (int c = 0; c < NC4; ++c) s += (__expf(v[c].x - m) + __expf(v[c].y - m)) + (__expf(v[c].z - m) + __expf(v[c].w - m));
-        const float l = m + __logf(s);
-        lse[r] = l;
-        float rl = 0.0f;
-        if (y != ignore && y >= 0 && y < nc) {
-            const float wy = ce_w<HAS_W>(w, (int)y);
-            const float d = fminf(ce_pick<NC4>(v, y) - l, 0.0f);
-            rl = wy * (focal_row(d, gamma).qg * (0.0f - d));
-            loss += rl;
-            den += wy;
-        }
-        if (row_loss) row_loss[r] = rl;
-    }
-    const float tl = block_sum(loss, sh);
-    const float td = block_sum(den, sh);
-    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = tl; partial[2 * blockIdx.x + 1] = td; }
-}
-
-template <int NC4, bool PAD, bool HAS_W>
-__global__ void __launch_bounds__(256)
-softmax_focal_bwd_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ lse,
-                             const float* __restrict__ scale, const float* __restrict__ row_grad, const float* __restrict__ w, long rows,
-                             int nc_, int ld, long ignore, float gamma, float* __restrict__ dlogits) {
-    const int nc = PAD ? nc_ : NC4 * 4;
-    const int pitch = PAD ? ld : NC4 * 4;
-    const float sc = scale ? scale[0] : 0.0f;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
-        const float4* __restrict__ xr = reinterpret_cast<const float4*>(logits + r * pitch);
-        float4* __restrict__ dr = reinterpret_cast<float4*>(dlogits + r * pitch);
-        float4 v[NC4];
-#pragma unroll
-        for (int c = 0; c < NC4; ++c) v[c] = xr[c];
-        const long y = labels[r];
-        const float l = lse[r];
-        const bool on = y != ignore && y >= 0 && y < nc;
-        float f = 0.0f;                                    // g w_y m, zero for ignored rows
-        if (on) f = ((scale ? sc : row_grad[r]) * ce_w<HAS_W>(w, (int)y)) * focal_row(fminf(ce_pick<NC4>(v, y) - l, 0.0f), gamma).m;
-#pragma unroll
-        for (int c = 0; c < NC4; ++c) {
-            float4 o;
-            o.x = (__expf(v[c].x - l) - (y == 4 * c ? 1.0f : 0.0f)) * f;
-            o.y = (__expf(v[c].y - l) - (y == 4 * c + 1 ? 1.0f : 0.0f)) * f;
-            o.z = (__expf(v[c].z - l) - (y == 4 * c + 2 ? 1.0f : 0.0f)) * f;
-            o.w = (__expf(v[c].w - l) - (y == 4 * c + 3 ? 1.0f : 0.0f)) * f;
-            if (PAD && c == NC4 - 1) ce_mask_tail(o, nc - 4 * c, 0.0f);
-            dr[c] = o;
-        }
-        if (PAD)
-            for (int c = NC4; c < (ld >> 2); ++c) dr[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-}
+#undef SIGMA_CE_PICK
 
 // NC4 = ceil(classes / 4) chunks held in registers up to 64 classes
 template <typename F>
@@ -695,64 +578,35 @@ sigma_ce_opt_params ce_plain(const float* logits, const int64_t* labels, int64_t
     return p;
 }
 
-// One launcher per direction for the plain (OPT = false: weight, row_loss, row_grad NULL and label_smoothing 0 in `p`) and
-// the option loss; the arguments are checked by the entry points.  Rows of up to 64 classes go to the register kernels.
-template <bool OPT>
-int ce_launch_fwd(const sigma_ce_opt_params& p, void* stream) {
+// One launcher per direction for the three kinds; `x` is the kernels' float (0 for kPlain, whose `p` holds weight, row_loss
+// and row_grad NULL).  The arguments are checked by the entry points.  Rows of up to 64 classes go to the register kernels.
+template <Loss KIND>
+int ce_launch_fwd(const sigma_ce_opt_params& p, float x, void* stream) {
     // every one of the SIGMA_CE_BLOCKS workgroups writes its (loss, weight or count) pair, rows or not: the caller adds them up
     const dim3 grid(SIGMA_CE_BLOCKS), block(256);
-    dispatch_flags(p.ld != p.classes, OPT && p.weight != nullptr, [&](auto pad, auto has_w) {
-        constexpr bool PAD = decltype(pad)::value, HAS_W = OPT && decltype(has_w)::value;
+    dispatch_flags(p.ld != p.classes, KIND != kPlain && p.weight != nullptr, [&](auto pad, auto has_w) {
+        constexpr bool PAD = decltype(pad)::value, HAS_W = KIND != kPlain && decltype(has_w)::value;
         auto launch = [&](auto kernel) {
             hipLaunchKernelGGL(kernel, grid, block, 0, static_cast<hipStream_t>(stream), p.logits, p.labels, p.weight, (long)p.rows,
-                               (int)p.classes, (int)p.ld, (long)p.ignore_index, p.label_smoothing, p.lse, p.row_loss, p.partial);
+                               (int)p.classes, (int)p.ld, (long)p.ignore_index, x, p.lse, p.row_loss, p.partial);
         };
-        if (!dispatch_nc4((p.classes + 3) / 4, [&](auto n) { launch(softmax_ce_fwd_reg_kernel<decltype(n)::value, PAD, OPT, HAS_W>); }))
-            launch(softmax_ce_fwd_kernel<PAD, OPT, HAS_W>);
+        if (!dispatch_nc4((p.classes + 3) / 4, [&](auto n) { launch(softmax_ce_fwd_reg_kernel<decltype(n)::value, PAD, KIND, HAS_W>); }))
+            launch(softmax_ce_fwd_kernel<PAD, KIND, HAS_W>);
     });
     return done();
 }
 
-template <bool OPT>
-int ce_launch_bwd(const sigma_ce_opt_params& p, void* stream) {
+template <Loss KIND>
+int ce_launch_bwd(const sigma_ce_opt_params& p, float x, void* stream) {
     const dim3 grid(stream_grid(p.rows)), block(256);
-    dispatch_flags(p.ld != p.classes, OPT && p.weight != nullptr, [&](auto pad, auto has_w) {
-        constexpr bool PAD = decltype(pad)::value, HAS_W = OPT && decltype(has_w)::value;
+    dispatch_flags(p.ld != p.classes, KIND != kPlain && p.weight != nullptr, [&](auto pad, auto has_w) {
+        constexpr bool PAD = decltype(pad)::value, HAS_W = KIND != kPlain && decltype(has_w)::value;
         auto launch = [&](auto kernel) {
             hipLaunchKernelGGL(kernel, grid, block, 0, static_cast<hipStream_t>(stream), p.logits, p.labels, p.lse, p.scale, (long)p.rows,
-                               (int)p.classes, (int)p.ld, (long)p.ignore_index, p.dlogits, p.weight, p.row_grad, p.label_smoothing);
+                               (int)p.classes, (int)p.ld, (long)p.ignore_index, p.dlogits, p.weight, p.row_grad, x);
         };
-        if (!dispatch_nc4((p.classes + 3) / 4, [&](auto n) { launch(softmax_ce_bwd_reg_kernel<decltype(n)::value, PAD, OPT, HAS_W>); }))
-            launch(softmax_ce_bwd_kernel<PAD, OPT, HAS_W>);
-    });
-    return done();
-}
-
-// the focal launchers: grids, flags and regimes of the launchers above
-int focal_launch_fwd(const sigma_ce_opt_params& p, float gamma, void* stream) {
-    const dim3 grid(SIGMA_CE_BLOCKS), block(256);
-    dispatch_flags(p.ld != p.classes, p.weight != nullptr, [&](auto pad, auto has_w) {
-        constexpr bool PAD = decltype(pad)::value, HAS_W = decltype(has_w)::value;
-        auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, block, 0, static_cast<hipStream_t>(stream), p.logits, p.labels, p.weight, (long)p.rows,
-                               (int)p.classes, (int)p.ld, (long)p.ignore_index, gamma, p.lse, p.row_loss, p.partial);
-        };
-        if (!dispatch_nc4((p.classes + 3) / 4, [&](auto n) { launch(softmax_focal_fwd_reg_kernel<decltype(n)::value, PAD, HAS_W>); }))
-            launch(softmax_focal_fwd_kernel<PAD, HAS_W>);
-    });
-    return done();
-}
-
-int focal_launch_bwd(const sigma_ce_opt_params& p, float gamma, void* stream) {
-    const dim3 grid(stream_grid(p.rows)), block(256);
-    dispatch_flags(p.ld != p.classes, p.weight != nullptr, [&](auto pad, auto has_w) {
-        constexpr bool PAD = decltype(pad)::value, HAS_W = decltype(has_w)::value;
-        auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, block, 0, static_cast<hipStream_t>(stream), p.logits, p.labels, p.lse, p.scale, p.row_grad,
-                               p.weight, (long)p.rows, (int)p.classes, (int)p.ld, (long)p.ignore_index, gamma, p.dlogits);
-        };
-        if (!dispatch_nc4((p.classes + 3) / 4, [&](auto n) { launch(softmax_focal_bwd_reg_kernel<decltype(n)::value, PAD, HAS_W>); }))
-            launch(softmax_focal_bwd_kernel<PAD, HAS_W>);
+        if (!dispatch_nc4((p.classes + 3) / 4, [&](auto n) { launch(softmax_ce_bwd_reg_kernel<decltype(n)::value, PAD, KIND, HAS_W>); }))
+            launch(softmax_ce_bwd_kernel<PAD, KIND, HAS_W>);
     });
     return done();
 }
@@ -860,7 +714,7 @@ int sigma_softmax_ce_fwd_ld(const float* logits, const int64_t* labels, int64_t 
     if (!partial) return SIGMA_OPS_ERR_ARG;
     if (rows > 0 && (!logits || !labels || !lse || !sigma::al16(logits))) return SIGMA_OPS_ERR_ARG;
     const sigma_ce_opt_params p = sigma::ce_plain(logits, labels, rows, classes, ld, ignore_index, lse, partial, nullptr, nullptr);
-    return sigma::ce_launch_fwd<false>(p, stream);
+    return sigma::ce_launch_fwd<sigma::kPlain>(p, 0.0f, stream);
 }
 
 int sigma_softmax_ce_bwd_ld(const float* logits, const int64_t* labels, const float* lse, const float* scale, int64_t rows, int32_t classes,
@@ -869,55 +723,58 @@ int sigma_softmax_ce_bwd_ld(const float* logits, const int64_t* labels, const fl
     if (rows == 0) return SIGMA_OPS_OK;
     if (!logits || !labels || !lse || !scale || !dlogits || !sigma::al16(logits) || !sigma::al16(dlogits)) return SIGMA_OPS_ERR_ARG;
     const sigma_ce_opt_params p = sigma::ce_plain(logits, labels, rows, classes, ld, ignore_index, lse, nullptr, scale, dlogits);
-    return sigma::ce_launch_bwd<false>(p, stream);
+    return sigma::ce_launch_bwd<sigma::kPlain>(p, 0.0f, stream);
 }
 
-// everything sigma_softmax_ce_opt_fwd and _bwd check alike, before any launch
-static int ce_opt_check(const sigma_ce_opt_params* p) {
+// everything the _opt_ and _focal_ entry points check alike in both directions, before any launch.  gamma (focal only, else
+// NULL): smoothing is refused, and an exponent that is NaN, negative or in (0, 1)
+static int ce_opt_check(const sigma_ce_opt_params* p, const float* gamma) {
     if (!p || p->rows < 0 || p->classes < 1 || p->ld % 4 != 0 || p->ld < p->classes) return SIGMA_OPS_ERR_ARG;
     if (!(p->label_smoothing >= 0.0f && p->label_smoothing <= 1.0f)) return SIGMA_OPS_ERR_ARG;      // NaN fails both
     if (!sigma::al4(p->weight) || !sigma::al4(p->lse) || !sigma::al4(p->row_loss) || !sigma::al4(p->partial) ||
         !sigma::al4(p->scale) || !sigma::al4(p->row_grad) || (reinterpret_cast<uintptr_t>(p->labels) & 7u) != 0)
         return SIGMA_OPS_ERR_ARG;
+    if (gamma) {
+        if (p->label_smoothing != 0.0f) return SIGMA_OPS_ERR_ARG;
+        if (!(*gamma == 0.0f || (*gamma >= 1.0f && *gamma <= 3.0e38f))) return SIGMA_OPS_ERR_ARG;      // NaN and inf fail both
+    }
+    return SIGMA_OPS_OK;
+}
+
+static int ce_opt_fwd_check(const sigma_ce_opt_params* p, const float* gamma) {
+    if (const int rc = ce_opt_check(p, gamma)) return rc;
+    if (!p->partial) return SIGMA_OPS_ERR_ARG;
+    if (p->rows > 0 && (!p->logits || !p->labels || !p->lse || !sigma::al16(p->logits))) return SIGMA_OPS_ERR_ARG;
+    return SIGMA_OPS_OK;
+}
+
+// no rows: nothing is launched and no buffer is looked at
+static int ce_opt_bwd_check(const sigma_ce_opt_params* p, const float* gamma) {
+    if (const int rc = ce_opt_check(p, gamma)) return rc;
+    if ((p->scale != nullptr) == (p->row_grad != nullptr)) return SIGMA_OPS_ERR_ARG;      // one of them, not both
+    if (p->rows > 0 && (!p->logits || !p->labels || !p->lse || !p->dlogits || !sigma::al16(p->logits) || !sigma::al16(p->dlogits)))
+        return SIGMA_OPS_ERR_ARG;
     return SIGMA_OPS_OK;
 }
 
 int sigma_softmax_ce_opt_fwd(const sigma_ce_opt_params* p, void* stream) {
-    if (const int rc = ce_opt_check(p)) return rc;
-    if (!p->partial) return SIGMA_OPS_ERR_ARG;
-    if (p->rows > 0 && (!p->logits || !p->labels || !p->lse || !sigma::al16(p->logits))) return SIGMA_OPS_ERR_ARG;
-    return sigma::ce_launch_fwd<true>(*p, stream);
+    if (const int rc = ce_opt_fwd_check(p, nullptr)) return rc;
+    return sigma::ce_launch_fwd<sigma::kOpt>(*p, p->label_smoothing, stream);
 }
 
 int sigma_softmax_ce_opt_bwd(const sigma_ce_opt_params* p, void* stream) {
-    if (const int rc = ce_opt_check(p)) return rc;
-    if ((p->scale != nullptr) == (p->row_grad != nullptr)) return SIGMA_OPS_ERR_ARG;      // one of them, not both
-    if (p->rows == 0) return SIGMA_OPS_OK;
-    if (!p->logits || !p->labels || !p->lse || !p->dlogits || !sigma::al16(p->logits) || !sigma::al16(p->dlogits)) return SIGMA_OPS_ERR_ARG;
-    return sigma::ce_launch_bwd<true>(*p, stream);
-}
-
-// what the focal entry points refuse on top of ce_opt_check: smoothing, and an exponent that is NaN, negative or in (0, 1)
-static int focal_check(const sigma_ce_opt_params* p, float gamma) {
-    if (const int rc = ce_opt_check(p)) return rc;
-    if (p->label_smoothing != 0.0f) return SIGMA_OPS_ERR_ARG;
-    if (!(gamma == 0.0f || (gamma >= 1.0f && gamma <= 3.0e38f))) return SIGMA_OPS_ERR_ARG;      // NaN and inf fail both
-    return SIGMA_OPS_OK;
+    if (const int rc = ce_opt_bwd_check(p, nullptr)) return rc;
+    return p->rows == 0 ? SIGMA_OPS_OK : sigma::ce_launch_bwd<sigma::kOpt>(*p, p->label_smoothing, stream);
 }
 
 int sigma_softmax_focal_fwd(const sigma_ce_opt_params* p, float gamma, void* stream) {
-    if (const int rc = focal_check(p, gamma)) return rc;
-    if (!p->partial) return SIGMA_OPS_ERR_ARG;
-    if (p->rows > 0 && (!p->logits || !p->labels || !p->lse || !sigma::al16(p->logits))) return SIGMA_OPS_ERR_ARG;
-    return sigma::focal_launch_fwd(*p, gamma, stream);
+    if (const int rc = ce_opt_fwd_check(p, &gamma)) return rc;
+    return sigma::ce_launch_fwd<sigma::kFocal>(*p, gamma, stream);
 }
 
 int sigma_softmax_focal_bwd(const sigma_ce_opt_params* p, float gamma, void* stream) {
-    if (const int rc = focal_check(p, gamma)) return rc;
-    if ((p->scale != nullptr) == (p->row_grad != nullptr)) return SIGMA_OPS_ERR_ARG;      // one of them, not both
-    if (p->rows == 0) return SIGMA_OPS_OK;
-    if (!p->logits || !p->labels || !p->lse || !p->dlogits || !sigma::al16(p->logits) || !sigma::al16(p->dlogits)) return SIGMA_OPS_ERR_ARG;
-    return sigma::focal_launch_bwd(*p, gamma, stream);
+    if (const int rc = ce_opt_bwd_check(p, &gamma)) return rc;
+    return p->rows == 0 ? SIGMA_OPS_OK : sigma::ce_launch_bwd<sigma::kFocal>(*p, gamma, stream);
 }
 
 }  // extern "C"

@@ -351,6 +351,19 @@ __device__ __forceinline__ float wave_sum(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
+// plain sum over the workgroup (whole waves), result valid in thread 0; sh: one float per wave.  The waves' sums are
+// added in wave order: the loss kernels of pointwise.hip and ohem.hip give the same bits for the same rows through it.
+__device__ __forceinline__ float block_sum(float s, float* sh) {
+    s = wave_sum(s);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) sh[w] = s;
+    __syncthreads();
+    float t = 0.0f;
+    if (threadIdx.x == 0) for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
+    __syncthreads();
+    return t;
+}
+
 // XCD-aware, bijective remap of the hardware workgroup id: consecutive LOGICAL
 // ids (which share a (batch, group) B/C tile) land on the same XCD's L2.
 // Hardware places workgroup w on XCD w % 8 (speed only, never correctness).

@@ -6,16 +6,18 @@
                    that writes dx.
 ``cross_entropy``  nn.CrossEntropyLoss(reduction='mean', ignore_index) of models/builder.py:146-166 on the CHANNELS-LAST
                    logits the classifier GEMM produces (MambaDecoder.up_x4): log-sum-exp + loss in one pass, gradient in
-                   one pass, no (B, classes, H, W) copy.  Class weights, label smoothing and the reductions 'sum' /
-                   'none' run on the OPT instantiations of the same kernels, through entry points of their own
-                   (``SoftmaxCEOptFn``).
+                   one pass, no (B, classes, H, W) copy (``SoftmaxCEFn``).  Class weights, label smoothing and the
+                   reductions 'sum' / 'none' run on the option kind of the same kernels (``SoftmaxCEOptFn``).
 ``ohem_cross_entropy``  ProbOhemCrossEntropy2d (utils/loss_opr.py:137-187) on the same logits: the forward of the option
                    kernels writes the per-pixel loss, csrc/ohem.hip selects the hard pixels on the device (a radix select
                    of the min_kept-th largest loss; no host round trip) and the backward of the option kernels runs on
                    the mined labels (``OhemCEFn``).
+``focal_cross_entropy``  FocalLoss2d (utils/loss_opr.py:12-23) with a run-time exponent on the same logits: the focal kind
+                   of the same kernels (``SoftmaxFocalFn``).
 
-``focal_cross_entropy``  FocalLoss2d (utils/loss_opr.py:12-23) with a run-time exponent on the same logits: the two
-                   cross-entropy passes with one per-row factor (``SoftmaxFocalFn``, sigma_softmax_focal_fwd / _bwd).
+The three front-ends share their checks (``_loss_rows``); the three Functions with options share one forward
+(``_rows_forward`` / ``_rows_finish``: buffers, parameters, saved tensors, reduction) and one backward (``_dlogits``), and
+differ in the entry point they name.
 
 GPU tensors only (no fallback); the callers keep the torch formulation for everything these kernels do not take.
 """
@@ -164,18 +166,18 @@ class SoftmaxCEFn(torch.autograd.Function):
     (the padded buffer of gemm.ClassifierPadFn; sigma_softmax_ce_fwd_ld / _bwd_ld, the pad is never read)"""
 
     @staticmethod
+    def _call(direction, ld, nc, before, after):
+        """sigma_softmax_ce_<direction>(*before, nc, *after, stream), or its _ld form with the pitch after the class count"""
+        name, pitch = (f"softmax_ce_{direction}", ()) if ld == nc else (f"softmax_ce_{direction}_ld", (ld,))
+        _capi.check(getattr(_capi.load(), "sigma_" + name)(*before, nc, *pitch, *after, _stream()), name)
+
+    @staticmethod
     def forward(ctx, logits2, labels, ignore_index, ld):
-        lib = _capi.load()
         rows, nc = logits2.shape
         lse = torch.empty(rows, device=logits2.device, dtype=torch.float32)
         partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=logits2.device, dtype=torch.float32)
         with torch.cuda.device(logits2.device):
-            if ld == nc:
-                _capi.check(lib.sigma_softmax_ce_fwd(_p(logits2), _p(labels), rows, nc, int(ignore_index), _p(lse), _p(partial), _stream()),
-                            "softmax_ce_fwd")
-            else:
-                _capi.check(lib.sigma_softmax_ce_fwd_ld(_p(logits2), _p(labels), rows, nc, ld, int(ignore_index), _p(lse), _p(partial),
-                                                        _stream()), "softmax_ce_fwd_ld")
+            SoftmaxCEFn._call("fwd", ld, nc, (_p(logits2), _p(labels), rows), (int(ignore_index), _p(lse), _p(partial)))
         tot = partial.sum(0)
         ctx.save_for_backward(logits2, labels, lse, tot)
         ctx.ignore_index, ctx.ld = int(ignore_index), ld
@@ -183,25 +185,19 @@ class SoftmaxCEFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _capi.load()
         logits2, labels, lse, tot = ctx.saved_tensors
         rows, nc = logits2.shape
         ld = ctx.ld
         scale = (g.float() / tot[1]).reshape(1).contiguous()
-        if ld == nc:
-            dl = torch.empty_like(logits2)
-            with torch.cuda.device(logits2.device):
-                _capi.check(lib.sigma_softmax_ce_bwd(_p(logits2), _p(labels), _p(lse), _p(scale), rows, nc, ctx.ignore_index, _p(dl), _stream()),
-                            "softmax_ce_bwd")
-            return dl, None, None, None
         # the gradient at the logits' pitch, pad columns written with zeros: the classifier's backward claims the whole
         # buffer for its GEMMs (_handoff.py) -- no zero fill, no re-laying copy
-        full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
+        full = torch.empty_like(logits2) if ld == nc else torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
         with torch.cuda.device(logits2.device):
-            _capi.check(lib.sigma_softmax_ce_bwd_ld(_p(logits2), _p(labels), _p(lse), _p(scale), rows, nc, ld, ctx.ignore_index, _p(full),
-                                                    _stream()), "softmax_ce_bwd_ld")
-        offer_padded_grad_buffer(full)
-        return full[:, :nc], None, None, None
+            SoftmaxCEFn._call("bwd", ld, nc, (_p(logits2), _p(labels), _p(lse), _p(scale), rows), (ctx.ignore_index, _p(full)))
+        if ld != nc:
+            offer_padded_grad_buffer(full)
+            full = full[:, :nc]
+        return full, None, None, None
 
 
 def _row_pitch(nhwc: torch.Tensor):
@@ -214,6 +210,64 @@ def _row_pitch(nhwc: torch.Tensor):
     if (W > 1 and sw != ld) or (H > 1 and sh != W * ld) or (B > 1 and sb != H * W * ld):
         return None
     return ld
+
+
+def _rows_forward(ctx, kind, extra, logits2, labels, weight, ignore_index, ld, eps, reduction, out_shape):
+    """The forward of ``SoftmaxCEOptFn`` (kind "ce_opt") and ``SoftmaxFocalFn`` ("focal"): sigma_softmax_<kind>_fwd(params,
+    *extra, stream) into a new lse, the partial pairs and, for 'none', the row losses; then ``_rows_finish``"""
+    rows = logits2.shape[0]
+    dev = logits2.device
+    lse = torch.empty(rows, device=dev, dtype=torch.float32)
+    partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=dev, dtype=torch.float32)
+    row_loss = torch.empty(rows, device=dev, dtype=torch.float32) if reduction == "none" else None
+    p = SoftmaxCEOptFn._params(logits2, labels, weight, lse, ignore_index, ld, eps)
+    p.partial = partial.data_ptr()
+    p.row_loss = row_loss.data_ptr() if row_loss is not None else None
+    with torch.cuda.device(dev):
+        _capi.check(getattr(_capi.load(), f"sigma_softmax_{kind}_fwd")(ctypes.byref(p), *extra, _stream()), f"softmax_{kind}_fwd")
+    return _rows_finish(ctx, kind, extra, logits2, labels, weight, lse, partial, row_loss, ignore_index, ld, eps, reduction, out_shape)
+
+
+def _rows_finish(ctx, kind, extra, logits2, labels, weight, lse, partial, row_loss, ignore_index, ld, eps, reduction, out_shape):
+    """What the three loss Functions do with the outputs of their forward kernels: save what ``_dlogits`` takes -- `labels`
+    are the labels the backward runs on, `kind` and `extra` name its entry point -- and reduce: 'mean' divides the summed
+    row losses by the summed weights of the labelled pixels ON THE DEVICE, 'sum' returns the sum, 'none' the per-pixel
+    losses in `out_shape`"""
+    tot = partial.sum(0)
+    ctx.save_for_backward(logits2, labels, lse, tot, weight)
+    ctx.ignore_index, ctx.ld, ctx.eps, ctx.reduction = int(ignore_index), ld, float(eps), reduction
+    ctx.kind, ctx.extra = kind, extra
+    if reduction == "none":
+        return row_loss.view(out_shape)
+    return tot[0] / tot[1] if reduction == "mean" else tot[0].clone()
+
+
+def _dlogits(ctx, g):
+    """The backward of the three loss Functions: sigma_softmax_<ctx.kind>_bwd(params, *ctx.extra, stream) on what
+    ``_rows_finish`` saved, into a new gradient buffer at the logits' pitch"""
+    logits2, labels, lse, tot, weight = ctx.saved_tensors
+    rows, nc = logits2.shape
+    ld = ctx.ld
+    p = SoftmaxCEOptFn._params(logits2, labels, weight, lse, ctx.ignore_index, ld, ctx.eps)
+    if ctx.reduction == "none":
+        grad = g.float().contiguous().view(-1)
+        p.row_grad = grad.data_ptr()
+    else:
+        grad = g.float().reshape(1)
+        if ctx.reduction == "mean":
+            grad = torch.where(tot[1:2] > 0, grad / tot[1:2], torch.zeros_like(grad))      # zero denominator: zero gradient
+        grad = grad.contiguous()
+        p.scale = grad.data_ptr()
+    full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
+    p.dlogits = full.data_ptr()
+    with torch.cuda.device(logits2.device):
+        _capi.check(getattr(_capi.load(), f"sigma_softmax_{ctx.kind}_bwd")(ctypes.byref(p), *ctx.extra, _stream()),
+                    f"softmax_{ctx.kind}_bwd")
+    if ld != nc:
+        # as SoftmaxCEFn: the classifier's backward claims the whole padded buffer (_handoff.py)
+        offer_padded_grad_buffer(full)
+        full = full[:, :nc]
+    return full
 
 
 class SoftmaxCEOptFn(torch.autograd.Function):
@@ -234,58 +288,11 @@ class SoftmaxCEOptFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits2, labels, weight, ignore_index, ld, eps, reduction, out_shape):
-        lib = _capi.load()
-        rows = logits2.shape[0]
-        dev = logits2.device
-        lse = torch.empty(rows, device=dev, dtype=torch.float32)
-        partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=dev, dtype=torch.float32)
-        row_loss = torch.empty(rows, device=dev, dtype=torch.float32) if reduction == "none" else None
-        p = SoftmaxCEOptFn._params(logits2, labels, weight, lse, ignore_index, ld, eps)
-        p.partial = partial.data_ptr()
-        p.row_loss = row_loss.data_ptr() if row_loss is not None else None
-        with torch.cuda.device(dev):
-            _capi.check(lib.sigma_softmax_ce_opt_fwd(ctypes.byref(p), _stream()), "softmax_ce_opt_fwd")
-        tot = partial.sum(0)
-        ctx.save_for_backward(logits2, labels, lse, tot, weight)
-        ctx.ignore_index, ctx.ld, ctx.eps, ctx.reduction = int(ignore_index), ld, float(eps), reduction
-        if reduction == "none":
-            return row_loss.view(out_shape)
-        return tot[0] / tot[1] if reduction == "mean" else tot[0].clone()
+        return _rows_forward(ctx, "ce_opt", (), logits2, labels, weight, ignore_index, ld, eps, reduction, out_shape)
 
     @staticmethod
     def backward(ctx, g):
-        return (SoftmaxCEOptFn._dlogits(ctx, g),) + (None,) * 7
-
-    @staticmethod
-    def _dlogits(ctx, g, focal_gamma=None):
-        """sigma_softmax_ce_opt_bwd on what the forward saved (``OhemCEFn`` saves its mined labels in the labels' place);
-        with `focal_gamma` sigma_softmax_focal_bwd (``SoftmaxFocalFn``: same arguments, same buffers)"""
-        lib = _capi.load()
-        logits2, labels, lse, tot, weight = ctx.saved_tensors
-        rows, nc = logits2.shape
-        ld = ctx.ld
-        p = SoftmaxCEOptFn._params(logits2, labels, weight, lse, ctx.ignore_index, ld, ctx.eps)
-        if ctx.reduction == "none":
-            grad = g.float().contiguous().view(-1)
-            p.row_grad = grad.data_ptr()
-        else:
-            grad = g.float().reshape(1)
-            if ctx.reduction == "mean":
-                grad = torch.where(tot[1:2] > 0, grad / tot[1:2], torch.zeros_like(grad))      # zero denominator: zero gradient
-            grad = grad.contiguous()
-            p.scale = grad.data_ptr()
-        full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
-        p.dlogits = full.data_ptr()
-        with torch.cuda.device(logits2.device):
-            if focal_gamma is None:
-                _capi.check(lib.sigma_softmax_ce_opt_bwd(ctypes.byref(p), _stream()), "softmax_ce_opt_bwd")
-            else:
-                _capi.check(lib.sigma_softmax_focal_bwd(ctypes.byref(p), focal_gamma, _stream()), "softmax_focal_bwd")
-        if ld != nc:
-            # as SoftmaxCEFn: the classifier's backward claims the whole padded buffer (_handoff.py)
-            offer_padded_grad_buffer(full)
-            full = full[:, :nc]
-        return full
+        return (_dlogits(ctx, g),) + (None,) * 7
 
 
 def ohem_stages(logits2, labels, weight, ignore_index, ld, thresh, min_kept, want_row_loss=False):
@@ -331,16 +338,12 @@ class OhemCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits2, labels, weight, ignore_index, ld, thresh, min_kept, reduction, out_shape):
         r = ohem_stages(logits2, labels, weight, ignore_index, ld, thresh, min_kept, want_row_loss=reduction == "none")
-        tot = r["partial"].sum(0)
-        ctx.save_for_backward(logits2, r["mined"], r["lse"], tot, weight)
-        ctx.ignore_index, ctx.ld, ctx.eps, ctx.reduction = int(ignore_index), ld, 0.0, reduction
-        if reduction == "none":
-            return r["row_loss"].view(out_shape)
-        return tot[0] / tot[1] if reduction == "mean" else tot[0].clone()
+        return _rows_finish(ctx, "ce_opt", (), logits2, r["mined"], weight, r["lse"], r["partial"], r["row_loss"], ignore_index, ld, 0.0,
+                            reduction, out_shape)
 
     @staticmethod
     def backward(ctx, g):
-        return (SoftmaxCEOptFn._dlogits(ctx, g),) + (None,) * 8
+        return (_dlogits(ctx, g),) + (None,) * 8
 
 
 class SoftmaxFocalFn(torch.autograd.Function):
@@ -350,27 +353,11 @@ class SoftmaxFocalFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits2, labels, weight, ignore_index, ld, gamma, reduction, out_shape):
-        lib = _capi.load()
-        rows = logits2.shape[0]
-        dev = logits2.device
-        lse = torch.empty(rows, device=dev, dtype=torch.float32)
-        partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=dev, dtype=torch.float32)
-        row_loss = torch.empty(rows, device=dev, dtype=torch.float32) if reduction == "none" else None
-        p = SoftmaxCEOptFn._params(logits2, labels, weight, lse, ignore_index, ld, 0.0)
-        p.partial = partial.data_ptr()
-        p.row_loss = row_loss.data_ptr() if row_loss is not None else None
-        with torch.cuda.device(dev):
-            _capi.check(lib.sigma_softmax_focal_fwd(ctypes.byref(p), float(gamma), _stream()), "softmax_focal_fwd")
-        tot = partial.sum(0)
-        ctx.save_for_backward(logits2, labels, lse, tot, weight)
-        ctx.ignore_index, ctx.ld, ctx.eps, ctx.gamma, ctx.reduction = int(ignore_index), ld, 0.0, float(gamma), reduction
-        if reduction == "none":
-            return row_loss.view(out_shape)
-        return tot[0] / tot[1] if reduction == "mean" else tot[0].clone()
+        return _rows_forward(ctx, "focal", (float(gamma),), logits2, labels, weight, ignore_index, ld, 0.0, reduction, out_shape)
 
     @staticmethod
     def backward(ctx, g):
-        return (SoftmaxCEOptFn._dlogits(ctx, g, focal_gamma=ctx.gamma),) + (None,) * 7
+        return (_dlogits(ctx, g),) + (None,) * 7
 
 
 CE_REDUCTIONS = ("mean", "sum", "none")
@@ -390,6 +377,34 @@ def _channels_last_rows(logits, label):
     if ld is None or ld % 4 != 0 or ld < nc:
         return None
     return nhwc, nc, ld
+
+
+def _class_weight(weight, nc, device):
+    """(True, w) with w None or the detached, contiguous weight the kernels read, or (False, None) for a weight they do
+    not take: anything but a 1-D fp32 tensor of `nc` elements on `device`, 4-byte aligned"""
+    if weight is None:
+        return True, None
+    if not (torch.is_tensor(weight) and weight.dtype == torch.float32 and weight.dim() == 1 and weight.numel() == nc
+            and weight.device == device):
+        return False, None
+    w = weight.detach().contiguous()
+    return (True, w) if w.data_ptr() % 4 == 0 else (False, None)
+
+
+def _loss_rows(logits, label, weight):
+    """What the three front-ends below hand to their Function: (logits2, labels, w, ld) -- the (rows, classes) view of
+    ``_channels_last_rows`` at its pitch, the int64 labels of its rows, the weight of ``_class_weight`` -- or None when
+    `logits` (B, classes, H, W), `label` (B, H, W) or `weight` is not what the loss kernels take"""
+    if not (logits.dim() == 4 and label.dim() == 3):
+        return None
+    rows_view = _channels_last_rows(logits, label)
+    if rows_view is None:
+        return None
+    nhwc, nc, ld = rows_view
+    ok, w = _class_weight(weight, nc, logits.device)
+    if not ok:
+        return None
+    return nhwc.reshape(-1, nc), label.long().contiguous().view(-1), w, ld      # reshape: a view at either pitch
 
 
 def criterion_route(criterion, device, classes, any_float_weight=False):
@@ -425,39 +440,21 @@ def cross_entropy(criterion, logits: torch.Tensor, label: torch.Tensor):
     Labels outside [0, classes) that are not ``ignore_index`` are treated as ignored (csrc/pointwise.hip), where
     torch's kernel device-asserts: the reference's datasets map every unlabeled pixel to 255 = ignore_index
     (dataloader/RGBXDataset.py), so such labels do not occur on this path."""
-    if not (logits.dim() == 4 and label.dim() == 3):
+    if logits.dim() != 4:
         return None
     route = criterion_route(criterion, logits.device, logits.shape[1])
     if route is None:
         return None
     if criterion.reduction == "none" and criterion.weight is None and float(getattr(criterion, "label_smoothing", 0.0)) == 0.0:
         return None                                        # declined before the option kernels existed, and still (see above)
-    rows_view = _channels_last_rows(logits, label)
-    if rows_view is None:
+    args = _loss_rows(logits, label, criterion.weight)
+    if args is None:
         return None
-    nhwc, nc, ld = rows_view
-    lab = label.long().contiguous()
+    logits2, lab, w, ld = args
     if route == "plain":
-        return SoftmaxCEFn.apply(nhwc.reshape(-1, nc), lab.view(-1), criterion.ignore_index, ld)      # reshape: a view at either pitch
-    w = criterion.weight
-    if w is not None:
-        w = w.detach().contiguous()
-        if w.data_ptr() % 4 != 0:
-            return None
-    return SoftmaxCEOptFn.apply(nhwc.reshape(-1, nc), lab.view(-1), w, criterion.ignore_index, ld, float(criterion.label_smoothing),
-                                criterion.reduction, tuple(label.shape))
-
-
-def _class_weight(weight, nc, device):
-    """(True, w) with w None or the detached, contiguous weight the kernels read, or (False, None) for a weight they do
-    not take: anything but a 1-D fp32 tensor of `nc` elements on `device`, 4-byte aligned"""
-    if weight is None:
-        return True, None
-    if not (torch.is_tensor(weight) and weight.dtype == torch.float32 and weight.dim() == 1 and weight.numel() == nc
-            and weight.device == device):
-        return False, None
-    w = weight.detach().contiguous()
-    return (True, w) if w.data_ptr() % 4 == 0 else (False, None)
+        return SoftmaxCEFn.apply(logits2, lab, criterion.ignore_index, ld)
+    return SoftmaxCEOptFn.apply(logits2, lab, w, criterion.ignore_index, ld, float(criterion.label_smoothing), criterion.reduction,
+                                tuple(label.shape))
 
 
 def ohem_cross_entropy(logits: torch.Tensor, label: torch.Tensor, ignore_index, thresh, min_kept, weight=None, reduction="mean"):
@@ -467,20 +464,13 @@ def ohem_cross_entropy(logits: torch.Tensor, label: torch.Tensor, ignore_index, 
     logits' device, a thresh outside (0, 1].  The hard pixels are selected on the device (sigma_ohem_select): no host
     synchronisation, so the step can be captured into a graph whichever branch the data take.  'none' returns (B, H, W)
     with zeros at dropped pixels; 'mean' divides by the summed weights of the KEPT pixels."""
-    if not (logits.dim() == 4 and label.dim() == 3) or reduction not in CE_REDUCTIONS:
+    if reduction not in CE_REDUCTIONS or not 0.0 < float(thresh) <= 1.0:
         return None
-    if not 0.0 < float(thresh) <= 1.0:
+    args = _loss_rows(logits, label, weight)
+    if args is None:
         return None
-    rows_view = _channels_last_rows(logits, label)
-    if rows_view is None:
-        return None
-    nhwc, nc, ld = rows_view
-    ok, w = _class_weight(weight, nc, logits.device)
-    if not ok:
-        return None
-    lab = label.long().contiguous()
-    return OhemCEFn.apply(nhwc.reshape(-1, nc), lab.view(-1), w, int(ignore_index), ld, float(thresh), int(min_kept), reduction,
-                          tuple(label.shape))
+    logits2, lab, w, ld = args
+    return OhemCEFn.apply(logits2, lab, w, int(ignore_index), ld, float(thresh), int(min_kept), reduction, tuple(label.shape))
 
 
 def focal_cross_entropy(logits: torch.Tensor, label: torch.Tensor, ignore_index, gamma, weight=None, reduction="mean"):
@@ -490,20 +480,35 @@ def focal_cross_entropy(logits: torch.Tensor, label: torch.Tensor, ignore_index,
     apply: another layout, dtype or device, a weight the OHEM route would decline, or an exponent the kernels do not
     take: 0 < gamma < 1 (q^(gamma - 1) is unbounded as p_y -> 1; see include/sigma_ops.h), negative, NaN or infinite.
     'mean' divides by the summed weights of the labelled pixels on the device; 'none' returns (B, H, W)."""
-    if not (logits.dim() == 4 and label.dim() == 3) or reduction not in CE_REDUCTIONS:
-        return None
     gamma = float(gamma)
-    if not (gamma == 0.0 or 1.0 <= gamma < float("inf")):
+    if reduction not in CE_REDUCTIONS or not (gamma == 0.0 or 1.0 <= gamma < float("inf")):
         return None
-    rows_view = _channels_last_rows(logits, label)
-    if rows_view is None:
+    args = _loss_rows(logits, label, weight)
+    if args is None:
         return None
-    nhwc, nc, ld = rows_view
-    ok, w = _class_weight(weight, nc, logits.device)
-    if not ok:
-        return None
-    lab = label.long().contiguous()
-    return SoftmaxFocalFn.apply(nhwc.reshape(-1, nc), lab.view(-1), w, int(ignore_index), ld, gamma, reduction, tuple(label.shape))
+    logits2, lab, w, ld = args
+    return SoftmaxFocalFn.apply(logits2, lab, w, int(ignore_index), ld, gamma, reduction, tuple(label.shape))
+
+
+def _det_labels(logits, label, ignore_index, weight):
+    """For the two element-wise losses below: (onehot, validf, wv, wy) -- the one-hot labels (B, classes, H, W), all zero
+    at ignored pixels (labels outside [0, classes) count as ignored); 1 / 0 per pixel for labelled / ignored; the weight as
+    (1, classes, 1, 1) or None; w_y per pixel, zero at ignored pixels"""
+    nc = logits.shape[1]
+    lab = label.long()
+    valid = (lab != ignore_index) & (lab >= 0) & (lab < nc)
+    onehot = F.one_hot(torch.where(valid, lab, torch.zeros_like(lab)), nc).permute(0, 3, 1, 2).to(logits.dtype)
+    validf = valid.to(logits.dtype)
+    wv = None if weight is None else weight.detach().to(logits.dtype).view(1, nc, 1, 1)
+    wy = validf if wv is None else (onehot * wv).sum(dim=1) * validf
+    return onehot, validf, wv, wy
+
+
+def _det_reduce(per_pixel, wy, reduction):
+    """'mean' divides the sum by the sum of w_y over the labelled pixels (0 / 0 = NaN when there is none)"""
+    if reduction == "none":
+        return per_pixel
+    return per_pixel.sum() / wy.sum() if reduction == "mean" else per_pixel.sum()
 
 
 def focal_deterministic(logits: torch.Tensor, label: torch.Tensor, ignore_index, gamma, weight=None, reduction="mean"):
@@ -511,18 +516,10 @@ def focal_deterministic(logits: torch.Tensor, label: torch.Tensor, ignore_index,
     on GPU tensors): element-wise ops and fixed-order reductions only, as ``cross_entropy_deterministic`` below.  Per
     pixel -w_y (1 - p_y)^gamma log p_y, zero at ignored pixels (labels outside [0, classes) count as ignored); 'mean'
     divides the sum by the sum of w_y over the labelled pixels (0 / 0 = NaN when there is none).  Any gamma >= 0."""
-    nc = logits.shape[1]
-    lab = label.long()
-    valid = (lab != ignore_index) & (lab >= 0) & (lab < nc)
-    onehot = F.one_hot(torch.where(valid, lab, torch.zeros_like(lab)), nc).permute(0, 3, 1, 2).to(logits.dtype)
-    validf = valid.to(logits.dtype)
+    onehot, _, _, wy = _det_labels(logits, label, ignore_index, weight)
     lsm = F.log_softmax(logits, dim=1)
     focal = lsm if float(gamma) == 0.0 else (1.0 - F.softmax(logits, dim=1)) ** float(gamma) * lsm
-    wy = validf if weight is None else (onehot * weight.detach().to(logits.dtype).view(1, nc, 1, 1)).sum(dim=1) * validf
-    per_pixel = -(focal * onehot).sum(dim=1) * wy
-    if reduction == "none":
-        return per_pixel
-    return per_pixel.sum() / wy.sum() if reduction == "mean" else per_pixel.sum()
+    return _det_reduce(-(focal * onehot).sum(dim=1) * wy, wy, reduction)
 
 
 def cross_entropy_deterministic(criterion, logits: torch.Tensor, label: torch.Tensor):
@@ -539,26 +536,13 @@ def cross_entropy_deterministic(criterion, logits: torch.Tensor, label: torch.Te
     route = criterion_route(criterion, logits.device, nc, any_float_weight=True)
     if route is None:
         return None
-    w = criterion.weight
-    lab = label.long()
-    valid = (lab != criterion.ignore_index) & (lab >= 0) & (lab < nc)
-    onehot = F.one_hot(torch.where(valid, lab, torch.zeros_like(lab)), nc).permute(0, 3, 1, 2).to(logits.dtype)
-    validf = valid.to(logits.dtype)
-    if route == "plain":
-        per_pixel = -(F.log_softmax(logits, dim=1) * onehot).sum(dim=1)
-        return (per_pixel * validf).sum() / validf.sum()
-    eps = float(criterion.label_smoothing)
+    onehot, validf, wv, wy = _det_labels(logits, label, criterion.ignore_index, criterion.weight)
     lsm = F.log_softmax(logits, dim=1)
-    if w is not None:
-        wv = w.detach().to(logits.dtype).view(1, nc, 1, 1)
-        lsm_w = lsm * wv
-        wy = (onehot * wv).sum(dim=1) * validf
-    else:
-        lsm_w, wy = lsm, validf
+    if route == "plain":
+        return _det_reduce(-(lsm * onehot).sum(dim=1) * validf, validf, "mean")
+    eps = float(criterion.label_smoothing)
+    lsm_w = lsm if wv is None else lsm * wv
     per_pixel = -(lsm_w * onehot).sum(dim=1)
     if eps > 0.0:
         per_pixel = (1.0 - eps) * per_pixel - (eps / nc) * lsm_w.sum(dim=1)
-    per_pixel = per_pixel * validf
-    if criterion.reduction == "none":
-        return per_pixel
-    return per_pixel.sum() / wy.sum() if criterion.reduction == "mean" else per_pixel.sum()
+    return _det_reduce(per_pixel * validf, wy, criterion.reduction)

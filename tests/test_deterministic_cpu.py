@@ -179,6 +179,7 @@ def test_dwconv_and_colscale_workspace_queries():
 
 # ------------------------------------------------------------------------------------------------------- static ISA
 ATOMIC = re.compile(r"^\s+(global_atomic|flat_atomic|buffer_atomic)\w*")
+ISA_TEXT = {}          # file -> its whole assembly listing, filled by the `isa` fixture
 ISA_FILES = ["scan_bwdr.hip", "scan_bwd.hip", "scan_bwd2.hip", "scan_bwd3.hip", "scan_bwd4.hip", "dwconv.hip", "pointwise.hip"]
 
 
@@ -207,7 +208,8 @@ def isa(tmp_path_factory):
         out = d / src.replace(".hip", ".s")
         subprocess.check_call([build.HIPCC, *flags, "--offload-device-only", "-S", os.path.join(build.CSRC, src), "-o", str(out)],
                               stderr=subprocess.DEVNULL)
-        return _functions(out.read_text().split("\n"))
+        ISA_TEXT[src] = out.read_text()
+        return _functions(ISA_TEXT[src].split("\n"))
 
     with cf.ThreadPoolExecutor(len(ISA_FILES)) as ex:
         funcs = {}
@@ -242,6 +244,18 @@ def test_deterministic_kernels_issue_no_float_atomics(isa, det_pat, default_pat)
         assert not _atomics(body), f"{name}: {_atomics(body)[:3]}"
     for name, body in default.items():              # the default instantiations keep their atomics (they are unchanged)
         assert any("global_atomic_add_f32" in a or "global_atomic_pk_add" in a for a in _atomics(body)), name
+
+
+def test_loss_family_is_340_kernels_without_scratch(isa):
+    """pointwise.hip instantiates the loss kernels that are launched and no other -- 17 regimes (16 register rows and the
+    walking kernel) x 2 pitches x 2 directions x (1 plain + 2 option + 2 focal, without and with class weights) -- and none
+    of them keeps its row, or anything else, in scratch memory"""
+    kernels = re.findall(r"^\t\.amdhsa_kernel (_ZN\S*softmax_\S+)\n(.*?)^\t\.end_amdhsa_kernel", ISA_TEXT["pointwise.hip"], re.M | re.S)
+    assert len(kernels) == len({n for n, _ in kernels}) == 340 == 17 * 2 * 2 * 5
+    assert sum(1 for n in isa if "softmax_" in n) == 340
+    for name, desc in kernels:
+        (size,) = re.findall(r"\.amdhsa_private_segment_fixed_size (\d+)", desc)
+        assert int(size) == 0 and ".amdhsa_uses_dynamic_stack 0" in desc, name
 
 
 def test_deterministic_row_lane_backward_keeps_the_counted_wait(isa):
