@@ -140,6 +140,16 @@ def _rows_ok(t: torch.Tensor) -> bool:
     return t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0 and 0 < t.stride(0) <= _MAX_LD
 
 
+def _as_rows(t: torch.Tensor) -> torch.Tensor:
+    """`t` itself when the kernels can read it (``_rows_ok``), else a copy they can: a strided gradient is packed, and a
+    packed one that starts off a 16-byte boundary (a slice of a larger buffer: ``.contiguous()`` hands it back as it is)
+    is cloned -- instead of sending the whole GEMM to the vendor library for the sake of four bytes"""
+    if _rows_ok(t):
+        return t
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _check_aux(name, bias, out, N, dev):
     """bias / out are read and written as raw fp32 by the kernels: refuse anything else"""
     if bias is not None and not (bias.is_cuda and bias.device == dev and bias.dtype == torch.float32 and bias.dim() == 1
@@ -328,7 +338,7 @@ class LinearSplit3Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x2, weight = ctx.saved_tensors
-        g2 = dy if _rows_ok(dy) else dy.contiguous()
+        g2 = _as_rows(dy)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = gemm_nn(g2, weight, pieces=_DGRAD) if (_DGRAD and nn_ok(g2, weight)) else torch.mm(g2, weight)
@@ -458,8 +468,8 @@ class LinearXZFn(torch.autograd.Function):
         x2, weight = ctx.saved_tensors
         M, C = x2.shape
         d = weight.shape[0] // 2
-        dxT = torch.zeros((d, M), device=x2.device, dtype=torch.float32) if dxT is None else (dxT if _rows_ok(dxT) else dxT.contiguous())
-        dz = torch.zeros((M, d), device=x2.device, dtype=torch.float32) if dz is None else (dz if _rows_ok(dz) else dz.contiguous())
+        dxT = torch.zeros((d, M), device=x2.device, dtype=torch.float32) if dxT is None else _as_rows(dxT)
+        dz = torch.zeros((M, d), device=x2.device, dtype=torch.float32) if dz is None else _as_rows(dz)
         w_x, w_z = weight[:d], weight[d:]
         dx2 = dw = db = None
         if ctx.needs_input_grad[0]:

@@ -90,6 +90,8 @@ def _ln_backward(ctx, dy, dx_add):
     C = xc.shape[-1]
     rows = xc.numel() // C
     dy = dy.contiguous()
+    if dy.data_ptr() % 16:                          # packed but off a 16-byte boundary: the kernel loads 16 bytes per lane
+        dy = dy.clone()
     dx = torch.empty_like(xc)
     dgamma = torch.empty_like(weight)
     dbeta = torch.empty_like(weight) if ctx.has_bias else None

@@ -126,6 +126,8 @@ class ScaleResidualFn(torch.autograd.Function):
         x, scale = ctx.saved_tensors
         C = x.shape[-1]
         g = dy.contiguous()
+        if g.data_ptr() % 16:                       # a packed gradient off a 16-byte boundary (a slice of a larger buffer):
+            g = g.clone()                           # the kernels load 16 bytes per lane and refuse it
         xc = x.contiguous()
         dx = torch.empty_like(xc)
         lib = _capi.load()

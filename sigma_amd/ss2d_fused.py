@@ -437,7 +437,12 @@ def _derived_params(x_proj_weight, dt_projs_weight, A_logs):
     if ent is not None and ent[0] == key and ent[1]() is x_proj_weight:
         return ent[2]
     val = build()
-    if len(_DERIVED) > 4096:                      # parameters that died without a lookup: start over
+    if torch.is_inference_mode_enabled():
+        # built under torch.inference_mode(): inference tensors, which a later training forward could not save for its
+        # backward (an evaluation between two training steps would leave them behind: the reference's optimizer steps
+        # none of these parameters, so nothing drops the entry).  Not cached; an entry built outside serves both.
+        return val
+    if len(_DERIVED) > 4096:                     # parameters that died without a lookup: start over
         _DERIVED.clear()
     _DERIVED[id(x_proj_weight)] = (key, weakref.ref(x_proj_weight), val, (id(x_proj_weight), id(dt_projs_weight), id(A_logs)))
     return val

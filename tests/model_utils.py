@@ -57,26 +57,42 @@ def assert_logits_close(a: torch.Tensor, b: torch.Tensor, rel: float):
     torch.testing.assert_close(a.double().cpu(), b.double().cpu(), rtol=10 * rel, atol=rel * float(b.abs().max()))
 
 
-def compare_with_reference_fixtures(case: str, gemm_mode: str) -> None:
+def compare_with_reference_fixtures(case: str, gemm_mode: str, frozen=None, grad_scale: float = 1.0):
     """The body of tests/test_model_gpu.py::test_logits_loss_and_grads_match_reference_fixtures (also run under torch's
     deterministic flag by tests/deterministic_model_worker.py): logits, loss, gradient digests and the element-wise
-    gradients of the scan-adjacent parameters of fixture `case` against the reference's own model."""
+    gradients of the scan-adjacent parameters of fixture `case` against the reference's own model.
+
+    ``frozen`` (optional predicate on parameter names, tests/autograd_contract_worker.py): those parameters do not require
+    a gradient, must come out with ``.grad is None`` and are left out of the comparison; every other name is compared as
+    always.  ``grad_scale`` (a whole number): the loss is run forward + backward that many times without clearing the
+    gradients, which are compared with ``grad_scale`` times the fixture's.  Tolerances are the same in every
+    configuration.  Returns (model, the last loss) for callers that go on with the model."""
+    passes = int(round(grad_scale))
+    assert passes >= 1 and passes == grad_scale, grad_scale
     meta, z = load_model_golden(case)
     model = build_model(meta["backbone"], meta["num_classes"], meta["H"], meta["W"]).cuda().eval()
+    if frozen is not None:
+        for n, p in model.named_parameters():
+            p.requires_grad_(not frozen(n))
     rgb, x, label = fill.make_inputs(meta["batch"], meta["H"], meta["W"], meta["num_classes"])
     with torch.no_grad():
         logits = model(rgb.cuda(), x.cuda())
     assert_logits_close(logits, torch.from_numpy(z["logits"]), 1e-3)
-    loss = model(rgb.cuda(), x.cuda(), label.cuda())
-    assert abs(loss.item() - float(z["loss"])) < 1e-3
-    loss.backward()
+    for _ in range(passes):
+        loss = model(rgb.cuda(), x.cuda(), label.cuda())
+        assert abs(loss.item() - float(z["loss"])) < 1e-3
+        loss.backward()
     names, ref = list(z["grad_names"]), z["grad_digest"]
     got = dict(model.named_parameters())
     bad = []
     for n, r in zip(names, ref):
         g = got[n].grad
+        if frozen is not None and frozen(str(n)):
+            assert g is None, f"frozen parameter {n} has a gradient"
+            continue
         assert g is not None, n
         d = digest(g)
+        r = grad_scale * r
         tol = 5e-3 * (abs(r[1]) + 1e-6)              # relative to the L1 mass of the gradient
         if not (abs(d[0] - r[0]) < tol and abs(d[1] - r[1]) < tol and abs(d[2] - r[2]) < tol):
             bad.append((n, d.tolist(), r.tolist()))
@@ -85,7 +101,10 @@ def compare_with_reference_fixtures(case: str, gemm_mode: str) -> None:
     # x_proj / dt_proj weights and biases, A_logs, Ds, out_norm, conv bias, decoder scales
     worst = []
     for i, n in enumerate(list(z["grad_full_names"])):
-        r = torch.from_numpy(z[f"grad_full_{i}"])
+        if frozen is not None and frozen(str(n)):
+            assert got[str(n)].grad is None, f"frozen parameter {n} has a gradient"
+            continue
+        r = grad_scale * torch.from_numpy(z[f"grad_full_{i}"])
         g = got[str(n)].grad.cpu()
         # + 2e-5: some of these gradients are sums of O(0.1) terms that cancel to ~1e-5 (cross_mamba.3 A_log_2: largest
         # element 7e-6); the dA / dD / dbias sums are fp32 atomics, whose order -- and with it the last bits of the partial
@@ -95,3 +114,4 @@ def compare_with_reference_fixtures(case: str, gemm_mode: str) -> None:
         if err > (5e-3 if gemm_mode == "fp32" else 1e-2):
             worst.append((str(n), err, scale))
     assert not worst, worst[:5]
+    return model, loss.detach()

@@ -459,47 +459,109 @@ def _mask_seed(kind, B, keep):
     raise AssertionError("no seed drops one sample and keeps one")
 
 
+class CaseData:
+    """what a case's runs share: the built block, its inputs and output gradients (plain tensors: every run makes its own
+    leaves from them), the seed and the per-sample factors of its stochastic-depth masks, and the twin's answer on this
+    data: ``ref`` (float64), ``e32``, ``e_pert`` and ``bnd`` = twin.bound(e32, e_pert) (+ EXTRA)"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
 @functools.lru_cache(maxsize=None)
-def case_result(cid):
-    """(ratios {slice: (err, bound)}, {reduced launch key: launches}, seconds) of case ``cid``; computed once, shared by the case's
-    test and the census"""
+def _block(cid):
     kind, (B, H, W, C), N, mode = CASES[cid]
-    t0 = time.time()
     blk = _build(kind, C, N, DROP if mode == "train" else 0.0)
     blk.train(mode != "eval")
-    g = torch.Generator().manual_seed(1000 + sum(map(ord, cid)))
+    return blk
+
+
+@functools.lru_cache(maxsize=None)
+def case_data(cid, variant="base"):
+    """CaseData of case ``cid``, computed once and shared by every test of the case (tests/test_autograd_contract_gpu.py
+    runs the product again on it under other autograd configurations: the twin's gradient of a trainable leaf does not
+    depend on which other leaves are frozen).  ``variant``: "base" the case's own data; "second" other inputs and output
+    gradients for the same block (a second micro-batch); "ones" the base inputs with output gradients of ones (what
+    ``out.sum().backward()`` delivers)."""
+    kind, (B, H, W, C), N, mode = CASES[cid]
+    t0 = time.time()
+    blk = _block(cid)
+    g = torch.Generator().manual_seed(1000 + sum(map(ord, cid)) + (7919 if variant == "second" else 0))
     n_in = 2 if kind in ("cromb", "conmb") else 1
     n_out = 2 if kind == "cromb" else 1
     oshape = (B, (H + 1) // 2, (W + 1) // 2, 2 * C) if kind == "merge" else (B, H, W, C)
-    xs = [torch.randn(B, H, W, C, generator=g).to(DEV).requires_grad_() for _ in range(n_in)]
+    xs = [torch.randn(B, H, W, C, generator=g).to(DEV) for _ in range(n_in)]
     gys = [torch.randn(oshape, generator=g).to(DEV) for _ in range(n_out)]
-    factors = None
+    if variant == "ones":
+        gys = [torch.ones_like(t) for t in gys]
+    factors = seed = None
     if mode == "train":
         seed = _mask_seed(kind, B, 1.0 - DROP)
         torch.manual_seed(seed)
         factors = _draw(kind, B, 1.0 - DROP)
         if B > 1:
             assert all(bool((f == 0).any()) and bool((f != 0).any()) for f in factors), factors
-        torch.manual_seed(seed)
-    with recording() as log:
-        outs = blk(*xs)
-        outs = outs if isinstance(outs, tuple) else (outs,)
-        torch.autograd.backward(outs, gys)
-        torch.cuda.synchronize()
-    keys = dict(collections.Counter(reduce_key(k) for k in log if k is not None))
     sd = {n: p.detach() for n, p in blk.named_parameters()}
-    got = {f"out{i}": o.detach() for i, o in enumerate(outs)}
-    got.update({f"dx{i}": x.grad for i, x in enumerate(xs)})
-    got.update({n: (p.grad if p.grad is not None else torch.zeros_like(p)) for n, p in blk.named_parameters()})
-    ref, e32, e_pert = twin.twin_reference(kind, sd, [x.detach() for x in xs], gys, factors, device=DEV)
-    assert sorted(ref) == sorted(got)
-    err = twin.slice_errors(kind, got, ref)
+    ref, e32, e_pert = twin.twin_reference(kind, sd, xs, gys, factors, device=DEV)
     bnd = twin.bound(e32, e_pert)
     for name, b in EXTRA.get(cid, {}).items():
         bnd[name] += b
     torch.cuda.synchronize()
-    del blk, ref, got, outs
     torch.cuda.empty_cache()
+    return CaseData(cid=cid, kind=kind, blk=blk, xs=xs, gys=gys, factors=factors, seed=seed, ref=ref, e32=e32, e_pert=e_pert,
+                    bnd=bnd, twin_seconds=time.time() - t0)
+
+
+def product_run(data, xs=None, frozen=None, freeze_inputs=False, log=None):
+    """one forward of the product block of ``data`` on fresh leaves: (outs, leaves xs).  Parameters named by ``frozen``
+    (a predicate on the name; None: none) and, with ``freeze_inputs``, the inputs do not require a gradient; every
+    ``.grad`` of the block is cleared first.  Training-mode cases draw their masks from the case's seed."""
+    blk = data.blk
+    for n, p in blk.named_parameters():
+        p.requires_grad_(not (frozen is not None and frozen(n)))
+        p.grad = None
+    xs = [x.detach().clone().requires_grad_(not freeze_inputs) for x in (data.xs if xs is None else xs)]
+    if data.seed is not None:
+        torch.manual_seed(data.seed)
+    outs = blk(*xs)
+    return (outs if isinstance(outs, tuple) else (outs,)), xs
+
+
+def collect(data, outs, xs, missing="zeros"):
+    """{"out<i>", "dx<i>", <parameter name>: gradient} of a finished run; a leaf without a gradient gives zeros
+    (``missing="zeros"``: the all-trainable contract, where only an unused parameter has none) or is left out"""
+    got = {f"out{i}": o.detach() for i, o in enumerate(outs)}
+    for i, x in enumerate(xs):
+        if x.grad is not None or missing == "zeros":
+            got[f"dx{i}"] = x.grad
+    for n, p in data.blk.named_parameters():
+        if p.grad is not None:
+            got[n] = p.grad
+        elif missing == "zeros":
+            got[n] = torch.zeros_like(p)
+    return got
+
+
+@functools.lru_cache(maxsize=None)
+def case_result(cid):
+    """(ratios {slice: (err, bound)}, {reduced launch key: launches}, seconds) of case ``cid``; computed once, shared by the case's
+    test and the census"""
+    kind = CASES[cid][0]
+    t0 = time.time()
+    data = case_data(cid)
+    with recording() as log:
+        outs, xs = product_run(data)
+        torch.autograd.backward(outs, data.gys)
+        torch.cuda.synchronize()
+    keys = dict(collections.Counter(reduce_key(k) for k in log if k is not None))
+    got = collect(data, outs, xs)
+    assert sorted(data.ref) == sorted(got)
+    err = twin.slice_errors(kind, got, data.ref)
+    bnd = data.bnd
+    torch.cuda.synchronize()
+    for p in data.blk.parameters():
+        p.grad = None
+    del got, outs
     return {k: (err[k], bnd[k]) for k in err}, keys, time.time() - t0
 
 

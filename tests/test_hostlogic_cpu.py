@@ -219,3 +219,34 @@ def test_derived_parameter_cache_follows_the_parameter_version():
     assert f._derived_params(xw, dw, al)[3] is d2[3]
     f.invalidate_derived_params()
     torch.testing.assert_close(f._derived_params(xw, dw, al)[3], -torch.exp(al.detach()))
+
+
+def test_derived_parameter_cache_keeps_nothing_built_in_inference_mode():
+    """tensors created under torch.inference_mode() cannot be saved for a backward: a first forward there (validation
+    before training) must not leave them in the cache for the training forward that follows, whose SS2DCoreFn saves
+    what ``_derived_params`` returns.  An entry built outside serves inference mode too."""
+    from sigma_amd import ss2d_fused as f
+    f._DERIVED.clear()
+    K, c, d, R, N = 4, 6, 8, 2, 4
+    xw, dw, al = (nn.Parameter(torch.randn(K, c, d)), nn.Parameter(torch.randn(K, d, R)), nn.Parameter(torch.randn(K * d, N)))
+    with torch.inference_mode():
+        inside = f._derived_params(xw, dw, al)
+    assert all(t.is_inference() for t in inside)
+    after = f._derived_params(xw, dw, al)
+    assert not any(t.is_inference() for t in after)
+
+    class Saves(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, *derived):
+            ctx.save_for_backward(x, *derived)
+            return x * derived[3].sum()
+
+        @staticmethod
+        def backward(ctx, g):
+            return (g * ctx.saved_tensors[4].sum(),) + (None,) * 4
+
+    x = torch.randn(3, requires_grad=True)
+    Saves.apply(x, *after).sum().backward()
+    assert x.grad is not None
+    with torch.inference_mode():
+        assert all(a is b for a, b in zip(after, f._derived_params(xw, dw, al)))      # hit: normal tensors serve both
