@@ -282,6 +282,40 @@ typedef struct sigma_ohem_params {
 int sigma_ohem_select(const sigma_ohem_params *params, void *stream);
 int64_t sigma_ohem_workspace_bytes(int64_t rows);
 
+/*   sigma_upsample_ce_fwd / sigma_upsample_ce_bwd  (csrc/deepsup.hip; additions only, the ABI version stays 13)
+ *       nn.CrossEntropyLoss(reduction='mean', ignore_index) of the bilinear x `scale` upsampling (align_corners=False) of
+ *       COARSE channels-last logits: the loss of the deep-supervision heads of MambaDecoder (models/decoders/
+ *       MambaDecoder.py:264-270, models/builder.py:158-166) with the bias-free 1x1 head run BEFORE the interpolation -- the
+ *       two commute.  The interpolated row z^ of `classes` logits of a fine pixel is formed on the fly, never stored.
+ *       Per axis, with n the coarse size (height for rows, width for columns) and s = scale:
+ *           src = max((dst + 0.5) / s - 0.5, 0),  i0 = floor(src),  i1 = min(i0 + 1, n - 1),  lambda = src - i0
+ *       (evaluated in integers: exact taps for every s, exact weights for s a power of two).
+ *           fwd : one fine pixel per thread, rows in the order of the plain kernels: lse[P] = logsumexp(z^(P)); a valid pixel
+ *                 (label != ignore_index, 0 <= label < classes) adds lse - z^_y and 1 to its workgroup's pair of `partial`
+ *                 (SIGMA_CE_BLOCKS pairs, all written).  Columns >= classes of the coarse rows take no part; they may hold NaN.
+ *           bwd : dlogits[b, i, j, c] = g * sum over the valid fine pixels P of wgt(P -> (i, j)) (exp(z^_c(P) - lse(P)) - [c == y(P)]),
+ *                 g = scale_grad[0] (upstream / count, a DEVICE scalar).  Gather: the lanes that own (b, i, j) and a chunk of
+ *                 four classes walk the footprint of the coarse pixel in a fixed order with the forward's index function (at a
+ *                 border i0 == i1 and both weights land on the same pixel).  No atomics, bitwise reproducible; columns
+ *                 [classes, ld) are written with exact zeros, the buffer is fully written.
+ *       SIGMA_OPS_ERR_ARG before any launch: classes < 1 or > 64, ld % 4 != 0, ld < classes, scale outside [1, 32], a
+ *       non-positive size, more than 2^31 - 1 fine pixels, a missing or misaligned pointer (logits / dlogits 16 bytes, labels
+ *       8, the rest 4; fwd needs partial, bwd scale_grad and dlogits).                                                  */
+typedef struct sigma_upsample_ce_params {
+    int32_t batch, height, width;  /* of the COARSE logits                                                   */
+    int32_t scale;                 /* s in [1, 32]: fine size (height * s, width * s)                        */
+    int32_t classes, ld;           /* ld % 4 == 0, ld >= classes, 1 <= classes <= 64                         */
+    int64_t ignore_index;
+    const float *logits;           /* coarse pixel (b, i, j) at logits + ((b * height + i) * width + j) * ld */
+    const int64_t *labels;         /* (batch, height * s, width * s)                                         */
+    float *lse;                    /* one float per fine pixel: fwd out, bwd in                              */
+    float *partial;                /* fwd out: SIGMA_CE_BLOCKS pairs (sum, count)                            */
+    const float *scale_grad;       /* bwd in: device scalar g                                                */
+    float *dlogits;                /* bwd out: coarse, pitch ld, fully written                               */
+} sigma_upsample_ce_params;
+int sigma_upsample_ce_fwd(const sigma_upsample_ce_params *params, void *stream);
+int sigma_upsample_ce_bwd(const sigma_upsample_ce_params *params, void *stream);
+
 /*   sigma_colscale_bwd
  *       backward of  y = a + x * scale with a per-channel `scale` on contiguous channels-last rows (rows, C): the residual
  *       of the decoder block, x * scale1 + op(norm1(x)) and x * scale2 + conv_blk(norm2(x)) (vmamba.py:1800-1805):

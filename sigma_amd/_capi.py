@@ -183,6 +183,16 @@ class OhemParams(ctypes.Structure):
     ]
 
 
+class UpsampleCeParams(ctypes.Structure):
+    """mirror of sigma_upsample_ce_params (include/sigma_ops.h)"""
+    _fields_ = [
+        ("batch", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("scale", ctypes.c_int32),
+        ("classes", ctypes.c_int32), ("ld", ctypes.c_int32), ("ignore_index", ctypes.c_int64),
+        ("logits", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("lse", ctypes.c_void_p), ("partial", ctypes.c_void_p),
+        ("scale_grad", ctypes.c_void_p), ("dlogits", ctypes.c_void_p),
+    ]
+
+
 SIGMA_CE_BLOCKS = 1024      # include/sigma_ops.h
 SIGMA_OHEM_HIST_BLOCKS = 512        # include/sigma_ops.h
 SIGMA_SEG_LDS_HIST_BYTES = 32768    # include/sigma_ops.h
@@ -202,7 +212,7 @@ OPS_SYMBOLS = ("sigma_dwconv3x3_silu_fwd", "sigma_dwconv3x3_silu_bwd", "sigma_cr
                "sigma_plane_dot", "sigma_plane_gate_bwd", "sigma_softmax_ce_fwd", "sigma_softmax_ce_bwd", "sigma_softmax_ce_fwd_ld",
                "sigma_softmax_ce_bwd_ld", "sigma_softmax_ce_opt_fwd", "sigma_softmax_ce_opt_bwd", "sigma_colscale_bwd",
                "sigma_colscale_bwd_ws", "sigma_seg_accumulate", "sigma_seg_argmax_confusion", "sigma_ohem_select",
-               "sigma_softmax_focal_fwd", "sigma_softmax_focal_bwd")
+               "sigma_softmax_focal_fwd", "sigma_softmax_focal_bwd", "sigma_upsample_ce_fwd", "sigma_upsample_ce_bwd")
 # the size queries include/sigma_ops.h declares (int64_t results)
 OPS_AUX_SYMBOLS = ("sigma_dwconv3x3_silu_bwd_workspace_bytes", "sigma_colscale_bwd_workspace_bytes", "sigma_ohem_workspace_bytes")
 
@@ -300,6 +310,8 @@ def load() -> ctypes.CDLL:
             fn.argtypes = [P(CeOptParams), ctypes.c_void_p]
         elif name in ("sigma_softmax_focal_fwd", "sigma_softmax_focal_bwd"):
             fn.argtypes = [P(CeOptParams), ctypes.c_float, ctypes.c_void_p]
+        elif name in ("sigma_upsample_ce_fwd", "sigma_upsample_ce_bwd"):
+            fn.argtypes = [P(UpsampleCeParams), ctypes.c_void_p]
         elif name == "sigma_ohem_select":
             fn.argtypes = [P(OhemParams), ctypes.c_void_p]
         elif name == "sigma_seg_accumulate":

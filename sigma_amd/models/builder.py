@@ -5,6 +5,8 @@ Mirror of /root/reference/models/builder.py:13-166 for the Sigma configurations
 same constructor signature, same attributes (``backbone``, ``decode_head``, ``criterion``,
 ``deep_supervision``), same ``forward(rgb, modal_x, label=None)`` contract (loss when a label
 is given, logits (B, num_classes, H, W) otherwise) and the same state_dict keys.
+``cfg.deep_supervision`` (absent from the reference's configs, so False) switches on the branch the reference has complete
+but never selects (builder.py:102, :141-144, :158-166): three auxiliary heads in the decoder and a four-term loss.
 Other backbones / decoders of the reference (SegFormer, Swin, UPerNet, ...) are other model
 families and out of this path's scope; asking for them raises.
 """
@@ -71,7 +73,9 @@ class EncoderDecoder(nn.Module):
                                       "(every other decoder hits the deep_supervision AttributeError, builder.py:131)")
         logger.info("Using Mamba Decoder")
         from .decoders.MambaDecoder import MambaDecoder
-        self.deep_supervision = False
+        self.deep_supervision = bool(getattr(cfg, "deep_supervision", False))
+        if self.deep_supervision:
+            self._check_deep_size(cfg.image_height, cfg.image_width)
         self.decode_head = MambaDecoder(img_size=[cfg.image_height, cfg.image_width], in_channels=self.channels,
                                         num_classes=cfg.num_classes, embed_dim=self.channels[0],
                                         deep_supervision=self.deep_supervision)
@@ -93,8 +97,19 @@ class EncoderDecoder(nn.Module):
         logger.info("Initing weights ...")
         _init_decoder_weights(self.decode_head, self.norm_layer, cfg.bn_eps, cfg.bn_momentum)
 
+    @staticmethod
+    def _check_deep_size(height, width):
+        """the aux branch of the reference (MambaDecoder.py:242-257) has no resize to the skip size: every stage must halve
+        exactly, down to 1 / 32"""
+        if height % 32 != 0 or width % 32 != 0:
+            raise ValueError(f"deep_supervision needs an image height and width that are multiples of 32, got {height}x{width}")
+
     def encode_decode(self, rgb, modal_x):
-        """backbone -> decoder -> bilinear resize to the input size (builder.py:128-144)."""
+        """backbone -> decoder -> bilinear resize to the input size (builder.py:128-144); with deep supervision the
+        decoder's 4-tuple (x_last, x_output_0, x_output_1, x_output_2) as it is (builder.py:141-144)."""
+        if self.deep_supervision:
+            self._check_deep_size(rgb.shape[2], rgb.shape[3])
+            return self.decode_head(self.backbone(rgb, modal_x))
         feats = self.backbone(rgb, modal_x)
         out = self.decode_head(feats)
         if tuple(out.shape[2:]) == tuple(rgb.shape[2:]):
@@ -103,16 +118,42 @@ class EncoderDecoder(nn.Module):
             return out
         return F.interpolate(out, size=rgb.shape[2:], mode="bilinear", align_corners=False)
 
+    def _forward_deep(self, rgb, modal_x, label):
+        """builder.py:158-166: criterion(x_last) + sum of criterion(x_output_i), every term against the unscaled label.  An
+        aux term takes the fused upsample + loss kernels where they apply (pointwise.upsampled_cross_entropy: the plain
+        criterion, up to 64 classes), else the expansion of its coarse logits and the route of the main logits.  Without a
+        label: x_last alone, the aux heads are not run."""
+        self._check_deep_size(rgb.shape[2], rgb.shape[3])
+        head = self.decode_head
+        feats = self.backbone(rgb, modal_x)
+        if label is None:
+            out = head.up_x4(head.forward_up_features(feats), head.patch_size)
+            return out if out.is_contiguous() else out.contiguous()
+        from ..pointwise import upsampled_cross_entropy
+        from .decoders.MambaDecoder import expand_logits
+        x_last, aux = head.forward_deep(feats)
+        loss = self._loss(x_last, label)
+        for z, s in aux:
+            term = upsampled_cross_entropy(self.criterion, z, s, label) if z.is_cuda else None
+            loss = loss + (term if term is not None else self._loss(expand_logits(z, s), label))
+        return loss
+
     def forward(self, rgb, modal_x, label=None):
+        if getattr(self, "deep_supervision", False):
+            return self._forward_deep(rgb, modal_x, label)
         out = self.encode_decode(rgb, modal_x)
         if label is not None:
-            # cross entropy (any weight / label_smoothing / reduction; 'none' gives (B, H, W)) straight from the channels-last
-            # logits of the classifier GEMM (csrc/pointwise.hip); any other criterion / layout: the criterion itself on the
-            # (B, nc, H, W) view
-            from ..pointwise import cross_entropy, cross_entropy_deterministic
-            loss = cross_entropy(self.criterion, out, label) if out.is_cuda else None
-            if loss is None and torch.are_deterministic_algorithms_enabled():
-                # deterministic mode: torch's nll_loss2d has no deterministic form (sigma_amd/deterministic.py)
-                loss = cross_entropy_deterministic(self.criterion, out, label)
-            return loss if loss is not None else self.criterion(out, label.long())
+            return self._loss(out, label)
         return out if out.is_contiguous() else out.contiguous()     # callers get the reference's (B, nc, H, W) layout
+
+    def _loss(self, out, label):
+        """criterion(out, label) for (B, nc, H, W) logits"""
+        # cross entropy (any weight / label_smoothing / reduction; 'none' gives (B, H, W)) straight from the channels-last
+        # logits of the classifier GEMM (csrc/pointwise.hip); any other criterion / layout: the criterion itself on the
+        # (B, nc, H, W) view
+        from ..pointwise import cross_entropy, cross_entropy_deterministic
+        loss = cross_entropy(self.criterion, out, label) if out.is_cuda else None
+        if loss is None and torch.are_deterministic_algorithms_enabled():
+            # deterministic mode: torch's nll_loss2d has no deterministic form (sigma_amd/deterministic.py)
+            loss = cross_entropy_deterministic(self.criterion, out, label)
+        return loss if loss is not None else self.criterion(out, label.long())

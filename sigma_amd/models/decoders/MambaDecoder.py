@@ -1,8 +1,10 @@
 """Channel-aware Mamba decoder.
 
 Mirror of /root/reference/models/decoders/MambaDecoder.py (PatchExpand :12-30, UpsampleExpand
-:33-51, FinalUpsample_X4 :76-97, Mamba_up :101-148, MambaDecoder :151-280); only the
-deep_supervision=False path that models/builder.py:102 selects is built.
+:33-51, FinalUpsample_X4 :76-97, Mamba_up :101-148, MambaDecoder :151-280).  deep_supervision=False is
+what models/builder.py:102 selects; deep_supervision=True builds the reference's ``norm_ds`` / ``output_ds`` heads (:210-212)
+and runs them on the COARSE tokens: a bias-free 1x1 convolution and a bilinear interpolation commute, so the head is a GEMM
+over h_i x w_i rows and the x16 / x8 / x4 expansion acts on `num_classes` channels instead of 384 / 192 / 96.
 """
 from __future__ import annotations
 
@@ -50,6 +52,47 @@ def _up2(x_nhwc: torch.Tensor) -> torch.Tensor:
         return _Up2xFn.apply(x_nhwc.contiguous())
     y = F.interpolate(x_nhwc.permute(0, 3, 1, 2), scale_factor=2, mode="bilinear", align_corners=False)
     return y.permute(0, 2, 3, 1)
+
+
+_INTERP = {}          # (coarse size, scale, device, dtype) -> the (size * scale, size) interpolation matrix of one axis
+
+
+def interp_matrix(n: int, s: int, device, dtype=torch.float32) -> torch.Tensor:
+    """U (n s, n) with U @ v = the bilinear x s interpolation (align_corners=False) of a vector of n samples:
+    src = max((dst + 0.5) / s - 0.5, 0), i0 = floor(src), i1 = min(i0 + 1, n - 1), lambda = src - i0, row dst holds
+    1 - lambda at i0 and lambda at i1 (both on i0 where the upper tap is clamped onto it).  Built once per key from
+    element-wise ops on `device` (no host round trip, nothing without a deterministic form) and kept."""
+    key = (int(n), int(s), torch.device(device), dtype)
+    U = _INTERP.get(key)
+    if U is None:
+        num = (2 * torch.arange(n * s, device=device) + 1 - s).clamp_min(0)
+        i0 = torch.div(num, 2 * s, rounding_mode="floor")
+        lam = ((num - i0 * 2 * s).to(dtype) / (2 * s))[:, None]
+        i1 = (i0 + 1).clamp_max(n - 1)
+        col = torch.arange(n, device=device)[None, :]
+        U = (col == i0[:, None]).to(dtype) * (1 - lam) + (col == i1[:, None]).to(dtype) * lam
+        # not kept when built inside a graph capture (a capture records the ops, it fills nothing) or under
+        # torch.inference_mode() (inference tensors, which a later training step could not save for its backward; as
+        # ss2d_fused._derived): an entry built outside serves every mode
+        if not (U.is_cuda and torch.cuda.is_current_stream_capturing()) and not torch.is_inference_mode_enabled():
+            _INTERP[key] = U
+    return U
+
+
+def expand_logits(z: torch.Tensor, s: int) -> torch.Tensor:
+    """Bilinear x s (align_corners=False) of channels-last logits z (B, h, w, nc) as two matmuls with the constant
+    matrices of ``interp_matrix``: differentiable, and deterministic in both directions (F.interpolate's backward on the
+    GPU is not).  Returns the (B, nc, h s, w s) VIEW of a channels-last result, which is how the main logits reach the
+    criterion; on the GPU a class count that is no multiple of 4 is expanded at a row pitch of 4 ceil(nc / 4) floats so
+    that the loss kernels take the result (pointwise.cross_entropy)."""
+    B, h, w, nc = z.shape
+    ld = (nc + 3) // 4 * 4 if z.is_cuda else nc
+    if ld != nc:
+        z = F.pad(z, (0, ld - nc))
+    Uh, Uw = interp_matrix(h, s, z.device, z.dtype), interp_matrix(w, s, z.device, z.dtype)
+    t = torch.matmul(Uh, z.reshape(B, h, w * ld))                      # (B, H, w ld)
+    t = torch.matmul(Uw, t.reshape(B * h * s, w, ld))                  # (B H, W, ld)
+    return t.view(B, h * s, w * s, ld)[..., :nc].permute(0, 3, 1, 2)
 
 
 class PatchExpand(nn.Module):
@@ -132,15 +175,13 @@ class MambaDecoder(nn.Module):
                  attn_drop_rate=0.0, drop_path_rate=0.1, norm_layer=LayerNorm, use_checkpoint=False,
                  deep_supervision=False, **kwargs):
         super().__init__()
-        if deep_supervision:
-            raise NotImplementedError("models/builder.py:102 always builds MambaDecoder with deep_supervision=False")
         depths = list(depths)
         self.num_classes = num_classes
         self.num_layers = len(depths)
         self.mlp_ratio = mlp_ratio
         self.patch_size = patch_size
         self.patches_resolution = [img_size[0] // patch_size, img_size[1] // patch_size]
-        self.deep_supervision = False
+        self.deep_supervision = bool(deep_supervision)
         dpr = [r.item() for r in torch.linspace(0, drop_path_rate, sum(depths))]
         self.layers_up = nn.ModuleList()
         for i in range(self.num_layers):
@@ -157,19 +198,38 @@ class MambaDecoder(nn.Module):
                                  use_checkpoint=use_checkpoint)
             self.layers_up.append(layer)
         self.norm_up = norm_layer(embed_dim)
+        if self.deep_supervision:                                 # MambaDecoder.py:210-212: same names, same shapes
+            dims = [embed_dim * 2 ** (self.num_layers - 2 - i) for i in range(self.num_layers - 1)]
+            self.norm_ds = nn.ModuleList([norm_layer(d) for d in dims])
+            self.output_ds = nn.ModuleList([nn.Conv2d(d, num_classes, kernel_size=1, bias=False) for d in dims])
         self.up = FinalUpsample_X4(input_resolution=tuple(self.patches_resolution), patch_size=4, dim=embed_dim)
         self.output = nn.Conv2d(embed_dim, num_classes, kernel_size=1, bias=False)
 
-    def forward_up_features(self, inputs):
-        """inputs: 4 fused maps (B, C_i, H_i, W_i), finest first."""
+    def forward_up_features(self, inputs, collect=None):
+        """inputs: 4 fused maps (B, C_i, H_i, W_i), finest first.  `collect` (deep supervision, MambaDecoder.py:242-257): a
+        list that receives norm_ds[i](y) after levels 0, 1, 2, channels-last."""
         y = self.layers_up[0](inputs[3].permute(0, 2, 3, 1))
+        if collect is not None:
+            collect.append(self.norm_ds[0](y))
         for i in range(1, self.num_layers):
             skip = inputs[3 - i]
             H, W = skip.shape[2], skip.shape[3]
             if y.shape[1] != H or y.shape[2] != W:               # odd sizes (PST900: 46 rows -> 45)
                 y = F.interpolate(y.permute(0, 3, 1, 2), size=(H, W), mode="bilinear", align_corners=False).permute(0, 2, 3, 1)
             y = self.layers_up[i](y + skip.permute(0, 2, 3, 1))
+            if collect is not None and i < self.num_layers - 1:
+                collect.append(self.norm_ds[i](y))
         return self.norm_up(y)
+
+    def _head(self, x, conv):
+        """the bias-free 1x1 convolution `conv` on channels-last fp32 GPU tokens x (B, H, W, C) as a GEMM: (B, H, W, nc)"""
+        from ...gemm import classifier, classifier_ok, gemm_mode, linear
+        if gemm_mode() == "split3" and classifier_ok(x.reshape(-1, x.shape[-1]), conv.weight):
+            # a class count that is no multiple of 4 (MFNet 9, PST900 5, SUN-RGBD 37): logits at a row pitch of
+            # 4 ceil(nc / 4) floats, so the classifier's three GEMMs and the loss stay on the project's kernels
+            return classifier(x, conv.weight)
+        w2 = conv.weight.view(conv.weight.shape[0], -1)
+        return linear(x, w2) if gemm_mode() == "split3" else F.linear(x, w2)
 
     def up_x4(self, x, pz):
         x = self.up(x)                                            # (B, 4H, 4W, C)
@@ -179,15 +239,26 @@ class MambaDecoder(nn.Module):
             # and a weight gradient with the strides of a (nc, C, 1, 1) view that DistributedDataParallel has to re-lay
             # (the "Grad strides do not match bucket view strides" warning of round 2).  The logits come back as a
             # (B, nc, 4H, 4W) VIEW of the channels-last result.
-            from ...gemm import classifier, classifier_ok, gemm_mode, linear
-            if gemm_mode() == "split3" and classifier_ok(x.reshape(-1, x.shape[-1]), self.output.weight):
-                # a class count that is no multiple of 4 (MFNet 9, PST900 5, SUN-RGBD 37): logits at a row pitch of
-                # 4 ceil(nc / 4) floats, so the classifier's three GEMMs and the loss stay on the project's kernels
-                return classifier(x, self.output.weight).permute(0, 3, 1, 2)
-            w2 = self.output.weight.view(self.output.weight.shape[0], -1)
-            y = linear(x, w2) if gemm_mode() == "split3" else F.linear(x, w2)
-            return y.permute(0, 3, 1, 2)
+            return self._head(x, self.output).permute(0, 3, 1, 2)
         return self.output(x.permute(0, 3, 1, 2))
 
+    def forward_deep(self, inputs):
+        """deep supervision: (x_last, [(coarse logits (B, h_i, w_i, nc), scale_i)] for the three heads) -- output_ds[i] on
+        norm_ds[i](y) at the resolution the decoder has it, with the integer scale (16, 8, 4) up to x_last's size"""
+        maps = []
+        x_last = self.up_x4(self.forward_up_features(inputs, collect=maps), self.patch_size)
+        aux = []
+        for i, m in enumerate(maps):
+            if m.is_cuda and m.dtype == torch.float32:
+                z = self._head(m, self.output_ds[i])
+            else:
+                z = F.linear(m, self.output_ds[i].weight.view(self.num_classes, -1))
+            aux.append((z, self.patch_size * 2 ** (self.num_layers - 2 - i)))
+        return x_last, aux
+
     def forward(self, inputs):
-        return self.up_x4(self.forward_up_features(inputs), self.patch_size)
+        if not self.deep_supervision:
+            return self.up_x4(self.forward_up_features(inputs), self.patch_size)
+        # MambaDecoder.py:264-270: (x_last, x_output_0, x_output_1, x_output_2), each (B, nc, H, W)
+        x_last, aux = self.forward_deep(inputs)
+        return (x_last, *(expand_logits(z, s) for z, s in aux))

@@ -15,6 +15,10 @@
 ``focal_cross_entropy``  FocalLoss2d (utils/loss_opr.py:12-23) with a run-time exponent on the same logits: the focal kind
                    of the same kernels (``SoftmaxFocalFn``).
 
+``upsampled_cross_entropy``  the plain mean cross entropy of the bilinear x s upsampling of COARSE channels-last logits --
+                   the loss of a deep-supervision head (MambaDecoder.forward_deep) -- with the interpolation inside the
+                   loss kernels of csrc/deepsup.hip: no full-size logits exist in either direction (``UpsampledCEFn``).
+
 The three front-ends share their checks (``_loss_rows``); the three Functions with options share one forward
 (``_rows_forward`` / ``_rows_finish``: buffers, parameters, saved tensors, reduction) and one backward (``_dlogits``), and
 differ in the entry point they name.
@@ -360,6 +364,85 @@ class SoftmaxFocalFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return (_dlogits(ctx, g),) + (None,) * 7
+
+
+class UpsampledCEFn(torch.autograd.Function):
+    """mean over the non-ignored pixels of -log softmax(upsample_s(logits))[label] for coarse logits2 (B h w, classes) at a
+    pitch of `ld` floats and labels (B, h s, w s): sigma_upsample_ce_fwd / _bwd (csrc/deepsup.hip).  Saved for the backward:
+    the coarse logits, the labels and one lse per fine pixel.  Nothing is read back; nothing labelled gives a NaN loss
+    (0 / 0) and an all-zero gradient, as ``SoftmaxCEFn`` / ``_dlogits`` do."""
+
+    @staticmethod
+    def _params(logits2, labels, lse, dims, ignore_index, ld):
+        p = _capi.UpsampleCeParams()
+        p.batch, p.height, p.width, p.scale = dims
+        p.classes, p.ld, p.ignore_index = logits2.shape[1], ld, int(ignore_index)
+        p.logits, p.labels, p.lse = logits2.data_ptr(), labels.data_ptr(), lse.data_ptr()
+        return p
+
+    @staticmethod
+    def forward(ctx, logits2, labels, ignore_index, ld, dims):
+        dev = logits2.device
+        lse = torch.empty(labels.shape, device=dev, dtype=torch.float32)
+        partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=dev, dtype=torch.float32)
+        p = UpsampledCEFn._params(logits2, labels, lse, dims, ignore_index, ld)
+        p.partial = partial.data_ptr()
+        with torch.cuda.device(dev):
+            _capi.check(_capi.load().sigma_upsample_ce_fwd(ctypes.byref(p), _stream()), "upsample_ce_fwd")
+        tot = partial.sum(0)
+        ctx.save_for_backward(logits2, labels, lse, tot)
+        ctx.ignore_index, ctx.ld, ctx.dims = int(ignore_index), ld, dims
+        return tot[0] / tot[1]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits2, labels, lse, tot = ctx.saved_tensors
+        rows, nc = logits2.shape
+        ld = ctx.ld
+        grad = g.float().reshape(1)
+        grad = torch.where(tot[1:2] > 0, grad / tot[1:2], torch.zeros_like(grad)).contiguous()      # nothing labelled: zeros
+        full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
+        p = UpsampledCEFn._params(logits2, labels, lse, ctx.dims, ctx.ignore_index, ld)
+        p.scale_grad, p.dlogits = grad.data_ptr(), full.data_ptr()
+        with torch.cuda.device(logits2.device):
+            _capi.check(_capi.load().sigma_upsample_ce_bwd(ctypes.byref(p), _stream()), "upsample_ce_bwd")
+        if ld != nc:
+            # as SoftmaxCEFn: the classifier's backward claims the whole padded buffer (_handoff.py)
+            offer_padded_grad_buffer(full)
+            full = full[:, :nc]
+        return full, None, None, None, None
+
+
+UPSAMPLED_CE_MAX_CLASSES = 64      # include/sigma_ops.h: sigma_upsample_ce_params.classes
+UPSAMPLED_CE_MAX_SCALE = 32
+
+
+def upsampled_cross_entropy(criterion, coarse: torch.Tensor, scale: int, label: torch.Tensor):
+    """criterion(upsample(coarse), label) for the bilinear x `scale` upsampling (align_corners=False) of channels-last
+    logits `coarse` (B, h, w, classes), without the upsampled tensor (``UpsampledCEFn``) -- or None when this route does
+    not apply: anything but the plain criterion (``criterion_route(...) == "plain"``: weights, smoothing, 'sum' / 'none',
+    OHEM and focal take the expansion, MambaDecoder.expand_logits), logits that are not fp32 GPU rows at a pitch
+    ``_row_pitch`` accepts (a multiple of 4, 16-byte aligned, every row's last 16-byte chunk inside the storage), more than 64 classes, a scale outside [1, 32], a label that
+    is not on the logits' device with the shape (B, h scale, w scale).  Labels outside [0, classes) count as ignored, as in
+    ``cross_entropy``."""
+    if coarse.dim() != 4 or label.dim() != 3 or not (coarse.is_cuda and coarse.dtype == torch.float32):
+        return None
+    B, h, w, nc = coarse.shape
+    scale = int(scale)
+    if criterion_route(criterion, coarse.device, nc) != "plain" or not 1 <= nc <= UPSAMPLED_CE_MAX_CLASSES:
+        return None
+    if not 1 <= scale <= UPSAMPLED_CE_MAX_SCALE or label.device != coarse.device or tuple(label.shape) != (B, h * scale, w * scale):
+        return None
+    ld = nc if coarse.is_contiguous() and nc % 4 == 0 else _row_pitch(coarse)
+    if ld is None or ld % 4 != 0 or ld < nc or coarse.data_ptr() % 16 != 0 or coarse.numel() == 0 or label.numel() >= 2 ** 31:
+        return None
+    # the kernels load whole 16-byte chunks: the last row is read up to column 4 ceil(nc / 4).  A pitch inferred for a
+    # single row (``_row_pitch``: strides say nothing there) must lie inside the tensor's storage, else a packed
+    # (1, 1, 1, nc) tensor with nc % 4 != 0 would be read past its end
+    floats = (B * h * w - 1) * ld + (nc + 3) // 4 * 4
+    if coarse.storage_offset() + floats > coarse.untyped_storage().nbytes() // coarse.element_size():
+        return None
+    return UpsampledCEFn.apply(coarse.reshape(-1, nc), label.long().contiguous(), criterion.ignore_index, ld, (B, h, w, scale))
 
 
 CE_REDUCTIONS = ("mean", "sum", "none")

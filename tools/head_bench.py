@@ -41,6 +41,21 @@ b  ``utils.loss_opr.FocalLoss2d`` (exponent 2) on the kernel route (``pointwise.
 c  the torch formulation of the class on the (B, nc, H, W) view: softmax, log_softmax, the product, nll_loss.
 a and b move the same bytes, so b / a is what the per-row transcendentals cost.  Gate: b / a <= 1.10 at (40, 40), unless the
 inter-quartile range of a is itself above 10 % of its median -- then the line says so and reports the spread instead.
+
+    python tools/head_bench.py --deepsup --run 1 --out profiles/deepsup_mi355x.jsonl
+    python tools/head_bench.py --deepsup --run 2 --append --out profiles/deepsup_mi355x.jsonl
+
+``--deepsup`` times the loss term of one deep-supervision head (forward + backward on given COARSE channels-last logits, no
+classifier) at the three real shapes -- batch 8, 30x40 x16, 60x80 x8, 120x160 x4, all up to 480x640 -- with 40 classes
+(pitch 40) and with 9 (pitch 12), two routes alternating in one process:
+fused    ``pointwise.upsampled_cross_entropy`` (csrc/deepsup.hip: the interpolation inside the loss kernels);
+general  the expansion of the coarse logits to full size with two constant interpolation matrices (torch matmul) and the
+         plain loss Function on the result (``pointwise.cross_entropy``), i.e. what the model does where the fused route
+         declines.
+One line per (shape, classes) and one per class count for the sum over the three heads.  ``fused_beats_general``: the
+difference of the medians is larger than the larger of the two inter-quartile ranges.  ``bytes``: what each route moves
+algorithmically (see ``deepsup_bytes``).  A process runs at its own level (0.04 - 0.06 ms apart on these streams), which the
+spread inside a process does not see: ``--run N`` tags the lines and ``--append`` adds a second process to the same file.
 """
 import argparse
 import json
@@ -238,6 +253,75 @@ def focal_main(a, dev):
     return lines
 
 
+DEEPSUP_SHAPES = [(8, 30, 40, 16), (8, 60, 80, 8), (8, 120, 160, 4)]
+
+
+def deepsup_bytes(B, h, w, s, ld):
+    """fused: the labels (8 bytes per fine pixel) and the coarse logits read in both directions, lse (4 bytes per fine
+    pixel) written once and read once, the coarse gradient written.  general: five passes over the full-size logits -- the
+    expansion writes them, the loss reads them in both directions and writes their gradient, the expansion's backward reads
+    it -- plus the same labels and lse and the coarse tensors at both ends."""
+    P, M = B * h * s * w * s, B * h * w
+    small = 2 * 4 * M * ld + 4 * M * ld
+    return {"fused": 2 * 8 * P + 2 * 4 * P + small, "general": 5 * 4 * P * ld + 2 * 8 * P + 2 * 4 * P + small}
+
+
+def deepsup_main(a, dev):
+    from sigma_amd.models.decoders.MambaDecoder import expand_logits
+    from sigma_amd.pointwise import cross_entropy, upsampled_cross_entropy
+    plain = nn.CrossEntropyLoss(reduction="mean", ignore_index=IGNORE)
+    tag = {} if a.run is None else {"run": a.run}
+    lines = []
+    for nc, ld in ((40, 40), (9, 12)):
+        total = {"fused": [0.0] * a.reps, "general": [0.0] * a.reps}
+        for B, h, w, s in DEEPSUP_SHAPES:
+            g = torch.Generator().manual_seed(1234)
+            buf = torch.zeros(B, h, w, ld)
+            buf[..., :nc] = torch.randn(B, h, w, nc, generator=g) * 3.0
+            buf = buf.to(dev).requires_grad_()
+            label = torch.randint(0, nc, (B, h * s, w * s), generator=g)
+            label[torch.rand(label.shape, generator=g) < 0.1] = IGNORE
+            label = label.to(dev)
+            routes = {"fused": lambda: upsampled_cross_entropy(plain, buf[..., :nc], s, label),
+                      "general": lambda: cross_entropy(plain, expand_logits(buf[..., :nc], s), label)}
+            times = {k: [] for k in routes}
+            losses, grads = {}, {}
+            for i in range(a.warmup + a.reps):
+                for k, fn in routes.items():
+                    buf.grad = None
+                    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    t0.record()
+                    loss = fn()
+                    loss.backward()
+                    t1.record()
+                    t1.synchronize()
+                    if i >= a.warmup:
+                        times[k].append(t0.elapsed_time(t1))
+                    losses[k], grads[k] = float(loss.detach()), buf.grad
+            assert type(routes["fused"]().grad_fn).__name__.startswith("UpsampledCEFn")
+            assert type(routes["general"]().grad_fn).__name__.startswith("SoftmaxCEFn")
+            for k in total:
+                total[k] = [x + y for x, y in zip(total[k], times[k])]
+            sp = {k: spread(v) for k, v in times.items()}
+            gap = sp["general"]["median_ms"] - sp["fused"]["median_ms"]
+            line = {**tag, "mode": "deepsup", "coarse": [B, h, w], "scale": s, "classes": nc, "ld": ld, "reps": a.reps, "warmup": a.warmup,
+                    "fused": sp["fused"], "general": sp["general"], "general_over_fused": round(sp["general"]["median_ms"] / sp["fused"]["median_ms"], 3),
+                    "fused_beats_general": bool(gap > max(sp["fused"]["iqr_ms"], sp["general"]["iqr_ms"])),
+                    "loss_fused": losses["fused"], "loss_general": losses["general"],
+                    "max_grad_diff": float((grads["fused"] - grads["general"]).abs().max()), "max_grad": float(grads["general"].abs().max()),
+                    "bytes": deepsup_bytes(B, h, w, s, ld), "device": torch.cuda.get_device_name(0)}
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+            del buf, label, grads
+            torch.cuda.empty_cache()
+        sp = {k: spread(v) for k, v in total.items()}
+        line = {**tag, "mode": "deepsup", "coarse": "sum of the three heads", "classes": nc, "ld": ld, "reps": a.reps, "fused": sp["fused"],
+                "general": sp["general"], "general_over_fused": round(sp["general"]["median_ms"] / sp["fused"]["median_ms"], 3)}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    return lines
+
+
 def spread(ts):
     q = statistics.quantiles(ts, n=4)
     return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4),
@@ -252,14 +336,17 @@ def main():
     ap.add_argument("--criterion", nargs="+", default=["plain"], choices=["plain", "weight", "weight_eps"])
     ap.add_argument("--ohem", action="store_true", help="time the OHEM loss against the plain loss and a torch composition")
     ap.add_argument("--focal", action="store_true", help="time the focal loss against the plain loss and the torch formulation")
+    ap.add_argument("--deepsup", action="store_true", help="time the fused upsample + loss of a deep-supervision head against the expansion")
+    ap.add_argument("--run", type=int, default=None, help="--deepsup: tag every line with this run number (one process per run)")
+    ap.add_argument("--append", action="store_true", help="--deepsup: add the lines to --out instead of replacing it")
     a = ap.parse_args()
     if a.reps < 30:
         ap.error("at least 30 repetitions")
     dev = torch.device("cuda", 0)
-    if a.ohem or a.focal:
-        lines = ohem_main(a, dev) if a.ohem else focal_main(a, dev)
+    if a.ohem or a.focal or a.deepsup:
+        lines = ohem_main(a, dev) if a.ohem else focal_main(a, dev) if a.focal else deepsup_main(a, dev)
         if a.out:
-            with open(a.out, "w") as f:
+            with open(a.out, "a" if a.deepsup and a.append else "w") as f:
                 for line in lines:
                     f.write(json.dumps(line) + "\n")
         return
