@@ -55,11 +55,16 @@ class DropPath(nn.Module):
         super().__init__()
         self.drop_prob = float(drop_prob)
 
+    def draw_mask(self, x: torch.Tensor, keep: float) -> torch.Tensor:
+        """the 0/1 keep mask of one call, one value per sample, shape (B, 1, ..., 1).  The only place this module draws:
+        forward, add_to and draw scale it by 1/keep and fold it into their branch themselves."""
+        return x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.drop_prob == 0.0 or not self.training:
             return x
         keep = 1.0 - self.drop_prob
-        mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
+        mask = self.draw_mask(x, keep)
         if keep > 0.0:
             mask.div_(keep)
         return x * mask
@@ -70,7 +75,7 @@ class DropPath(nn.Module):
         if self.drop_prob == 0.0 or not self.training:
             return residual + x
         keep = 1.0 - self.drop_prob
-        mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
+        mask = self.draw_mask(x, keep)
         if keep > 0.0:
             mask.div_(keep)
         return torch.addcmul(residual, x, mask)
@@ -81,7 +86,7 @@ class DropPath(nn.Module):
         if self.drop_prob == 0.0 or not self.training:
             return None
         keep = 1.0 - self.drop_prob
-        mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
+        mask = self.draw_mask(x, keep)
         if keep > 0.0:
             mask.div_(keep)
         return mask

@@ -43,17 +43,25 @@ CASES = [
 
 
 class GivenDropPath(torch.nn.Module):
-    """x * factors[b] in training mode (factors = mask / keep probability, set by the caller), identity otherwise"""
+    """x * factors[b] in training mode (factors = mask / keep probability, set by the caller), identity otherwise.
+    ``factors``: one (B,) tensor applied at every call, or a list with one (B,) tensor per call of a step -- the reference's
+    encoder calls each of its DropPath modules twice per step, in its RGB pass and in its X pass.  ``calls`` counts the
+    training-mode calls; whoever hands in a list resets it before each step."""
 
     def __init__(self, drop_prob=0.0, scale_by_keep=True):
         super().__init__()
         self.drop_prob = drop_prob
         self.factors = None
+        self.calls = 0
 
     def forward(self, x):
-        if not self.training or self.factors is None:
+        if not self.training:
             return x
-        return x * self.factors.to(x.dtype).reshape(-1, *([1] * (x.dim() - 1)))
+        call, self.calls = self.calls, self.calls + 1
+        if self.factors is None:
+            return x
+        f = self.factors[call] if isinstance(self.factors, (list, tuple)) else self.factors
+        return x * f.to(x.dtype).reshape(-1, *([1] * (x.dim() - 1)))
 
 
 def case_tensors(name, kind, shape):

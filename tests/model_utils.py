@@ -1,4 +1,5 @@
 import ast
+import contextlib
 import os
 import sys
 import types
@@ -57,7 +58,120 @@ def assert_logits_close(a: torch.Tensor, b: torch.Tensor, rel: float):
     torch.testing.assert_close(a.double().cpu(), b.double().cpu(), rtol=10 * rel, atol=rel * float(b.abs().max()))
 
 
-def compare_with_reference_fixtures(case: str, gemm_mode: str, frozen=None, grad_scale: float = 1.0):
+def load_mask_table(z):
+    """The stochastic-depth masks of a training-mode fixture (tests/golden/make_golden_model_train.py):
+    ({DropPath module name: [0/1 mask (B,) of each call the REFERENCE makes per step]}, {name: the reference's drop_prob}).
+    The reference runs its encoder twice (RGB pass, X pass): its encoder modules have two calls, all others one."""
+    names = [str(n) for n in z["dp_names"]]
+    table = {n: [torch.from_numpy(z["masks"][i, c].astype(np.float32)) for c in range(int(z["dp_calls"][i]))]
+             for i, n in enumerate(names)}
+    return table, dict(zip(names, (float(p) for p in z["dp_probs"])))
+
+
+def swap_modalities(table):
+    """negative control: the RGB and the X call of every encoder module exchanged"""
+    return {n: (m[::-1] if len(m) == 2 else m) for n, m in table.items()}
+
+
+def shift_stage3(table):
+    """negative control: the encoder's stage-3 blocks take the masks of their neighbour (rotation by one block)"""
+    keys = sorted(n for n in table if ".vssm.layers.3.blocks." in n)
+    assert len(keys) >= 2
+    return {**table, **{k: table[keys[(i + 1) % len(keys)]] for i, k in enumerate(keys)}}
+
+
+@contextlib.contextmanager
+def inject_masks(model, table, probs, may_skip=()):
+    """For ONE forward of the product model: DropPath.draw_mask -- the draw alone -- returns the fixture's masks, while the
+    module's own rate, its 1 / keep scaling and the fold into the branch run as always.  The product runs the encoder once on
+    cat(RGB, X): an encoder module gets cat(call 0, call 1), every other module call 0.  Raises if a module draws more than
+    once, draws for another batch size, is not in the table, or -- on leaving -- if a module whose reference rate is above
+    0 never drew (names in ``may_skip`` excepted).  Yields {name: number of draws}."""
+    from sigma_amd.models.encoders.vmamba import DropPath
+    names = {id(m): n for n, m in model.named_modules() if isinstance(m, DropPath)}
+    asked = {n: 0 for n in names.values()}
+
+    def given(self, x, keep):
+        n = names.get(id(self))
+        if n is None or n not in table:
+            raise AssertionError(f"DropPath module {n!r} draws and is not in the mask table")
+        asked[n] += 1
+        if asked[n] > 1:
+            raise AssertionError(f"{n} draws more often than the table provides")
+        mask = torch.cat(table[n])
+        if mask.numel() != x.shape[0]:
+            raise AssertionError(f"{n} draws for {x.shape[0]} samples, the table has {mask.numel()}")
+        return mask.to(device=x.device, dtype=x.dtype).reshape((x.shape[0],) + (1,) * (x.dim() - 1))
+
+    saved = DropPath.draw_mask
+    DropPath.draw_mask = given
+    try:
+        yield asked
+    finally:
+        DropPath.draw_mask = saved
+    idle = sorted(n for n, k in asked.items() if k == 0 and probs.get(n, 0.0) > 0 and n not in may_skip)
+    if idle:
+        raise AssertionError(f"never asked for a mask: {idle[:4]}")
+
+
+def product_block(model, drop_path_name):
+    """the block that owns DropPath module `drop_path_name`"""
+    return model.get_submodule(drop_path_name.rsplit(".", 1)[0])
+
+
+def train_structure_violations(model, z, step):
+    """What a dropped sample must look like EXACTLY, whatever the arithmetic: ``step()`` runs one forward + backward of
+    `model` under the fixture's masks (inject_masks); returns the list of violations.
+      * encoder block (x + factor * branch(x)), sample dropped: the block's output equals its input bit for bit;
+        sample kept: it does not
+      * encoder block with every sample dropped (condition b): every parameter gradient of the block is exactly 0.0
+      * decoder block, sample dropped: its SS2D branch delivers exactly 0 for that sample (the block itself still scales
+        the residual and adds its convolution branch for every sample: there is no identity to compare with)"""
+    table, probs = load_mask_table(z)
+    seen, hooks, hooked = {}, [], set()
+    for n, m in table.items():
+        if probs[n] == 0 or ".cross_mamba." in n or ".channel_attn_mamba." in n:
+            continue
+        blk = product_block(model, n)
+        hooked.add(n)
+        if ".vssm." in n:
+            hooks.append(blk.register_forward_hook(lambda mod, inp, out, n=n: seen.__setitem__(n, (inp[0].detach().clone(), out.detach().clone()))))
+        else:
+            hooks.append(blk.op.register_forward_hook(lambda mod, inp, out, n=n: seen.__setitem__(n, (None, out.detach().clone()))))
+    try:
+        step()
+    finally:
+        for h in hooks:
+            h.remove()
+    bad, dropped, all_dropped = [], 0, 0
+    for n, m in table.items():
+        if n not in seen:
+            if n in hooked:
+                bad.append((n, "block never ran"))
+            continue
+        mask = torch.cat(m) if ".vssm." in n else m[0]
+        inp, out = seen[n]
+        for b, keep in enumerate(mask.tolist()):
+            if ".vssm." in n:
+                same = torch.equal(out[b], inp[b])
+                if same != (keep == 0):
+                    bad.append((n, b, "kept sample passed through unchanged" if same else "dropped sample changed"))
+            else:
+                zero = not bool(out[b].any())
+                if zero != (keep == 0):
+                    bad.append((n, b, "kept sample has a zero branch" if zero else "dropped sample has a non-zero branch"))
+            dropped += keep == 0
+        if ".vssm." in n and not mask.any():
+            all_dropped += 1
+            for pn, p in product_block(model, n).named_parameters():
+                if p.grad is None or bool(p.grad.any()):
+                    bad.append((n, pn, "gradient of a block that dropped every sample is not exactly 0"))
+    assert dropped >= 8 and all_dropped >= 1, (dropped, all_dropped)      # the fixture's conditions (a), (b), (d) were met
+    return bad
+
+
+def compare_with_reference_fixtures(case: str, gemm_mode: str, frozen=None, grad_scale: float = 1.0, masks=None,
+                                    prepare=None, may_skip=(), violations=None):
     """The body of tests/test_model_gpu.py::test_logits_loss_and_grads_match_reference_fixtures (also run under torch's
     deterministic flag by tests/deterministic_model_worker.py): logits, loss, gradient digests and the element-wise
     gradients of the scan-adjacent parameters of fixture `case` against the reference's own model.
@@ -66,21 +180,60 @@ def compare_with_reference_fixtures(case: str, gemm_mode: str, frozen=None, grad
     a gradient, must come out with ``.grad is None`` and are left out of the comparison; every other name is compared as
     always.  ``grad_scale`` (a whole number): the loss is run forward + backward that many times without clearing the
     gradients, which are compared with ``grad_scale`` times the fixture's.  Tolerances are the same in every
-    configuration.  Returns (model, the last loss) for callers that go on with the model."""
+    configuration.  Returns (model, the last loss) for callers that go on with the model.
+
+    ``masks`` (a table as of load_mask_table, tests/test_model_train_gpu.py): `case` is a training-mode fixture; the model
+    runs in ``train()`` and every forward draws its stochastic-depth masks from the table (inject_masks; ``may_skip`` goes
+    there), which may differ from the fixture's own for a negative control.  A deep-supervision fixture builds the model
+    with the flag and compares its four loss terms too.  ``prepare(model)`` runs once on the built model.  ``violations``
+    (a list): what misses a tolerance is appended to it instead of failing an assertion."""
     passes = int(round(grad_scale))
     assert passes >= 1 and passes == grad_scale, grad_scale
     meta, z = load_model_golden(case)
-    model = build_model(meta["backbone"], meta["num_classes"], meta["H"], meta["W"]).cuda().eval()
+
+    def check(ok, what):
+        if violations is None:
+            assert ok, what
+        elif not ok:
+            violations.append(what)
+
+    def close(a, b, rel, what):
+        if violations is None:
+            assert_logits_close(a, b, rel)
+        else:
+            try:
+                assert_logits_close(a, b, rel)
+            except AssertionError as e:
+                violations.append((what, str(e)[:200]))
+
+    deep = any(".norm_ds." in str(n) for n in z["grad_names"])
+    if deep:
+        from tests.deepsup_utils import build_ds_model
+        model = build_ds_model(meta["num_classes"], meta["H"], meta["W"]).cuda()
+    else:
+        model = build_model(meta["backbone"], meta["num_classes"], meta["H"], meta["W"]).cuda()
+    model.train(masks is not None)
+    if prepare is not None:
+        prepare(model)
+    probs = load_mask_table(z)[1] if masks is not None else None
+    given = (lambda: inject_masks(model, masks, probs, may_skip)) if masks is not None else contextlib.nullcontext
     if frozen is not None:
         for n, p in model.named_parameters():
             p.requires_grad_(not frozen(n))
     rgb, x, label = fill.make_inputs(meta["batch"], meta["H"], meta["W"], meta["num_classes"])
-    with torch.no_grad():
+    with torch.no_grad(), given():
         logits = model(rgb.cuda(), x.cuda())
-    assert_logits_close(logits, torch.from_numpy(z["logits"]), 1e-3)
+    close(logits, torch.from_numpy(z["logits"]), 1e-3, "logits")
+    if deep:
+        with torch.no_grad(), given():
+            outs = model.encode_decode(rgb.cuda(), x.cuda())
+            terms = [float(model.criterion(o, label.cuda())) for o in outs]
+        for i, (t, r) in enumerate(zip(terms, z["terms"])):
+            check(abs(t - float(r)) < 1e-3, ("loss term", i, t, float(r)))
     for _ in range(passes):
-        loss = model(rgb.cuda(), x.cuda(), label.cuda())
-        assert abs(loss.item() - float(z["loss"])) < 1e-3
+        with given():
+            loss = model(rgb.cuda(), x.cuda(), label.cuda())
+        check(abs(loss.item() - float(z["loss"])) < 1e-3, ("loss", loss.item(), float(z["loss"])))
         loss.backward()
     names, ref = list(z["grad_names"]), z["grad_digest"]
     got = dict(model.named_parameters())
@@ -96,7 +249,7 @@ def compare_with_reference_fixtures(case: str, gemm_mode: str, frozen=None, grad
         tol = 5e-3 * (abs(r[1]) + 1e-6)              # relative to the L1 mass of the gradient
         if not (abs(d[0] - r[0]) < tol and abs(d[1] - r[1]) < tol and abs(d[2] - r[2]) < tol):
             bad.append((n, d.tolist(), r.tolist()))
-    assert not bad, bad[:5]
+    check(not bad, bad[:5])
     # element-wise comparison for the scan-adjacent parameters of ten blocks (every kind of block):
     # x_proj / dt_proj weights and biases, A_logs, Ds, out_norm, conv bias, decoder scales
     worst = []
@@ -113,5 +266,5 @@ def compare_with_reference_fixtures(case: str, gemm_mode: str, frozen=None, grad
         err = float((g - r).abs().max()) / scale
         if err > (5e-3 if gemm_mode == "fp32" else 1e-2):
             worst.append((str(n), err, scale))
-    assert not worst, worst[:5]
+    check(not worst, worst[:5])
     return model, loss.detach()
