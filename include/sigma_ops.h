@@ -175,7 +175,16 @@ int sigma_softmax_ce_bwd(const float *logits, const int64_t *labels, const float
  *           bwd : columns < classes as above; columns [classes, ld) are WRITTEN with exact zeros (chosen by index), so
  *                 GEMMs may read whole rows of ld.
  *       A label in [classes, ld) is out of range like any label >= classes: the pixel is ignored.
- *       Rows of up to 64 classes (16 chunks of 16 bytes) are held in registers, longer ones are walked.               */
+ *       Rows of up to 64 classes (16 chunks of 16 bytes) are held in registers, longer ones are walked.
+ *       Non-finite logits, for every entry point of the family (plain, option, focal; both forms, either pitch):
+ *           a -inf logit away from the label is a MASKED CLASS: it adds exp(-inf) = 0 to the sum, lse and the loss are
+ *           those of the remaining classes and its dlogit is exactly zero -- wherever it sits, a first 16-byte chunk that
+ *           is masked whole included (without label smoothing: the smoothing term sums w_c x_c over every class);
+ *           a row that holds NaN or +inf, is -inf throughout or has -inf at its label touches only ITS OWN lse, row_loss
+ *           and dlogits row -- every other row keeps its bits -- and reaches the partial pair of its workgroup only if
+ *           it is labelled: an ignored row adds nothing, whatever it holds.  lse of such a row is non-finite exactly
+ *           where logsumexp is; -inf at the label gives a finite lse and row_loss = +inf.  The gradient values inside
+ *           such a row are not specified; the pad columns are exact zeros all the same.                             */
 int sigma_softmax_ce_fwd_ld(const float *logits, const int64_t *labels, int64_t rows, int32_t classes, int32_t ld,
                             int64_t ignore_index, float *lse, float *partial, void *stream);
 int sigma_softmax_ce_bwd_ld(const float *logits, const int64_t *labels, const float *lse, const float *scale, int64_t rows,

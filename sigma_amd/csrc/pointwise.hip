@@ -295,7 +295,10 @@ softmax_ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restric
             if (PAD) ce_mask_tail(v, nc - c, kNegInf);
             const float vm = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
             if (vm > m) { s *= __expf(m - vm); m = vm; }
-            s += (__expf(v.x - m) + __expf(v.y - m)) + (__expf(v.z - m) + __expf(v.w - m));
+            // every column so far -inf (masked classes): the exponents are taken against 0 -- exp(-inf - 0) = 0 where
+            // -inf - (-inf) is NaN -- and s stays 0 until a finite column raises m.  Finite rows never come here.
+            const float mz = m > kNegInf ? m : 0.0f;
+            s += (__expf(v.x - mz) + __expf(v.y - mz)) + (__expf(v.z - mz) + __expf(v.w - mz));
         }
         const float l = m + __logf(s);
         lse[r] = l;

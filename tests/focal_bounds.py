@@ -137,16 +137,17 @@ def bounds(x64, lab, nc, weight, gamma, g):
     return t
 
 
-def emulate_fp32(x32, lab, nc, weight, gamma, g, variant=None):
+def emulate_fp32(x32, lab, nc, weight, gamma, g, variant=None, form="reg"):
     """The kernels' formulas step by step in fp32 torch ops (csrc/pointwise.hip: focal_row and the four focal kernels):
-    lse, row_loss, w_y and dlogits for the per-row upstream g.  ``variant`` as in the twin: the wrong kernels."""
+    lse, row_loss, w_y and dlogits for the per-row upstream g.  ``variant`` as in the twin: the wrong kernels.  ``form``:
+    lse with the row maximum first ("reg") or by the walk with the online rescale ("walk"), tests/loss_regimes.lse_fp32."""
+    from tests.loss_regimes import lse_fp32
     f32 = torch.float32
     rows = x32.shape[0]
     gamma_p = 2.0 if variant == "square" else gamma
     valid = (lab != IGNORE) & (lab >= 0) & (lab < nc)
     safe = torch.where(valid, lab, torch.zeros_like(lab))
-    mx = x32.max(1).values
-    l = mx + torch.log(torch.exp(x32 - mx[:, None]).sum(1))
+    l = lse_fp32(x32, form)
     d = torch.minimum(x32.gather(1, safe[:, None])[:, 0] - l, torch.zeros_like(l))
     w = weight.to(f32) if weight is not None else torch.ones(nc, dtype=f32)
     wy = torch.where(valid, w[safe], torch.zeros_like(l))

@@ -56,6 +56,15 @@ One line per (shape, classes) and one per class count for the sum over the three
 difference of the medians is larger than the larger of the two inter-quartile ranges.  ``bytes``: what each route moves
 algorithmically (see ``deepsup_bytes``).  A process runs at its own level (0.04 - 0.06 ms apart on these streams), which the
 spread inside a process does not see: ``--run N`` tags the lines and ``--append`` adds a second process to the same file.
+
+    python tools/head_bench.py --loss-fwd --run 1 --out profiles/loss_masked_fix_mi355x.jsonl
+    SIGMA_HIP_LIB=<another build> python tools/head_bench.py --loss-fwd --run 1 --tag parent --append --out ...
+
+``--loss-fwd`` times the FORWARD loss kernel alone (sigma_softmax_ce_fwd_ld through the C ABI, no autograd, one launch
+between two device events) at 8 x 480 x 640 rows for (classes, pitch) = (68, 68) and (65, 68), the rows the walking kernel
+takes (above 64 classes), and (40, 40), a register row, as the control.  One line per shape with the median and spread and
+the bytes the launch moves; ``--tag`` names the build the line belongs to (the library is chosen by SIGMA_HIP_LIB), so that
+two builds can alternate process by process in one session.
 """
 import argparse
 import json
@@ -322,6 +331,47 @@ def deepsup_main(a, dev):
     return lines
 
 
+LOSS_FWD_SHAPES = [(8, 480, 640, 68, 68), (8, 480, 640, 65, 68), (8, 480, 640, 40, 40)]
+
+
+def loss_fwd_main(a, dev):
+    import ctypes
+    from sigma_amd import _capi
+    lib = _capi.load()
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    tag = {"build": a.tag, **({} if a.run is None else {"run": a.run})}
+    lines = []
+    for B, H, W, nc, ld in LOSS_FWD_SHAPES:
+        rows = B * H * W
+        g = torch.Generator().manual_seed(1234)
+        buf = torch.zeros(rows, ld)
+        buf[:, :nc] = torch.randn(rows, nc, generator=g) * 3.0
+        label = torch.randint(0, nc, (rows,), generator=g)
+        label[torch.rand(rows, generator=g) < 0.1] = IGNORE
+        buf, label = buf.to(dev), label.to(dev)
+        lse = torch.empty(rows, device=dev)
+        partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=dev)
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        times = []
+        for i in range(a.warmup + a.reps):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            _capi.check(lib.sigma_softmax_ce_fwd_ld(vp(buf), vp(label), rows, nc, ld, IGNORE, vp(lse), vp(partial), st), "ce fwd ld")
+            t1.record()
+            t1.synchronize()
+            if i >= a.warmup:
+                times.append(t0.elapsed_time(t1))
+        tot = partial.double().sum(0)
+        line = {**tag, "mode": "loss-fwd", "rows": rows, "classes": nc, "ld": ld, "reps": a.reps, "warmup": a.warmup, "fwd": spread(times),
+                "loss": float(tot[0] / tot[1]), "bytes": rows * (4 * ld + 8 + 4), "library": os.path.basename(_capi.LIB_PATH),
+                "device": torch.cuda.get_device_name(0)}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del buf, label, lse
+        torch.cuda.empty_cache()
+    return lines
+
+
 def spread(ts):
     q = statistics.quantiles(ts, n=4)
     return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4),
@@ -337,16 +387,18 @@ def main():
     ap.add_argument("--ohem", action="store_true", help="time the OHEM loss against the plain loss and a torch composition")
     ap.add_argument("--focal", action="store_true", help="time the focal loss against the plain loss and the torch formulation")
     ap.add_argument("--deepsup", action="store_true", help="time the fused upsample + loss of a deep-supervision head against the expansion")
-    ap.add_argument("--run", type=int, default=None, help="--deepsup: tag every line with this run number (one process per run)")
-    ap.add_argument("--append", action="store_true", help="--deepsup: add the lines to --out instead of replacing it")
+    ap.add_argument("--loss-fwd", action="store_true", help="time the forward loss kernel alone at 68, 65 and 40 classes")
+    ap.add_argument("--tag", default="tree", help="--loss-fwd: the name of the build the lines belong to")
+    ap.add_argument("--run", type=int, default=None, help="--deepsup / --loss-fwd: tag every line with this run number (one process per run)")
+    ap.add_argument("--append", action="store_true", help="--deepsup / --loss-fwd: add the lines to --out instead of replacing it")
     a = ap.parse_args()
     if a.reps < 30:
         ap.error("at least 30 repetitions")
     dev = torch.device("cuda", 0)
-    if a.ohem or a.focal or a.deepsup:
-        lines = ohem_main(a, dev) if a.ohem else focal_main(a, dev) if a.focal else deepsup_main(a, dev)
+    if a.ohem or a.focal or a.deepsup or a.loss_fwd:
+        lines = ohem_main(a, dev) if a.ohem else focal_main(a, dev) if a.focal else deepsup_main(a, dev) if a.deepsup else loss_fwd_main(a, dev)
         if a.out:
-            with open(a.out, "a" if a.deepsup and a.append else "w") as f:
+            with open(a.out, "a" if (a.deepsup or a.loss_fwd) and a.append else "w") as f:
                 for line in lines:
                     f.write(json.dumps(line) + "\n")
         return
