@@ -132,7 +132,8 @@ int sigma_upsample2x_nhwc(const float *in, float *out, int32_t batch, int32_t he
  *           dot      : out[p] = sum_i a[p][i] * b[p][i]          (d/d scale of the product: a = dy, b = x)
  *           gate_bwd : dx[p][i] = g[p][i] * scale[p] + dmean[p] / hw + (x[p][i] == max[p] ? dmax[p] / count[p] : 0)
  *       -- the gradient of the max pool is shared by tied maxima, as torch.amax does (the reference's
- *       AdaptiveMaxPool2d routes it to one of them; the two agree wherever the maximum is unique).  The tiny (2B, C)
+ *       AdaptiveMaxPool2d routes it to one of them; the two agree wherever the maximum is unique).  A NaN element is the
+ *       maximum of its plane, as in both: max[p] = NaN and count[p] = 0 (nothing equals it).  The tiny (2B, C)
  *       squeeze/excite MLP between pool and scale stays with the caller.                                          */
 int sigma_plane_pool(const float *x, int64_t planes, int64_t hw, float *mean, float *max, float *count, void *stream);
 int sigma_plane_scale(const float *x, const float *scale, float *out, int64_t planes, int64_t hw, void *stream);

@@ -61,7 +61,22 @@ plane_pool_kernel(const float* __restrict__ x, long hw, int vec, float* __restri
     } else {
         for (long i = threadIdx.x; i < hw; i += blockDim.x) { const float v = xp[i]; s += v; max_count(v, m, c); }
     }
-    const float wm = wave_max_all(m);
+    // A NaN is the maximum of its plane, as torch.amax and the reference's AdaptiveMaxPool2d have it, and equals nothing
+    // (count 0); the comparisons above and fmaxf drop it.  The thread's sum is NaN whenever it read one (or both
+    // infinities): only then it looks at its elements again, so the pass above costs what it did.
+    if (s != s) {
+        bool nan = false;
+        if (vec) {
+            for (long i = threadIdx.x; i < (hw >> 2); i += blockDim.x) {
+                const float4 v = reinterpret_cast<const float4*>(xp)[i];
+                nan = nan || v.x != v.x || v.y != v.y || v.z != v.z || v.w != v.w;
+            }
+        } else {
+            for (long i = threadIdx.x; i < hw; i += blockDim.x) nan = nan || xp[i] != xp[i];
+        }
+        if (nan) m = __builtin_nanf("");
+    }
+    const float wm = __any(m != m) ? __builtin_nanf("") : wave_max_all(m);
     c = wave_sum(m == wm ? c : 0.0f);
     s = wave_sum(s);
     const int w = threadIdx.x >> 6;
@@ -73,10 +88,11 @@ plane_pool_kernel(const float* __restrict__ x, long hw, int vec, float* __restri
             ts += sh[i];
             if (sh[4 + i] > tm) { tm = sh[4 + i]; tc = sh[8 + i]; }
             else if (sh[4 + i] == tm) tc += sh[8 + i];
+            else if (sh[4 + i] != sh[4 + i]) tm = sh[4 + i];
         }
         mean[plane] = ts / (float)hw;
         mx[plane] = tm;
-        cnt[plane] = tc;
+        cnt[plane] = tm != tm ? 0.0f : tc;
     }
 }
 
