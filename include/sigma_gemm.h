@@ -16,6 +16,18 @@
  * from global memory to LDS (no operand images in HBM).  Error against an fp64 product ~4e-6 rms (the fp32
  * library GEMM: ~1e-6), see profiles/.
  *
+ * Where the contract differs from an fp32 GEMM (pinned by tests/test_gemm_gpu.py and tests/test_gemm_exact_cpu.py):
+ *   - an operand element of +-inf splits into (a_hi, a_lo) = (+-inf, NaN), and a FINITE element whose magnitude rounds
+ *     to inf in bf16 -- bit pattern 0x7F7F8000 (about 3.396e38) and above; 0x7F7F7FFF is the largest safe one -- into
+ *     (+-inf, -+inf): its whole row (element of A) or column (element of Bt) of C is NaN, where an fp32 GEMM returns
+ *     +-inf or a finite value.  A NaN element does the same, as in any GEMM.  Nothing else of C is touched: with a_mod
+ *     the row of every problem that reads the weight, with c_mod the one shared output the problem is summed into,
+ *     whatever the tiles, reduction slices, two-stage sums or transposed column range.  A non-finite bias or residual
+ *     element reaches its column / its one element unchanged (fp32 adds).  The split is not guarded against this: it is
+ *     14 % of a k-step, and a run that produces such operands has diverged either way.
+ *   - an element below about 2^-117 has |a_lo| <= 2^-9 |a| under bf16's smallest normal 2^-126; it may lose a_lo
+ *     (relative error of its products up to 2^-8 instead of ~2^-16), and a product below 2^-126 may flush to zero.
+ *
  * Conventions as sigma_scan.h: device pointers, fp32, the callee enqueues on `stream` (hipStream_t as void*) of
  * the current device, never allocates, never synchronises; returns 0 or a SIGMA_OPS_ERR_* code (sigma_ops.h).
  */

@@ -346,10 +346,11 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
                     //   softplus'(raw)      = sigmoid(raw) = 1 - exp(-dl) = -expm1(-dl)
                     // -expm1(-dl): 1 - exp2 above 0.25 (relative error < 3e-7), a degree-7 series below (< 1e-7).
                     // dl == 0 only past the end of the row or where exp(raw) underflows, i.e. sigmoid(raw) = 0 too.
+                    // The test is "dead", not "live": a NaN dl is not dead and reaches ddelta.
                     auto dd_of = [&](int k) {
                         const float d = dl[k];
-                        const bool live = d >= 1.17549435e-38f;
-                        const float usx = dlu[k] * (sdxB[k] * fast_rcp(live ? d : 1.0f));
+                        const bool dead = d < 1.17549435e-38f;
+                        const float usx = dlu[k] * (sdxB[k] * fast_rcp(dead ? 1.0f : d));
                         const float big = 1.0f - fast_exp2(-d * kLog2e);
                         float ser = fmaf(d, -1.0f / 7.0f, 1.0f);
                         ser = fmaf(ser * d, -1.0f / 6.0f, 1.0f);
@@ -358,7 +359,7 @@ __device__ __forceinline__ void scan_bwd4_body(const BwdArgs& q, float* smem, in
                         ser = fmaf(ser * d, -1.0f / 3.0f, 1.0f);
                         ser = fmaf(ser * d, -1.0f / 2.0f, 1.0f);
                         const float sig = d > 0.25f ? big : ser * d;
-                        return live ? (usx + sAx[k]) * sig : 0.0f;
+                        return dead ? 0.0f : (usx + sAx[k]) * sig;
                     };
                     float duv[T], ddv[T];
 #pragma unroll

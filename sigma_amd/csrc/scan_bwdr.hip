@@ -204,7 +204,8 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
     auto tile_of = [&](int st) { return REV ? (ntiles - 1 - st) : st; };   // memory tile of scan step st
     // u / delta / dout of a tile travel by LDS-DMA one tile ahead (with register targets the compiler, short of
     // registers, moved the requests next to their use: three exposed memory latencies per tile).  Chunks past the end of
-    // the row are requested at the row start (finite values) and masked when they are read back.
+    // the row are requested at the row start (memory the row owns) and replaced by selects when they are read back: the
+    // row start may hold NaN or inf, and 0 * that is NaN.
     auto request = [&](int mt) {
         const int tl = T * mt + 4 * cc < L ? T * mt : -4 * cc;      // past the end: the row start
         rl_dma16s(u_blk, (unsigned)(u_off + tl) * 4u, raw_base);
@@ -216,8 +217,8 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
     request(m);
     float x1_nx[NS];                                                // the states entering the next step
     // the NS states entering scan step st_ = those after the previous step's tile: one access per lane (before the first
-    // step there is none: the load is clamped to a valid block and the value scaled by zero where it is used -- a select
-    // next to the load would make the compiler wait for it there)
+    // step there is none: the load is clamped to a valid block and the value replaced by zero where it is used -- by a
+    // select, the block may hold a non-finite state; a select next to the load would make the compiler wait for it there)
     auto ck_load = [&](int st_, float (&xo)[NS]) {
         rl_load_ck<NS, NS>(ck + (unsigned)(tile_of(st_ > 0 ? st_ - 1 : 0) * N * 64), n0, lane, xo);      // host: floats per row block < 2^31
     };
@@ -240,10 +241,12 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
         // after its requests (the touch, ONE checkpoint load, NS dB/dC stores, du, ddelta), which stay in
         // flight; the partial tile may skip some of them, so it (and the step after it: the caller waits) drains the counter.
         if (TAIL) rl_dma_wait(); else rl_dma_wait_keep<4 + NS + SIGMA_BWDR_WAIT_SKEW>();
-        const v4f uu = sRaw[tid], dd = sRaw[256 + tid];
+        v4f uu = sRaw[tid];
+        const v4f dd = sRaw[256 + tid];
         v4f g4 = sRaw[512 + tid];
         const v4f zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-        g4 = valid ? g4 : zero4;                                    // dout reads as zero past the end
+        g4 = valid ? g4 : zero4;                                    // dout and u read as zero past the end
+        uu = valid ? uu : zero4;
         float x1[NS];
         touch_acc += touch_nx;
 #pragma unroll
@@ -293,7 +296,7 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
             asm volatile("" : "+v"(dl[0]), "+v"(dlu[0]), "+v"(gg[0]), "+v"(dl[4]), "+v"(dlu[4]), "+v"(gg[4]),
                               "+v"(dl[8]), "+v"(dlu[8]), "+v"(gg[8]), "+v"(dl[12]), "+v"(dlu[12]), "+v"(gg[12]));
             __builtin_amdgcn_sched_barrier(0);
-            const float xin_scale = st > 0 ? 1.0f : 0.0f;
+            const bool has_xin = st > 0;
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 float Bt[T], Ct[T];
@@ -307,7 +310,7 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
                     rl_load_bc(Cw + (s + 1) * C_ns + T * m, nch, Cn);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                const float xin = x1[s] * xin_scale;
+                const float xin = has_xin ? x1[s] : 0.0f;
                 float a[T], xs[T];
                 // ---- forward replay of the tile from the state entering it
                 {
@@ -315,8 +318,10 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
 #pragma unroll
                     for (int kk = 0; kk < T; ++kk) {
                         const int k = REV ? T - 1 - kk : kk;
-                        a[k] = fast_exp2(dl[k] * A2[s]);
-                        x = fmaf(a[k], x, dlu[k] * Bt[k]);
+                        // past the end (partial tile only; wave-uniform): the identity step, whatever A, B and x hold
+                        const bool live = !TAIL || T * m + k < L;
+                        a[k] = live ? fast_exp2(dl[k] * A2[s]) : 1.0f;
+                        x = live ? fmaf(a[k], x, dlu[k] * Bt[k]) : x;
                         xs[k] = x;
                     }
                 }
@@ -326,12 +331,13 @@ __device__ __forceinline__ void scan_bwdr_body(const BwdArgs& q, float* smem, co
 #pragma unroll
                 for (int kk = T - 1; kk >= 0; --kk) {
                     const int k = REV ? T - 1 - kk : kk;
-                    const float dx = fmaf(gg[k], Ct[k], e);
+                    const bool live = !TAIL || T * m + k < L;
+                    const float dx = live ? fmaf(gg[k], Ct[k], e) : e;
                     e = a[k] * dx;
                     const int kp = REV ? k + 1 : k - 1;             // previous position in scan order
                     const float xprev = kk > 0 ? xs[kk > 0 ? kp : k] : xin;
                     sdxB[k] = fmaf(dx, Bt[k], sdxB[k]);
-                    const float t = e * xprev;                      // dx * a_k * x_{k-1}
+                    const float t = live ? e * xprev : 0.0f;        // dx * a_k * x_{k-1}
                     sAx[k] = fmaf(A2[s], t, sAx[k]);                // x ln 2 in the epilogue
                     dAacc[s] = fmaf(dl[k], t, dAacc[s]);
                     w[k & 7] = fold32(dx * dlu[k], gg[k] * xs[k]);  // this row's terms of dB[n, l] and dC[n, l], wave halves summed

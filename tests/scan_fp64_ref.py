@@ -203,12 +203,13 @@ def softplus64(raw, threshold=20.0):
 
 
 def reference(u, delta, A, B, C, D, bias, dout, softplus, consts: Constants, *, rev_mask=0, u_gshift=0, dout_gshift=0,
-              io="float32", io_bc=True, elems=1 << 25, wrong=None, wrong_at=0):
+              io="float32", io_bc=True, elems=1 << 25, wrong=None, wrong_at=0, finite=True):
     """(ref, S, sums): dicts of float64 tensors in the operator's layout (du one row per channel row), ref and S over
     OUTPUTS, sums = sum |terms| of the five deep sums (for ``rebound``).  ``wrong``
     names a plausible defect (negative controls; only this reference code runs in them):
     bf16_decay, exp_1e-5, drop_carry (the last state's carry into position ``wrong_at``), threshold10, sigmoid1_10,
-    adjoint_at, rev_skip_first, dB_last_row, dC_last_row, dA_last_image, out_D, du_D."""
+    adjoint_at, rev_skip_first, dB_last_row, dC_last_row, dA_last_image, out_D, du_D.  ``finite=False``: operands with
+    planted non-finite elements (tests/scan_footprint.py); only WHERE ref is non-finite means anything then, S does not."""
     dev = delta.device
     f8 = lambda t: None if t is None else t.detach().to(torch.float64)
     u, delta, A, B, C, D, bias, dout = map(f8, (u, delta, A, B, C, D, bias, dout))
@@ -257,6 +258,7 @@ def reference(u, delta, A, B, C, D, bias, dout, softplus, consts: Constants, *, 
                 zA = (dl[:, None, :] * An).abs()
                 kt = (cs.k + esp)[:, None, :] * zA                                      # k_t |delta_t A|
                 w = (dl * uu)[:, None, :] * Bg
+                w[..., 0] += a[..., 0] * 0.0                    # a_0 x_{-1}, x_{-1} = 0: exact, and a non-finite a_0 is seen
                 # ---- forward: x, X, then E
                 x, X = lin_scan(a, [w, w.abs()])
                 Xmax = X.amax(-1, keepdim=True)
@@ -323,7 +325,7 @@ def reference(u, delta, A, B, C, D, bias, dout, softplus, consts: Constants, *, 
     if io == "float16":
         for name in rounded:
             S[name] += 2.0 ** -25 / U
-    for name in OUTPUTS:
+    for name in OUTPUTS if finite else ():
         assert bool(torch.isfinite(ref[name]).all()) and bool(torch.isfinite(S[name]).all()), f"reference {name}: not finite"
     return ref, S, sums
 

@@ -357,3 +357,42 @@ def test_real_shapes_are_in_the_list_once_each():
                  ("nn", 112, 1200, 768, 4, False, 0), ("nn", 768, 1200, 24, 8, False, 0)):
         assert want in shapes, want
     assert len(g) == len(shapes)
+
+
+# ------------------------------------------------------------------------------------ the edges of the split (header formula)
+def _bits(pattern):
+    return torch.tensor([pattern], dtype=torch.int32).view(torch.float32)
+
+
+@pytest.mark.parametrize("P", [2, 3])
+def test_pieces_of_a_non_finite_or_overflowing_element(P):
+    """include/sigma_gemm.h, contract difference from an fp32 GEMM: by the header's formula an element of +-inf has the
+    pieces (+-inf, NaN, NaN), and a FINITE element at or above bit pattern 0x7F7F8000 (about 3.396e38), which rounds to inf
+    in bf16, has (+-inf, -+inf, NaN): either way hi * b + lo * b is NaN for every b, where an fp32 GEMM returns +-inf or
+    a finite value.  0x7F7F7FFF, the largest safe pattern, splits into finite pieces that add up to it."""
+    inf = float("inf")
+    for s in (1.0, -1.0):
+        ps = pieces_of(torch.tensor([s * inf]), P)
+        assert float(ps[0]) == s * inf and all(bool(torch.isnan(p).all()) for p in ps[1:])
+        unsafe = s * _bits(0x7F7F8000)
+        assert bool(torch.isfinite(unsafe).all())
+        ps = pieces_of(unsafe, P)
+        assert float(ps[0]) == s * inf and float(ps[1]) == -s * inf
+        for b in (1.0, -0.3, 1e-30, 0.0):                                  # the kept products of the element cancel into NaN
+            assert bool(torch.isnan(ps[0] * b + ps[1] * b).all())
+        safe = s * _bits(0x7F7F7FFF)
+        ps = pieces_of(safe, 3)
+        assert all(bool(torch.isfinite(p).all()) for p in ps) and float(ps[0]) == s * float(_bits(0x7F7F0000))
+        assert torch.equal(sum(p.double() for p in ps), safe.double())
+    assert bool(torch.isnan(pieces_of(torch.tensor([float("nan")]), P)[0]).all())
+
+
+def test_lo_piece_of_a_small_element_is_a_bf16_denormal():
+    """below about 2^-117 the lo piece (|lo| <= 2^-9 |x|) falls under bf16's smallest normal 2^-126: hardware that flushes
+    bf16 denormals loses it, at a cost of at most 2^-8 |x| (the bound of test_gemm_bound_on_small_magnitudes)"""
+    x = torch.tensor([1.001953125 * 2.0 ** -118, 1.744140625 * 2.0 ** -120, 1.001953125 * 2.0 ** -116])   # lo = 2^-9 of the binade
+    hi, lo = pieces_of(x, 2)
+    assert torch.equal((hi + lo).double(), x.double())
+    assert bool((lo[:2].abs() > 0).all()) and bool((lo[:2].abs() < 2.0 ** -126).all())      # denormal in bf16 and in fp32
+    assert float(lo[2].abs()) >= 2.0 ** -126                                                  # 2^-116 * 2^-9: still normal
+    assert bool((lo.abs() <= 2.0 ** -8 * x.abs()).all())

@@ -4,6 +4,10 @@ Checker: the same product in fp64 (torch on the GPU).  A product of fp32 operand
 lo*lo term dropped has a relative error of ~2^-16 per product term at worst and ~4e-6 rms on sums; the bound used here is
 3e-5 * sum_k |a||b| per output element (the fp32 library GEMM sits at ~1e-6 of the same scale).  The model-level
 tolerance (1e-3 on logits, the reference's gradient tolerances) is checked in tests/test_model_gpu.py with these kernels on.
+
+The last section plants NaN, +-inf, magnitudes at the bf16 overflow edge and very small magnitudes in operand elements
+and pins which elements of C they may touch.  Those tests only detect: non-finite VALUES are data, not addresses, and no
+test makes a kernel read or write outside memory the test owns.
 """
 import pytest
 import torch
@@ -519,3 +523,280 @@ def test_gemm_keeps_its_relative_bound_under_row_and_column_scales(form):
     ref = want / (r[:, None].double() * c[None, :].double())
     rms = float(rel.pow(2).mean().sqrt() / ref.pow(2).mean().sqrt())
     assert rms < 2e-5, f"{form} scaled: relative rms error {rms:.3e}"
+
+
+# ---- non-finite operand elements, the bf16 overflow edge, small magnitudes ------------------------------------------------
+# Non-finite VALUES are data, not addresses: no test here makes a kernel read or write outside memory the test owns.
+# Contract (include/sigma_gemm.h): split_pair turns an operand element of +-inf, or a finite one whose magnitude rounds to
+# inf in bf16 (bit pattern 0x7F7F8000 and above), into the pieces (inf, NaN) / (inf, -inf): its row (A) or column (B) of C
+# is NaN where an fp32 GEMM returns +-inf or stays finite -- and nothing else of C moves.
+
+NONFINITE = (float("nan"), float("inf"), float("-inf"))
+REPORT: dict = {}
+
+
+def _from_bits(bits):
+    return torch.tensor([bits], dtype=torch.int32).view(torch.float32).item()
+
+
+def _same_or_bound(got, clean, want64, bound, keep, what):
+    """outside the footprint: bit-identical to the unplanted run where the launch sums in a fixed order (two-stage /
+    deterministic mode, and launches whose work items own their outputs), inside the existing bound otherwise"""
+    from sigma_amd import gemm
+    assert bool(torch.isfinite(got[keep]).all()), f"{what}: non-finite outside the footprint"
+    if gemm._two_stage():
+        assert torch.equal(got[keep], clean[keep]), f"{what}: {int((got[keep] != clean[keep]).sum())} elements outside the footprint moved"
+    else:
+        err = (got.double() - want64).abs()[keep]
+        assert float((err / (bound[keep] + 1e-30)).max()) < 3e-5, what
+
+
+def _footprint_of(form_mm, a, b, who, idx):
+    """set arithmetic: the elements of C that have the planted element among their terms"""
+    ma, mb = torch.zeros_like(a, dtype=torch.float64), torch.zeros_like(b, dtype=torch.float64)
+    (ma if who == "a" else mb)[idx] = 1.0
+    return (form_mm(ma, torch.ones_like(mb)) + form_mm(torch.ones_like(ma), mb)) > 0
+
+
+def _check_plants(run, form_mm, a, b, plants, what, nan_only=True):
+    """``run(a, b)`` -> C.  For every plant (operand, index) and every value of NONFINITE: C is NaN exactly on the
+    footprint of the plant, everything else as in the unplanted run"""
+    clean = run(a, b).clone()
+    want64, bound = form_mm(a.double(), b.double()), form_mm(a.double().abs(), b.double().abs())
+    assert bool(torch.isfinite(clean).all())
+    for who, idx in plants:
+        for v in NONFINITE:
+            pa, pb = a.clone(), b.clone()
+            (pa if who == "a" else pb)[idx] = v
+            got = run(pa, pb)
+            cone = _footprint_of(form_mm, a, b, who, idx)
+            assert bool(cone.any()) and not bool(cone.all()), (what, who, idx)
+            bad = torch.isnan(got) if nan_only else ~torch.isfinite(got)
+            assert bool(bad[cone].all()), f"{what} {who}{idx} = {v}: {int((~bad[cone]).sum())} elements of the footprint are not NaN"
+            _same_or_bound(got, clean, want64, bound, ~cone, f"{what} {who}{idx} = {v}")
+
+
+def _ab_plants(a_shape, b_shape, a_rk, b_ck):
+    """one plant in the full part and one in each partial part: (row, k) of A and (column, k) of B given as axis numbers"""
+    out = []
+    for who, shape, (ax, kx) in (("a", a_shape, a_rk), ("b", b_shape, b_ck)):
+        for r, k in ((5, 3), (shape[ax] - 1, shape[kx] - 1)):
+            idx = [0] * len(shape)
+            idx[ax], idx[kx] = r, k
+            out.append((who, tuple(idx)))
+    return out
+
+
+# (M, K, N): a partial row tile, a partial column tile and a partial last k-step (K % 32 != 0)
+FOOT_SHAPES = [(130, 36, 200), (257, 100, 72)]
+
+
+@pytest.mark.parametrize("pieces", [2, 3])
+@pytest.mark.parametrize("shape", FOOT_SHAPES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("form", ["nt", "nn", "tn"])
+def test_one_non_finite_operand_element_reaches_its_row_or_column_only(form, shape, pieces):
+    """NaN, +inf and -inf in one element of A and of B, in the full and in the partial tiles / k-step: C is NaN exactly on
+    that row (A) or column (B) -- +-inf too: the pieces of inf are (inf, NaN) -- and bit-identical elsewhere"""
+    from sigma_amd import gemm
+    M, K, N = shape
+    if form == "nt":
+        a, b = _rand(M, K, seed=101), _rand(N, K, seed=102, scale=0.05)
+        run, mm, plants = (lambda x, y: gemm.gemm_nt(x, y, pieces=pieces)), (lambda x, y: x @ y.t()), _ab_plants(a.shape, b.shape, (0, 1), (0, 1))
+    elif form == "nn":
+        a, b = _rand(M, K, seed=101), _rand(K, N, seed=102, scale=0.05)
+        run, mm, plants = (lambda x, y: gemm.gemm_nn(x, y, pieces=pieces)), (lambda x, y: x @ y), _ab_plants(a.shape, b.shape, (0, 1), (1, 0))
+    else:                                                    # reduction over the K tokens, C is M x N (M a multiple of 4)
+        M = (M + 3) // 4 * 4
+        a, b = _rand(K, M, seed=101, scale=0.1), _rand(K, N, seed=102)
+        run, mm, plants = (lambda x, y: gemm.gemm_tn(x, y, pieces=pieces)), (lambda x, y: x.t() @ y), _ab_plants(a.shape, b.shape, (1, 0), (1, 0))
+    _check_plants(run, mm, a, b, plants, f"{form} p{pieces}")
+
+
+def test_non_finite_elements_in_a_sliced_tn_stay_in_their_row_or_column():
+    """tn with several reduction slices summed in two stages (8004 tokens, 8004 % 32 = 4): a plant in the first slice, one in
+    the last, partial k-step -- the row / column of C is NaN, the rest bit-identical"""
+    from sigma_amd import gemm
+    T, N, K = 8004, 132, 200
+    a, b = _rand(T, N, seed=103, scale=0.1), _rand(T, K, seed=104)
+    out = lambda x, y: gemm.gemm_tn(x, y, out=torch.full((N, K), float("nan"), device=DEV))
+    plants = [("a", (3, 5)), ("a", (T - 1, N - 1)), ("b", (4000, 7)), ("b", (T - 1, K - 1))]
+    _check_plants(out, lambda x, y: x.t() @ y, a, b, plants, "tn sliced")
+
+
+def test_non_finite_bias_and_addends_reach_their_column_or_element_only():
+    """nt with bias and a residual; bgemm_nn with both epilogue addends: a plant in the bias makes its column non-finite
+    (+-inf stays +-inf: the epilogue adds in fp32), a plant in an addend its one element"""
+    from sigma_amd import gemm
+    M, K, N = 130, 36, 200
+    x, w, bias, r = _rand(M, K, seed=105), _rand(N, K, seed=106, scale=0.05), _rand(N, seed=107), _rand(M, N, seed=108)
+    clean = gemm.gemm_nt(x, w, bias, residual=r).clone()
+    for v in NONFINITE:
+        for j in (7, N - 1):
+            pb = bias.clone()
+            pb[j] = v
+            got = gemm.gemm_nt(x, w, pb, residual=r)
+            keep = torch.ones_like(got, dtype=torch.bool)
+            keep[:, j] = False
+            assert not bool(torch.isfinite(got[:, j]).any()) and torch.equal(got[keep], clean[keep]), ("bias", j, v)
+        for i, j in ((5, 7), (M - 1, N - 1), (M - 1, 3), (2, N - 1)):
+            pr = r.clone()
+            pr[i, j] = v
+            got = gemm.gemm_nt(x, w, bias, residual=pr)
+            keep = torch.ones_like(got, dtype=torch.bool)
+            keep[i, j] = False
+            assert not bool(torch.isfinite(got[i, j])) and torch.equal(got[keep], clean[keep]), ("residual", i, j, v)
+    Z, c2, d, L = 4, 36, 132, 200                           # the stacked x_proj input gradient + the scan's two du
+    Wt, dp = _rand(2, d, c2, seed=109, scale=0.05), _rand(Z, c2, L, seed=110)
+    du = _rand(Z, 2, d, L, seed=111)
+    run = lambda r1, r2: gemm.bgemm_nn(Wt, dp, torch.empty(Z, d, L, device=DEV), residual=r1, residual2=r2)
+    clean = run(du[:, 0], du[:, 1]).clone()
+    for v in NONFINITE:
+        for which in (0, 1):
+            for z, i, j in ((1, 5, 7), (Z - 1, d - 1, L - 1)):
+                pd = du.clone()
+                pd[z, which, i, j] = v
+                got = run(pd[:, 0], pd[:, 1])
+                keep = torch.ones_like(got, dtype=torch.bool)
+                keep[z, i, j] = False
+                assert not bool(torch.isfinite(got[z, i, j])) and torch.equal(got[keep], clean[keep]), ("addend", which, z, i, j, v)
+
+
+def test_non_finite_elements_of_shared_weights_and_shared_outputs():
+    """bgemm_nn with a weight stack shared by problems (a_mod): a plant in the weight reaches its row of EVERY problem
+    that reads it, a plant in a problem's own operand its column of that problem.  Outputs shared by problems (c_mod):
+    exactly the shared output that the planted problem adds into, even (bgemm_nt_sum, 4 problems on 2 outputs) and ragged
+    (5 problems on 2 outputs, through the C ABI by the header's contract)."""
+    import ctypes
+    from sigma_amd import _capi, gemm
+    Z, am, M, K, N = 4, 2, 72, 36, 200
+    W, X = _rand(am, M, K, seed=112, scale=0.05), _rand(Z, K, N, seed=113)
+    run = lambda w, x: gemm.bgemm_nn(w, x, torch.empty(Z, M, N, device=DEV))
+    mm = lambda w, x: torch.matmul(w[torch.arange(Z, device=w.device) % am], x)
+    _check_plants(run, mm, W, X, [("a", (1, 5, 3)), ("a", (0, M - 1, K - 1)), ("b", (2, 3, 7)), ("b", (Z - 1, K - 1, N - 1))], "bgemm_nn a_mod")
+
+    def fold(p, cm):                                         # problems z with the same z % cm summed
+        out = torch.zeros((cm,) + tuple(p.shape[1:]), dtype=p.dtype, device=p.device)
+        return out.index_add_(0, torch.arange(p.shape[0], device=p.device) % cm, p)
+
+    Z, cm, M, N, K = 4, 2, 40, 132, 200
+    a, b = _rand(Z, M, K, seed=114), _rand(Z, N, K, seed=115, scale=0.05)
+    run = lambda x, y: gemm.bgemm_nt_sum(x, y, torch.full((cm, M, N), float("nan"), device=DEV), accumulate=False)
+    mm = lambda x, y: fold(torch.matmul(x, y.transpose(-1, -2)), cm)
+    _check_plants(run, mm, a, b, [("a", (0, 5, 3)), ("a", (3, M - 1, K - 1)), ("b", (1, 7, 3)), ("b", (2, N - 1, K - 1))], "c_mod even")
+
+    Z, cm, M, N, K = 5, 2, 32, 192, 1204                    # ragged: output 0 sums z = 0, 2, 4, output 1 sums z = 1, 3
+    a, b = _rand(Z, M, K, seed=116), _rand(Z, N, K, seed=117, scale=0.05)
+
+    def ragged(x, y):
+        margin = N + 64
+        buf, flat = _guarded(cm * M * N, margin)
+        c = flat.view(cm, M, N)
+        p = gemm._params(M, N, K, x, y, c, None, K, K, N, False, batch=Z, sA=M * K, sB=N * K, sC=M * N, c_mod=cm)
+        need = int(_capi.load().sigma_gemm_workspace_bytes(ctypes.byref(p), 0))
+        assert need > 0
+        ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+        p.workspace, p.workspace_bytes = ws.data_ptr(), need
+        gemm._selftest(x.device)
+        assert _call("sigma_gemm_nt_split3", p, x.device) == 0
+        assert _margins_intact(buf, cm * M * N, margin), "ragged c_mod wrote outside C"
+        return c
+
+    mm = lambda x, y: fold(torch.matmul(x, y.transpose(-1, -2)), cm)
+    _check_plants(ragged, mm, a, b, [("a", (4, 5, 3)), ("a", (3, M - 1, K - 1)), ("b", (2, 7, 1203)), ("b", (0, N - 1, 40))], "c_mod ragged")
+
+
+def test_non_finite_elements_with_a_transposed_column_range():
+    """in_proj with the x half leaving the kernel transposed (t_cols): 132 tokens, K = 36, 96 + 96 columns -- a plant in a
+    token reaches that token in BOTH halves, a plant in a weight row its one column, in whichever half it lies"""
+    from sigma_amd import gemm
+    Bn, H, W_, C, d = 1, 3, 44, 36, 96
+    x, w = _rand(Bn * H * W_, C, seed=118), _rand(2 * d, C, seed=119, scale=0.05)
+    assert gemm.xz_ok(x, w)
+
+    def run(xx, ww):
+        with torch.no_grad():
+            xi, z = gemm.linear_xz(xx.view(Bn, H, W_, C), ww, None)
+        return torch.cat([xi.permute(0, 2, 3, 1).reshape(-1, d), z.reshape(-1, d)], 1)
+
+    plants = [("a", (5, 3)), ("a", (131, 35)), ("b", (7, 3)), ("b", (d - 1, 35)), ("b", (d, 0)), ("b", (2 * d - 1, 35))]
+    _check_plants(run, lambda a_, b_: a_ @ b_.t(), x, w, plants, "t_cols")
+
+
+def test_bf16_overflow_edge_of_the_split_is_pinned():
+    """the contract difference from an fp32 GEMM: an operand element whose magnitude rounds to inf in bf16 -- bit pattern
+    0x7F7F8000 (about 3.396e38, finite in fp32) and above -- splits into (inf, -inf) and makes its row or column of C NaN,
+    and only that; 0x7F7F7FFF, the largest safe one, splits into finite pieces and keeps the usual bound.  B is scaled by
+    2^-30 so that the fp32 result itself stays finite."""
+    from sigma_amd import gemm
+    M, K, N = 130, 36, 200
+    a, w = _rand(M, K, seed=120), _rand(N, K, seed=121, scale=0.05 * 2.0 ** -30)
+    clean = gemm.gemm_nt(a, w).clone()
+    safe, unsafe = _from_bits(0x7F7F7FFF), _from_bits(0x7F7F8000)
+    assert safe < unsafe < float("inf")
+    for sign in (1.0, -1.0):
+        for who, idx in (("a", (5, 3)), ("a", (M - 1, K - 1)), ("b", (7, 3)), ("b", (N - 1, K - 1))):
+            pa, pw = a.clone(), w.clone()
+            (pa if who == "a" else pw)[idx] = sign * unsafe
+            got = gemm.gemm_nt(pa, pw)
+            cone = _footprint_of(lambda x, y: x @ y.t(), a, w, who, idx)
+            assert bool(torch.isnan(got[cone]).all()), (who, idx, "an element above the bf16 threshold must give NaN")
+            assert torch.equal(got[~cone], clean[~cone]), (who, idx)
+        pa = a.clone()
+        pa[5, 3] = sign * safe
+        got = gemm.gemm_nt(pa, w)
+        want = pa.double() @ w.double().t()
+        assert bool(torch.isfinite(got).all())
+        _assert_close(got[5:6], want[5:6], _bound(pa.double(), w.double().t())[5:6], "largest safe magnitude")
+        assert torch.equal(torch.cat([got[:5], got[6:]]), torch.cat([clean[:5], clean[6:]]))
+
+
+@pytest.mark.parametrize("form", ["nt", "nn", "tn"])
+def test_gemm_bound_on_small_magnitudes(form):
+    """rows scaled by powers of two down to 2^-118 (operand elements down to about 2^-120) and columns down to 2^-22
+    (products down to 2^-140 and below).  Derived, not fitted: an element below 2^-117 may lose its lo piece (|lo| <= 2^-9 |x|
+    falls below bf16's smallest normal 2^-126), which costs at most 2^-8 of each of its products; a product below 2^-126
+    may flush.  So  |err| <= 3e-5 sum_big |a||b| + 2^-8 sum_small |a||b| + 2^-126 x (kept products),  big = both elements
+    at or above 2^-117, kept products = 3 per term (hi hi, hi lo, lo hi).  The report line gives the worst ratio with and
+    without the second term (a ratio <= 1 without it: the MFMA keeps bf16 denormals)."""
+    from sigma_amd import gemm
+    M, N, K = (8000, 132, 200) if form == "tn" else (300, 200, 132)
+    rows, cols = (N, K) if form == "tn" else (M, N)
+    r, c = _pow2_scales(rows, 131, lo=-118, hi=0), _pow2_scales(cols, 132, lo=-22, hi=0)
+    if form == "nt":
+        a, b = _rand(M, K, seed=133) * r[:, None], _rand(N, K, seed=134, scale=0.05) * c[:, None]
+        got, a64, b64 = gemm.gemm_nt(a, b), a.double(), b.double().t()
+    elif form == "nn":
+        a, b = _rand(M, K, seed=133) * r[:, None], _rand(K, N, seed=134, scale=0.05) * c[None, :]
+        got, a64, b64 = gemm.gemm_nn(a, b), a.double(), b.double()
+    else:
+        a, b = _rand(M, N, seed=133, scale=0.1) * r[None, :], _rand(M, K, seed=134) * c[None, :]
+        got, a64, b64 = gemm.gemm_tn(a, b), a.double().t(), b.double()
+    thr = 2.0 ** -117
+    assert float(a64.abs()[a64 != 0].min()) < 2.0 ** -119 and bool(torch.isfinite(got).all())
+    big = lambda t: torch.where(t.abs() >= thr, t.abs(), torch.zeros_like(t))
+    total, s_big = _bound(a64, b64), big(a64) @ big(b64)
+    assert float(r.min()) * float(c.min()) == 2.0 ** -140
+    kept = 3 * a64.shape[1] * 2.0 ** -126
+    err = (got.double() - a64 @ b64).abs()
+    with_lo = float((err / (3e-5 * s_big + 2.0 ** -8 * (total - s_big) + kept)).max())
+    without = float((err / (3e-5 * total + kept)).max())
+    REPORT[form] = (with_lo, without)
+    print(f"  small magnitudes {form}: worst err / bound = {with_lo:.3g}; without the lost-lo term {without:.3g}")
+    assert with_lo <= 1.0, f"{form}: err / bound = {with_lo:.3g}"
+
+
+def test_report_whether_a_lo_piece_below_the_bf16_normal_range_survives():
+    """x = (1 + 2^-9) 2^-118 splits into hi = 2^-118 and lo = 2^-127, a bf16 denormal; against b = 2^10 both products are
+    normal in fp32 (2^-108, 2^-117), so C = K x b exactly when the conversion and the MFMA keep bf16 denormals and
+    K 2^-108 when they flush them.  Either is inside the contract (the second term of the small-magnitude bound); the line
+    printed says which this device does."""
+    from sigma_amd import gemm
+    M, K, N = 32, 32, 32
+    x = (1.0 + 2.0 ** -9) * 2.0 ** -118
+    a, b = torch.full((M, K), x, device=DEV), torch.full((N, K), 2.0 ** 10, device=DEV)
+    got = gemm.gemm_nt(a, b)
+    kept, flushed = K * x * 2.0 ** 10, K * 2.0 ** -108
+    assert bool(((got == kept) | (got == flushed)).all()), got.flatten()[:4]
+    which = "kept" if bool((got == kept).all()) else ("flushed" if bool((got == flushed).all()) else "mixed")
+    REPORT["lo denormal"] = which
+    print(f"  a lo piece of 2^-127 (bf16 denormal) is {which}")

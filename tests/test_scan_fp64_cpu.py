@@ -284,3 +284,128 @@ def test_planner_picks_the_intended_family_for_every_gpu_case():
         assert lib.sigma_scan_bwd_plan(ctypes.byref(bwd_params(batch, KD, L, N, G, mask, ush, pitch, IO[dtype],
                                                                _capi.SIGMA_SCAN_BWD_DETERMINISTIC)), ctypes.byref(det)) == 0
         assert list(det) == bp, name
+
+
+# ------------------------------------------------------------------------- the footprint of one non-finite element
+# tests/scan_footprint.py: the rule == the fp64 reference == a literal fp64 loop, every operand, both directions
+from tests import scan_footprint as F  # noqa: E402
+
+TINY_DIMS = (2, 8, 37, 4, 4)                        # batch, KD, L, N, G: groups 1 and 3 reversed, u / dout shared by pairs
+TINY_KW = dict(rev_mask=0b1010, u_gshift=1, dout_gshift=1)
+PLANT_KINDS = [(op, v) for op in F.SEQ_OPERANDS for v in (F.NAN, F.INF)] + [(op, F.NAN) for op in F.ROW_OPERANDS]
+KIND_IDS = [f"{op}-{'nan' if v != v else 'inf'}" for op, v in PLANT_KINDS]
+
+
+def tiny_problem(regime="init"):
+    batch, KD, L, N, G = TINY_DIMS
+    return R.make(regime, batch, KD, L, N, G, ush=1, seed=3)
+
+
+def tiny_plants(op, value):
+    """a plant per direction at the first, the second, an inner and the last position (row operands: one row each way)"""
+    batch, KD, L, N, G = TINY_DIMS
+    rows = KD // G
+    if op in F.ROW_OPERANDS:
+        return [F.Plant(op, ((g * rows + 1, 2) if op == "A" else (g * rows + 1,)), value) for g in (0, 1)]
+    out = []
+    for t in (0, 1, L // 2, L - 1):
+        if op in ("u", "dout"):
+            out.append(F.Plant(op, (1, 1, t), value))                     # feeds groups 0 and 1: both directions at once
+        for g in (0, 1) if op not in ("u", "dout") else ():
+            out.append(F.Plant(op, (1, g * rows + 1, t) if op == "delta" else (0, g, 2, t), value))
+    return out
+
+
+def tiny_reference(args, **kw):
+    batch, KD, L, N, G = TINY_DIMS
+    return R.reference(*args[:8], args[8], serial_constants(batch, KD, L, G), finite=False, **TINY_KW, **kw)
+
+
+def literal_loop(args):
+    """the literal sequential fp64 loop of ``standin`` on the same operands (shared u / dout rows written out per group)"""
+    batch, KD, L, N, G = TINY_DIMS
+    rows = KD // G
+    src = torch.cat([torch.arange(rows) + (g >> 1) * rows for g in range(G)])
+    args = list(args)
+    args[0], args[7] = args[0][:, src], args[7][:, src]
+    return standin(args, TINY_KW["rev_mask"], dtype=torch.float64)
+
+
+@pytest.mark.parametrize("op,value", PLANT_KINDS, ids=KIND_IDS)
+@pytest.mark.parametrize("regime", ["init", "neg_delta"])            # softplus with a bias; plain delta without one
+def test_footprint_rule_equals_the_reference_and_a_literal_loop(regime, op, value):
+    """the non-finite set of the fp64 reference on operands holding ONE plant EQUALS the rule's mask, for every operand,
+    NaN and +inf, forward and reversed rows, first / inner / last position -- no exception; and so does the set of a
+    literal sequential fp64 loop (the doubling scan of lin_scan does not smear it).  Finite against non-finite only."""
+    args = tiny_problem(regime)
+    if args[F.ARG_INDEX[op]] is None:
+        assert regime == "neg_delta" and op == "delta_bias"         # the regime has no bias: nothing to plant in
+        return
+    for plant in tiny_plants(op, value):
+        want = F.footprint(plant, TINY_DIMS, softplus=args[8], **TINY_KW)
+        planted = F.plant_into(args, [plant])
+        got = F.non_finite_sets(tiny_reference(planted)[0])
+        loop = F.non_finite_sets(literal_loop(planted))
+        for name in outputs_of(args):
+            show = lambda m: m.nonzero().tolist()[:8]
+            assert torch.equal(got[name], want[name]), f"{plant} {name}: reference {show(got[name])} rule {show(want[name])}"
+            assert torch.equal(loop[name], want[name]), f"{plant} {name}: loop {show(loop[name])} rule {show(want[name])}"
+        for name in ("out", "du", "ddelta", "dB", "dC"):            # what the GPU test asserts per plant: not vacuous
+            assert bool(want[name].any()) == (name in F.reached(plant, TINY_DIMS, **TINY_KW)), (plant, name)
+            assert not bool(want[name].all())
+
+
+def test_footprint_launch_plans_cover_every_position_in_disjoint_cones():
+    """``launches``: every position both ways, every launch's cones pairwise disjoint (the GPU cases' group layout)"""
+    dims, kw = (2, 32, 700, 4, 4), dict(rev_mask=0b1010, u_gshift=1, dout_gshift=1)
+    ts = F.positions(700, segment_starts=(352,))
+    assert ts == [0, 1, 2, 3, 16, 160, 352, 640, 699]
+    for op, value in PLANT_KINDS:
+        plan = F.launches(op, value, dims, 0b1010, 1, 1, ts)
+        seen = set()
+        for plants in plan:
+            cones = [F.footprint(p, dims, **kw) for p in plants]
+            assert F.disjoint(cones), (op, plants)
+            for p in plants:
+                seen |= {(t, rev) for _, _, _, rev, t, _ in F.rows_of(p, dims, **kw)}
+        want = {(t, d) for t in ts for d in (False, True)} if op in F.SEQ_OPERANDS else {(None, False), (None, True)}
+        assert seen == want, (op, sorted(want - seen))
+        assert len(plan) <= 5, (op, len(plan))
+
+
+# (control, what the checker must report): only reference code runs here -- the planted reference plays the kernel
+FOOTPRINT_CONTROLS = ["cone_shifted_one_tile", "dB_cone_whole_group_row", "lost_nan"]
+
+
+@pytest.mark.parametrize("control", FOOTPRINT_CONTROLS)
+def test_footprint_checker_fails_wrong_cones_and_a_lost_nan(control):
+    """the checker of the GPU test (F.check) on the fp64 reference's own planted outputs: clean against the true rule;
+    a cone shifted by one 16-tile, a dB cone widened to the whole row of the group, and a plant replaced by zero (a NaN
+    that got lost) must each be reported"""
+    args = tiny_problem("init")
+    plant = F.Plant("u", (1, 1, 18), F.NAN)
+    clean, S, _ = tiny_reference(args)
+    cones, owns = F.footprint(plant, TINY_DIMS, **TINY_KW), F.own(plant, TINY_DIMS, 16, **TINY_KW)
+    got, _, _ = tiny_reference(F.plant_into(args, [plant]))
+    assert F.check(got, cones, owns, clean, S) == ([], {})
+    if control == "cone_shifted_one_tile":
+        cones = F.footprint(F.Plant("u", (1, 1, 18 - 16), F.NAN), TINY_DIMS, **TINY_KW)
+        expect = ("out: ", "dB: ", "dC: ")
+    elif control == "dB_cone_whole_group_row":
+        cones = dict(cones, dB=cones["dB"].clone())
+        cones["dB"][1, 0] = True
+        expect = ("dB: ",)
+    else:
+        got, _, _ = tiny_reference(F.plant_into(args, [F.Plant("u", (1, 1, 18), 0.0)]))
+        expect = ("out: ", "ddelta: ", "dB: ", "dC: ", "dA: ", "dD: ")
+    failures, _ = F.check(got, cones, owns, clean, S)
+    for e in expect:
+        assert any(f.startswith(e) for f in failures), (control, e, failures)
+    # a stray NaN in another row is a failure whatever the table allows; inside the own row only the table excuses it
+    cones, got = F.footprint(plant, TINY_DIMS, **TINY_KW), tiny_reference(F.plant_into(args, [plant]))[0]
+    got["du"][0, 5, 3] = float("nan")
+    assert any(f.startswith("du: ") for f in F.check(got, cones, owns, clean, S, excused={"du": owns["du"]})[0])
+    got["du"][0, 5, 3] = clean["du"][0, 5, 3]
+    got["du"][1, 1, 3] = float("nan")
+    assert F.check(got, cones, owns, clean, S, excused={"du": owns["du"]}) == ([], {"du": 1})
+    assert any(f.startswith("du: ") for f in F.check(got, cones, owns, clean, S)[0])
