@@ -197,40 +197,97 @@ SIGMA_CE_BLOCKS = 1024      # include/sigma_ops.h
 SIGMA_OHEM_HIST_BLOCKS = 512        # include/sigma_ops.h
 SIGMA_SEG_LDS_HIST_BYTES = 32768    # include/sigma_ops.h
 
-# every symbol include/sigma_gemm.h declares
-GEMM_SYMBOLS = ("sigma_gemm_nt_split3", "sigma_gemm_nn_split3", "sigma_gemm_tn_split3")
-GEMM_AUX_SYMBOLS = ("sigma_gemm_selftest", "sigma_gemm_workspace_bytes", "sigma_gemm_plan")
 GEMM_FORMS = {"nt": 0, "nn": 1, "tn": 2}
 GEMM_EPILOGUES = ("rows", "direct", "transposed")      # sigma_gemm_plan out[7] bits 0-1
 GEMM_RES_LOADS = ("none", "vector", "scalar")          # bits 2-3
 GEMM_STORES = ("store", "accumulate", "atomic")        # bits 6-7
 
-# every symbol include/sigma_ops.h declares
-OPS_SYMBOLS = ("sigma_dwconv3x3_silu_fwd", "sigma_dwconv3x3_silu_bwd", "sigma_cross_merge_nhwc", "sigma_cross_split_nhwc",
-               "sigma_layernorm_fwd", "sigma_layernorm_bwd", "sigma_layernorm_bwd_partial_rows", "sigma_transpose2d",
-               "sigma_pair_sum_add", "sigma_upsample2x_nhwc", "sigma_plane_pool", "sigma_plane_scale",
-               "sigma_plane_dot", "sigma_plane_gate_bwd", "sigma_softmax_ce_fwd", "sigma_softmax_ce_bwd", "sigma_softmax_ce_fwd_ld",
-               "sigma_softmax_ce_bwd_ld", "sigma_softmax_ce_opt_fwd", "sigma_softmax_ce_opt_bwd", "sigma_colscale_bwd",
-               "sigma_colscale_bwd_ws", "sigma_seg_accumulate", "sigma_seg_argmax_confusion", "sigma_ohem_select",
-               "sigma_softmax_focal_fwd", "sigma_softmax_focal_bwd", "sigma_upsample_ce_fwd", "sigma_upsample_ce_bwd")
-# the size queries include/sigma_ops.h declares (int64_t results)
-OPS_AUX_SYMBOLS = ("sigma_dwconv3x3_silu_bwd_workspace_bytes", "sigma_colscale_bwd_workspace_bytes", "sigma_ohem_workspace_bytes")
+# C struct name -> ctypes mirror, every struct of the three headers (tests compare each layout with the compiler's)
+STRUCTS = {
+    "sigma_scan_fwd_params": FwdParams, "sigma_scan_bwd_params": BwdParams,
+    "sigma_dwconv_params": DwConvParams, "sigma_merge_params": MergeParams, "sigma_transpose_params": TransposeParams,
+    "sigma_layernorm_params": LayerNormParams, "sigma_gate_bwd_params": GateBwdParams,
+    "sigma_seg_accumulate_params": SegAccumulateParams, "sigma_seg_confusion_params": SegConfusionParams,
+    "sigma_ce_opt_params": CeOptParams, "sigma_ohem_params": OhemParams, "sigma_upsample_ce_params": UpsampleCeParams,
+    "sigma_gemm_params": GemmParams,
+}
 
-# every symbol include/sigma_scan.h declares; tests check the library exports all of them
-EXPORTED_SYMBOLS = (
-    "sigma_selective_scan_fwd",
-    "sigma_selective_scan_bwd",
-    "sigma_scan_bwd_workspace_bytes",
-    "sigma_scan_fwd_workspace_bytes",
-    "sigma_scan_last_error",
-    "sigma_scan_abi_version",
-    "sigma_scan_set_option",
-    "sigma_scan_get_option",
-    "sigma_scan_fwd_plan",
-    "sigma_scan_bwd_plan",
-    "sigma_scan_selftest",
-    "sigma_scan_rowlane_selftest",
-)
+# The prototypes of the three headers, one row per entry point: name -> (restype, [argtypes]).  ``load`` binds exactly
+# these rows -- an entry point without a row cannot be called through the binding -- and tests/test_capi_cpu.py holds
+# every row against its prototype.  A new entry point is declared HERE, once; the public tuples below follow.
+_I32, _I64, _INT, _F32, _VP, _STR = (ctypes.c_int32, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
+                                     ctypes.c_char_p)
+_P = ctypes.POINTER
+
+
+def _params_stream(struct, *names):
+    """rows of the commonest prototype, int f(const struct *params, void *stream)"""
+    return {n: (_INT, [_P(struct), _VP]) for n in names}
+
+
+# include/sigma_scan.h
+_SCAN_SIGNATURES = {
+    **_params_stream(FwdParams, "sigma_selective_scan_fwd"),
+    **_params_stream(BwdParams, "sigma_selective_scan_bwd"),
+    "sigma_scan_bwd_workspace_bytes": (_I64, [_P(BwdParams)]),
+    "sigma_scan_fwd_workspace_bytes": (_I64, [_P(FwdParams)]),
+    "sigma_scan_last_error": (_STR, []),
+    "sigma_scan_abi_version": (_INT, []),
+    "sigma_scan_set_option": (_INT, [_STR, _INT]),
+    "sigma_scan_get_option": (_INT, [_STR]),
+    "sigma_scan_fwd_plan": (_INT, [_P(FwdParams), _P(_I32 * 6)]),
+    "sigma_scan_bwd_plan": (_INT, [_P(BwdParams), _P(_I32 * 6)]),
+    "sigma_scan_selftest": (_INT, [_VP]),
+    "sigma_scan_rowlane_selftest": (_INT, [_VP]),
+}
+# include/sigma_ops.h: the launches and the host-side row count of the LayerNorm backward (int results) ...
+_OPS_SIGNATURES = {
+    **_params_stream(DwConvParams, "sigma_dwconv3x3_silu_fwd", "sigma_dwconv3x3_silu_bwd"),
+    **_params_stream(MergeParams, "sigma_cross_merge_nhwc", "sigma_cross_split_nhwc"),
+    **_params_stream(LayerNormParams, "sigma_layernorm_fwd", "sigma_layernorm_bwd"),
+    "sigma_layernorm_bwd_partial_rows": (_INT, [_I64, _I32]),
+    **_params_stream(TransposeParams, "sigma_transpose2d"),
+    "sigma_pair_sum_add": (_INT, [_VP, _VP, _I64, _I64, _VP]),
+    "sigma_upsample2x_nhwc": (_INT, [_VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
+    "sigma_plane_pool": (_INT, [_VP, _I64, _I64, _VP, _VP, _VP, _VP]),
+    "sigma_plane_scale": (_INT, [_VP, _VP, _VP, _I64, _I64, _VP]),
+    "sigma_plane_dot": (_INT, [_VP, _VP, _VP, _I64, _I64, _VP]),
+    **_params_stream(GateBwdParams, "sigma_plane_gate_bwd"),
+    "sigma_softmax_ce_fwd": (_INT, [_VP, _VP, _I64, _I32, _I64, _VP, _VP, _VP]),
+    "sigma_softmax_ce_bwd": (_INT, [_VP, _VP, _VP, _VP, _I64, _I32, _I64, _VP, _VP]),
+    "sigma_softmax_ce_fwd_ld": (_INT, [_VP, _VP, _I64, _I32, _I32, _I64, _VP, _VP, _VP]),
+    "sigma_softmax_ce_bwd_ld": (_INT, [_VP, _VP, _VP, _VP, _I64, _I32, _I32, _I64, _VP, _VP]),
+    **_params_stream(CeOptParams, "sigma_softmax_ce_opt_fwd", "sigma_softmax_ce_opt_bwd"),
+    "sigma_colscale_bwd": (_INT, [_VP, _VP, _VP, _VP, _VP, _I64, _I32, _VP]),
+    "sigma_colscale_bwd_ws": (_INT, [_VP, _VP, _VP, _VP, _VP, _I64, _I32, _VP, _I64, _VP]),
+    **_params_stream(SegAccumulateParams, "sigma_seg_accumulate"),
+    **_params_stream(SegConfusionParams, "sigma_seg_argmax_confusion"),
+    **_params_stream(OhemParams, "sigma_ohem_select"),
+    "sigma_softmax_focal_fwd": (_INT, [_P(CeOptParams), _F32, _VP]),
+    "sigma_softmax_focal_bwd": (_INT, [_P(CeOptParams), _F32, _VP]),
+    **_params_stream(UpsampleCeParams, "sigma_upsample_ce_fwd", "sigma_upsample_ce_bwd"),
+}
+# ... and its size queries (int64_t results)
+_OPS_AUX_SIGNATURES = {
+    "sigma_dwconv3x3_silu_bwd_workspace_bytes": (_I64, [_P(DwConvParams)]),
+    "sigma_colscale_bwd_workspace_bytes": (_I64, [_I64, _I32]),
+    "sigma_ohem_workspace_bytes": (_I64, [_I64]),
+}
+# include/sigma_gemm.h: the three launches, then the host-side entry points and the self test
+_GEMM_SIGNATURES = _params_stream(GemmParams, "sigma_gemm_nt_split3", "sigma_gemm_nn_split3", "sigma_gemm_tn_split3")
+_GEMM_AUX_SIGNATURES = {
+    "sigma_gemm_selftest": (_INT, [_VP]),
+    "sigma_gemm_workspace_bytes": (_I64, [_P(GemmParams), _INT]),
+    "sigma_gemm_plan": (_INT, [_P(GemmParams), _INT, _P(_I32 * 8)]),
+}
+
+# every symbol each header declares, in the table's order; tests check the library exports all of them
+EXPORTED_SYMBOLS = tuple(_SCAN_SIGNATURES)
+OPS_SYMBOLS = tuple(_OPS_SIGNATURES)
+OPS_AUX_SYMBOLS = tuple(_OPS_AUX_SIGNATURES)
+GEMM_SYMBOLS = tuple(_GEMM_SIGNATURES)
+GEMM_AUX_SYMBOLS = tuple(_GEMM_AUX_SIGNATURES)
+SIGNATURES = {**_SCAN_SIGNATURES, **_OPS_SIGNATURES, **_OPS_AUX_SIGNATURES, **_GEMM_SIGNATURES, **_GEMM_AUX_SIGNATURES}
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -248,97 +305,12 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # e.g. libamdhip64 not found
         raise SigmaHipUnavailable(f"cannot load {LIB_PATH}: {e}") from e
-    P = ctypes.POINTER
-    lib.sigma_selective_scan_fwd.argtypes = [P(FwdParams), ctypes.c_void_p]
-    lib.sigma_selective_scan_fwd.restype = ctypes.c_int
-    lib.sigma_selective_scan_bwd.argtypes = [P(BwdParams), ctypes.c_void_p]
-    lib.sigma_selective_scan_bwd.restype = ctypes.c_int
-    lib.sigma_scan_bwd_workspace_bytes.argtypes = [P(BwdParams)]
-    lib.sigma_scan_bwd_workspace_bytes.restype = ctypes.c_int64
-    lib.sigma_scan_fwd_workspace_bytes.argtypes = [P(FwdParams)]
-    lib.sigma_scan_fwd_workspace_bytes.restype = ctypes.c_int64
-    lib.sigma_scan_last_error.argtypes = []
-    lib.sigma_scan_last_error.restype = ctypes.c_char_p
-    lib.sigma_scan_abi_version.argtypes = []
-    lib.sigma_scan_abi_version.restype = ctypes.c_int
-    lib.sigma_scan_set_option.argtypes = [ctypes.c_char_p, ctypes.c_int]
-    lib.sigma_scan_set_option.restype = ctypes.c_int
-    lib.sigma_scan_get_option.argtypes = [ctypes.c_char_p]
-    lib.sigma_scan_get_option.restype = ctypes.c_int
-    lib.sigma_scan_fwd_plan.argtypes = [P(FwdParams), P(ctypes.c_int32 * 6)]
-    lib.sigma_scan_fwd_plan.restype = ctypes.c_int
-    lib.sigma_scan_bwd_plan.argtypes = [P(BwdParams), P(ctypes.c_int32 * 6)]
-    lib.sigma_scan_bwd_plan.restype = ctypes.c_int
-    lib.sigma_scan_selftest.argtypes = [ctypes.c_void_p]
-    lib.sigma_scan_selftest.restype = ctypes.c_int
-    lib.sigma_scan_rowlane_selftest.argtypes = [ctypes.c_void_p]
-    lib.sigma_scan_rowlane_selftest.restype = ctypes.c_int
-    for name in OPS_SYMBOLS:
-        fn = getattr(lib, name)
-        if name == "sigma_layernorm_bwd_partial_rows":
-            fn.argtypes = [ctypes.c_int64, ctypes.c_int32]
-        elif name == "sigma_pair_sum_add":
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
-        elif name == "sigma_upsample2x_nhwc":
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                           ctypes.c_int32, ctypes.c_void_p]
-        elif name == "sigma_plane_pool":
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        elif name in ("sigma_plane_scale", "sigma_plane_dot"):
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
-        elif name == "sigma_plane_gate_bwd":
-            fn.argtypes = [P(GateBwdParams), ctypes.c_void_p]
-        elif name == "sigma_colscale_bwd":
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                           ctypes.c_int32, ctypes.c_void_p]
-        elif name == "sigma_colscale_bwd_ws":
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
-        elif name == "sigma_softmax_ce_fwd":
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
-                           ctypes.c_void_p, ctypes.c_void_p]
-        elif name == "sigma_softmax_ce_bwd":
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                           ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
-        elif name == "sigma_softmax_ce_fwd_ld":
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        elif name == "sigma_softmax_ce_bwd_ld":
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                           ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
-        elif name in ("sigma_softmax_ce_opt_fwd", "sigma_softmax_ce_opt_bwd"):
-            fn.argtypes = [P(CeOptParams), ctypes.c_void_p]
-        elif name in ("sigma_softmax_focal_fwd", "sigma_softmax_focal_bwd"):
-            fn.argtypes = [P(CeOptParams), ctypes.c_float, ctypes.c_void_p]
-        elif name in ("sigma_upsample_ce_fwd", "sigma_upsample_ce_bwd"):
-            fn.argtypes = [P(UpsampleCeParams), ctypes.c_void_p]
-        elif name == "sigma_ohem_select":
-            fn.argtypes = [P(OhemParams), ctypes.c_void_p]
-        elif name == "sigma_seg_accumulate":
-            fn.argtypes = [P(SegAccumulateParams), ctypes.c_void_p]
-        elif name == "sigma_seg_argmax_confusion":
-            fn.argtypes = [P(SegConfusionParams), ctypes.c_void_p]
-        else:
-            st = (MergeParams if "cross_" in name else LayerNormParams if "layernorm" in name else
-                  TransposeParams if "transpose" in name else DwConvParams)
-            fn.argtypes = [P(st), ctypes.c_void_p]
-        fn.restype = ctypes.c_int
-    lib.sigma_dwconv3x3_silu_bwd_workspace_bytes.argtypes = [P(DwConvParams)]
-    lib.sigma_dwconv3x3_silu_bwd_workspace_bytes.restype = ctypes.c_int64
-    lib.sigma_colscale_bwd_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32]
-    lib.sigma_colscale_bwd_workspace_bytes.restype = ctypes.c_int64
-    lib.sigma_ohem_workspace_bytes.argtypes = [ctypes.c_int64]
-    lib.sigma_ohem_workspace_bytes.restype = ctypes.c_int64
-    for name in GEMM_SYMBOLS:
-        fn = getattr(lib, name)
-        fn.argtypes = [P(GemmParams), ctypes.c_void_p]
-        fn.restype = ctypes.c_int
-    lib.sigma_gemm_selftest.argtypes = [ctypes.c_void_p]
-    lib.sigma_gemm_selftest.restype = ctypes.c_int
-    lib.sigma_gemm_workspace_bytes.argtypes = [P(GemmParams), ctypes.c_int]
-    lib.sigma_gemm_workspace_bytes.restype = ctypes.c_int64
-    lib.sigma_gemm_plan.argtypes = [P(GemmParams), ctypes.c_int, P(ctypes.c_int32 * 8)]
-    lib.sigma_gemm_plan.restype = ctypes.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise SigmaHipUnavailable(f"{LIB_PATH} does not export {name}; rebuild") from e
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.sigma_scan_abi_version() != SIGMA_SCAN_ABI_VERSION:
         raise SigmaHipUnavailable(
             f"ABI mismatch: library {lib.sigma_scan_abi_version()} vs binding {SIGMA_SCAN_ABI_VERSION}; rebuild")

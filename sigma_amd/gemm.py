@@ -32,7 +32,7 @@ import types
 import torch
 import torch.nn as nn
 
-from . import _capi
+from . import _capi, _launch
 
 MIN_DIM = 32               # smaller projections are launch / HBM bound either way
 
@@ -64,19 +64,16 @@ def _selftest(dev) -> None:
     """Once per process and device: sigma_gemm_selftest (csrc/gemm_split.hip) runs the three kernel forms on operands
     whose products are exact in fp32 and compares with host arithmetic -- the operand loads are hand-counted inline
     assembly, so a toolchain that schedules them differently must fail HERE, loudly."""
-    key = (dev.index if dev.index is not None else torch.cuda.current_device())
-    if key in _SELFTESTED:
-        return
-    if torch.cuda.is_current_stream_capturing():
-        # the self test allocates, copies from pageable host memory and synchronises: all illegal inside a capture
-        raise RuntimeError("sigma_amd.gemm: the first split-operand GEMM of this process on this device was issued inside a "
-                           "stream capture; run one step (or sigma_amd.gemm.selftest(device)) eagerly before capturing")
-    with torch.cuda.device(dev):
-        rc = _capi.load().sigma_gemm_selftest(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"sigma_gemm_selftest failed on {dev} (code {rc}): the split-operand GEMM kernels of this build do not "
-                           f"compute A B^T exactly on an exactly representable problem; rebuild libsigma_hip.so with the supported ROCm")
-    _SELFTESTED.add(key)
+
+    def run():
+        rc = _launch.call("sigma_gemm_selftest", device=dev)
+        if rc != 0:
+            raise RuntimeError(f"sigma_gemm_selftest failed on {dev} (code {rc}): the split-operand GEMM kernels of this build do not "
+                               f"compute A B^T exactly on an exactly representable problem; rebuild libsigma_hip.so with the supported ROCm")
+
+    # the self test allocates, copies from pageable host memory and synchronises: all illegal inside a capture
+    _launch.first_use(_SELFTESTED, dev, "sigma_amd.gemm: the first split-operand GEMM of this process on this device was issued "
+                      "inside a stream capture; run one step (or sigma_amd.gemm.selftest(device)) eagerly before capturing", run)
 
 
 def selftest(device=None) -> None:
@@ -115,12 +112,10 @@ def _run(name, p, dev):
         # problems share an output but the query offers no scratch (ragged c_mod): the kernel would add with fp32 atomics
         from .deterministic import no_deterministic_implementation
         no_deterministic_implementation(f"{name} with {p.batch} problems on {p.c_mod} shared outputs")
-    ws = None
-    if need > 0:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _launch.workspace(max(need, 0), dev, name)
+    if ws is not None:
         p.workspace, p.workspace_bytes = ws.data_ptr(), need
-    with torch.cuda.device(dev):
-        rc = getattr(lib, name)(ctypes.byref(p), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    rc = _launch.call(name, ctypes.byref(p), device=dev)
     del ws
     if rc != 0:
         raise RuntimeError(f"{name} failed (sigma_ops status {rc}): M={p.M} N={p.N} K={p.K} lda={p.lda} ldb={p.ldb}")

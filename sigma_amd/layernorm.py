@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 from . import _capi
 from ._handoff import offer_xz_grad_buffer
+from ._launch import launch
 
 
 def _gate_view(z: torch.Tensor, C: int):
@@ -34,7 +35,6 @@ def _gate_view(z: torch.Tensor, C: int):
 class LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps, gate=None, row_scale=None):
-        lib = _capi.load()
         xc = x.contiguous()
         C = xc.shape[-1]
         rows = xc.numel() // C
@@ -57,9 +57,7 @@ class LayerNormFn(torch.autograd.Function):
             if rsc.numel() == 0 or rows % rsc.numel() != 0 or rsc.numel() != xc.shape[0]:
                 raise RuntimeError("LayerNorm row_scale: one factor per sample of the leading dimension")
             p.row_scale, p.rows_per_scale = rsc.data_ptr(), rows // rsc.numel()
-        with torch.cuda.device(x.device):
-            _capi.check(lib.sigma_layernorm_fwd(ctypes.byref(p), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                        "layernorm_fwd")
+        launch("sigma_layernorm_fwd", ctypes.byref(p), device=x.device, what="layernorm_fwd")
         if need_bwd:
             ctx.save_for_backward(xc, weight, mean, rstd, bias if bias is not None else weight.new_empty(0),
                                   zk if zk is not None else weight.new_empty(0), rsc if rsc is not None else weight.new_empty(0))
@@ -122,9 +120,7 @@ def _ln_backward(ctx, dy, dx_add):
             dz = torch.empty(ctx.gate_shape, device=xc.device, dtype=torch.float32)
         p.beta = bias.data_ptr() if ctx.has_bias else None
         p.gate, p.gate_row_stride, p.dgate = zk.data_ptr(), ctx.zstride, dz.data_ptr()
-    with torch.cuda.device(xc.device):
-        _capi.check(lib.sigma_layernorm_bwd(ctypes.byref(p), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                    "layernorm_bwd")
+    launch("sigma_layernorm_bwd", ctypes.byref(p), device=xc.device, what="layernorm_bwd")
     return dx, dgamma, dbeta, None, dz, None
 
 

@@ -11,6 +11,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from ..._launch import launch, ptr
 from ...layernorm import LayerNorm
 import torch.nn.functional as F
 
@@ -22,26 +23,18 @@ class _Up2xFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
-        import ctypes
-        from ... import _capi
         B, H, W, C = x.shape
         out = torch.empty(B, 2 * H, 2 * W, C, device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            _capi.check(_capi.load().sigma_upsample2x_nhwc(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, H, W, C, 0,
-                                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "upsample2x_nhwc")
+        launch("sigma_upsample2x_nhwc", ptr(x), ptr(out), B, H, W, C, 0, device=x.device, what="upsample2x_nhwc")
         ctx.dims = (B, H, W, C)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes
-        from ... import _capi
         B, H, W, C = ctx.dims
         g = g.contiguous()
         dx = torch.empty(B, H, W, C, device=g.device, dtype=torch.float32)
-        with torch.cuda.device(g.device):
-            _capi.check(_capi.load().sigma_upsample2x_nhwc(ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(dx.data_ptr()), B, H, W, C, 1,
-                                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "upsample2x_nhwc (adjoint)")
+        launch("sigma_upsample2x_nhwc", ptr(g), ptr(dx), B, H, W, C, 1, device=g.device, what="upsample2x_nhwc (adjoint)")
         return dx
 
 

@@ -35,14 +35,7 @@ import torch.nn.functional as F
 
 from . import _capi
 from ._handoff import offer_padded_grad_buffer
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
+from ._launch import launch, ptr
 
 
 def _mlp(pooled, w1, w2, batch):
@@ -54,30 +47,29 @@ def _mlp(pooled, w1, w2, batch):
 class ChannelGateFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, w2):
-        lib = _capi.load()
         B, C, H, W = x.shape
         planes, hw = B * C, H * W
         w1m, w2m = w1.reshape(w1.shape[0], -1), w2.reshape(w2.shape[0], -1)
         pooled = torch.empty(2 * planes, device=x.device, dtype=torch.float32)       # [mean (B, C); max (B, C)]
         cnt = torch.empty(planes, device=x.device, dtype=torch.float32)
         with torch.cuda.device(x.device):
-            _capi.check(lib.sigma_plane_pool(_p(x), planes, hw, _p(pooled), _p(pooled[planes:]), _p(cnt), _stream()), "plane_pool")
+            launch("sigma_plane_pool", ptr(x), planes, hw, ptr(pooled), ptr(pooled[planes:]), ptr(cnt), device=x.device,
+                   what="plane_pool")
             s = torch.sigmoid(_mlp(pooled.view(2 * B, C), w1m, w2m, B)).contiguous()
             y = torch.empty_like(x)
-            _capi.check(lib.sigma_plane_scale(_p(x), _p(s), _p(y), planes, hw, _stream()), "plane_scale")
+            launch("sigma_plane_scale", ptr(x), ptr(s), ptr(y), planes, hw, device=x.device, what="plane_scale")
         ctx.save_for_backward(x, w1, w2, pooled, cnt, s)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        lib = _capi.load()
         x, w1, w2, pooled, cnt, s = ctx.saved_tensors
         B, C, H, W = x.shape
         planes, hw = B * C, H * W
         g = g.float().contiguous()
         with torch.cuda.device(x.device):
             ds = torch.empty(B, C, device=x.device, dtype=torch.float32)
-            _capi.check(lib.sigma_plane_dot(_p(g), _p(x), _p(ds), planes, hw, _stream()), "plane_dot")
+            launch("sigma_plane_dot", ptr(g), ptr(x), ptr(ds), planes, hw, device=x.device, what="plane_dot")
             # the (2B, C) squeeze/excite MLP and the sigmoid by hand on tiny tensors (no nested autograd: the step is
             # captured into HIP graphs):  h = P W1^T, a = silu(h), g = a W2^T, gate = g[:B] + g[B:], s = sigmoid(gate)
             w1m, w2m = w1.reshape(w1.shape[0], -1), w2.reshape(w2.shape[0], -1)
@@ -98,7 +90,7 @@ class ChannelGateFn(torch.autograd.Function):
             p.g, p.x, p.scale, p.dx = g.data_ptr(), x.data_ptr(), s.data_ptr(), dx.data_ptr()
             p.dmean, p.dmax = dpl.data_ptr(), dpl[B:].data_ptr()
             p.max, p.count = pooled[planes:].data_ptr(), cnt.data_ptr()
-            _capi.check(lib.sigma_plane_gate_bwd(ctypes.byref(p), _stream()), "plane_gate_bwd")
+            launch("sigma_plane_gate_bwd", ctypes.byref(p), device=x.device, what="plane_gate_bwd")
         return dx, dw1, dw2
 
 
@@ -134,21 +126,18 @@ class ScaleResidualFn(torch.autograd.Function):
             g = g.clone()                           # the kernels load 16 bytes per lane and refuse it
         xc = x.contiguous()
         dx = torch.empty_like(xc)
-        lib = _capi.load()
         if torch.are_deterministic_algorithms_enabled():
             # deterministic mode (sigma_amd/deterministic.py): per-block column sums, added in a fixed order; ds is written
             rows = xc.numel() // C
-            ws_bytes = int(lib.sigma_colscale_bwd_workspace_bytes(rows, C))
+            ws_bytes = int(_capi.load().sigma_colscale_bwd_workspace_bytes(rows, C))
             ws = torch.empty(max(ws_bytes, 16), device=x.device, dtype=torch.uint8)
             ds = torch.empty(C, device=x.device, dtype=torch.float32)
-            with torch.cuda.device(x.device):
-                _capi.check(lib.sigma_colscale_bwd_ws(_p(g), _p(xc), _p(scale), _p(dx), _p(ds), rows, C, _p(ws), ws_bytes,
-                                                      _stream()), "colscale_bwd_ws")
+            launch("sigma_colscale_bwd_ws", ptr(g), ptr(xc), ptr(scale), ptr(dx), ptr(ds), rows, C, ptr(ws), ws_bytes,
+                   device=x.device, what="colscale_bwd_ws")
             return dy, dx, ds
         ds = torch.zeros(C, device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            _capi.check(lib.sigma_colscale_bwd(_p(g), _p(xc), _p(scale), _p(dx), _p(ds), xc.numel() // C, C, _stream()),
-                        "colscale_bwd")
+        launch("sigma_colscale_bwd", ptr(g), ptr(xc), ptr(scale), ptr(dx), ptr(ds), xc.numel() // C, C, device=x.device,
+               what="colscale_bwd")
         return dy, dx, ds
 
 
@@ -166,24 +155,34 @@ def scale_residual(a: torch.Tensor, x: torch.Tensor, scale: torch.Tensor) -> tor
     return torch.addcmul(a, x, scale)
 
 
+def _hand_off_padded(full, nc):
+    """The gradient a loss backward returns for logits of `nc` classes, from the buffer `full` (rows, ld) its kernel
+    wrote: at a padded pitch the classifier's backward claims the WHOLE buffer for its GEMMs (_handoff.py) and autograd
+    gets the view of the first `nc` columns"""
+    if full.shape[1] != nc:
+        offer_padded_grad_buffer(full)
+        full = full[:, :nc]
+    return full
+
+
 class SoftmaxCEFn(torch.autograd.Function):
     """mean over the non-ignored pixels of -log softmax(logits)[label]; logits2 (rows, classes) with contiguous rows at a
     pitch of `ld` floats: the class count itself (sigma_softmax_ce_fwd / _bwd), or a multiple of 4 above it
     (the padded buffer of gemm.ClassifierPadFn; sigma_softmax_ce_fwd_ld / _bwd_ld, the pad is never read)"""
 
     @staticmethod
-    def _call(direction, ld, nc, before, after):
+    def _call(direction, ld, nc, before, after, device):
         """sigma_softmax_ce_<direction>(*before, nc, *after, stream), or its _ld form with the pitch after the class count"""
         name, pitch = (f"softmax_ce_{direction}", ()) if ld == nc else (f"softmax_ce_{direction}_ld", (ld,))
-        _capi.check(getattr(_capi.load(), "sigma_" + name)(*before, nc, *pitch, *after, _stream()), name)
+        launch("sigma_" + name, *before, nc, *pitch, *after, device=device, what=name)
 
     @staticmethod
     def forward(ctx, logits2, labels, ignore_index, ld):
         rows, nc = logits2.shape
         lse = torch.empty(rows, device=logits2.device, dtype=torch.float32)
         partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=logits2.device, dtype=torch.float32)
-        with torch.cuda.device(logits2.device):
-            SoftmaxCEFn._call("fwd", ld, nc, (_p(logits2), _p(labels), rows), (int(ignore_index), _p(lse), _p(partial)))
+        SoftmaxCEFn._call("fwd", ld, nc, (ptr(logits2), ptr(labels), rows), (int(ignore_index), ptr(lse), ptr(partial)),
+                          logits2.device)
         tot = partial.sum(0)
         ctx.save_for_backward(logits2, labels, lse, tot)
         ctx.ignore_index, ctx.ld = int(ignore_index), ld
@@ -198,12 +197,9 @@ class SoftmaxCEFn(torch.autograd.Function):
         # the gradient at the logits' pitch, pad columns written with zeros: the classifier's backward claims the whole
         # buffer for its GEMMs (_handoff.py) -- no zero fill, no re-laying copy
         full = torch.empty_like(logits2) if ld == nc else torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
-        with torch.cuda.device(logits2.device):
-            SoftmaxCEFn._call("bwd", ld, nc, (_p(logits2), _p(labels), _p(lse), _p(scale), rows), (ctx.ignore_index, _p(full)))
-        if ld != nc:
-            offer_padded_grad_buffer(full)
-            full = full[:, :nc]
-        return full, None, None, None
+        SoftmaxCEFn._call("bwd", ld, nc, (ptr(logits2), ptr(labels), ptr(lse), ptr(scale), rows), (ctx.ignore_index, ptr(full)),
+                          logits2.device)
+        return _hand_off_padded(full, nc), None, None, None
 
 
 def _row_pitch(nhwc: torch.Tensor):
@@ -229,8 +225,7 @@ def _rows_forward(ctx, kind, extra, logits2, labels, weight, ignore_index, ld, e
     p = SoftmaxCEOptFn._params(logits2, labels, weight, lse, ignore_index, ld, eps)
     p.partial = partial.data_ptr()
     p.row_loss = row_loss.data_ptr() if row_loss is not None else None
-    with torch.cuda.device(dev):
-        _capi.check(getattr(_capi.load(), f"sigma_softmax_{kind}_fwd")(ctypes.byref(p), *extra, _stream()), f"softmax_{kind}_fwd")
+    launch(f"sigma_softmax_{kind}_fwd", ctypes.byref(p), *extra, device=dev, what=f"softmax_{kind}_fwd")
     return _rows_finish(ctx, kind, extra, logits2, labels, weight, lse, partial, row_loss, ignore_index, ld, eps, reduction, out_shape)
 
 
@@ -266,14 +261,9 @@ def _dlogits(ctx, g):
         p.scale = grad.data_ptr()
     full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
     p.dlogits = full.data_ptr()
-    with torch.cuda.device(logits2.device):
-        _capi.check(getattr(_capi.load(), f"sigma_softmax_{ctx.kind}_bwd")(ctypes.byref(p), *ctx.extra, _stream()),
-                    f"softmax_{ctx.kind}_bwd")
-    if ld != nc:
-        # as SoftmaxCEFn: the classifier's backward claims the whole padded buffer (_handoff.py)
-        offer_padded_grad_buffer(full)
-        full = full[:, :nc]
-    return full
+    launch(f"sigma_softmax_{ctx.kind}_bwd", ctypes.byref(p), *ctx.extra, device=logits2.device,
+           what=f"softmax_{ctx.kind}_bwd")
+    return _hand_off_padded(full, nc)
 
 
 class SoftmaxCEOptFn(torch.autograd.Function):
@@ -330,9 +320,8 @@ def ohem_stages(logits2, labels, weight, ignore_index, ld, thresh, min_kept, wan
     q.weight = weight.data_ptr() if weight is not None else None
     q.row_loss = row_loss.data_ptr() if row_loss is not None else None
     q.partial = partial.data_ptr()                          # overwritten: the unweighted sums of stage 1 are not used
-    with torch.cuda.device(dev):
-        _capi.check(lib.sigma_softmax_ce_opt_fwd(ctypes.byref(p), _stream()), "softmax_ce_opt_fwd (ohem nll)")
-        _capi.check(lib.sigma_ohem_select(ctypes.byref(q), _stream()), "ohem_select")
+    launch("sigma_softmax_ce_opt_fwd", ctypes.byref(p), device=dev, what="softmax_ce_opt_fwd (ohem nll)")
+    launch("sigma_ohem_select", ctypes.byref(q), device=dev, what="ohem_select")
     return dict(lse=lse, nll=nll, mined=mined, tau=tau, counts=counts, partial=partial, row_loss=row_loss)
 
 
@@ -387,8 +376,7 @@ class UpsampledCEFn(torch.autograd.Function):
         partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=dev, dtype=torch.float32)
         p = UpsampledCEFn._params(logits2, labels, lse, dims, ignore_index, ld)
         p.partial = partial.data_ptr()
-        with torch.cuda.device(dev):
-            _capi.check(_capi.load().sigma_upsample_ce_fwd(ctypes.byref(p), _stream()), "upsample_ce_fwd")
+        launch("sigma_upsample_ce_fwd", ctypes.byref(p), device=dev, what="upsample_ce_fwd")
         tot = partial.sum(0)
         ctx.save_for_backward(logits2, labels, lse, tot)
         ctx.ignore_index, ctx.ld, ctx.dims = int(ignore_index), ld, dims
@@ -404,13 +392,8 @@ class UpsampledCEFn(torch.autograd.Function):
         full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
         p = UpsampledCEFn._params(logits2, labels, lse, ctx.dims, ctx.ignore_index, ld)
         p.scale_grad, p.dlogits = grad.data_ptr(), full.data_ptr()
-        with torch.cuda.device(logits2.device):
-            _capi.check(_capi.load().sigma_upsample_ce_bwd(ctypes.byref(p), _stream()), "upsample_ce_bwd")
-        if ld != nc:
-            # as SoftmaxCEFn: the classifier's backward claims the whole padded buffer (_handoff.py)
-            offer_padded_grad_buffer(full)
-            full = full[:, :nc]
-        return full, None, None, None, None
+        launch("sigma_upsample_ce_bwd", ctypes.byref(p), device=logits2.device, what="upsample_ce_bwd")
+        return _hand_off_padded(full, nc), None, None, None, None
 
 
 UPSAMPLED_CE_MAX_CLASSES = 64      # include/sigma_ops.h: sigma_upsample_ce_params.classes

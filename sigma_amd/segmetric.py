@@ -16,10 +16,7 @@ import numpy as np
 import torch
 
 from . import _capi
-
-
-def _stream(dev: torch.device):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+from ._launch import call, launch
 
 
 def _labels(t: torch.Tensor, what: str) -> torch.Tensor:
@@ -45,11 +42,11 @@ def accumulate_scores(acc: torch.Tensor, score: torch.Tensor, first: bool) -> No
     p.classes, p.first = acc.shape[0], int(bool(first))
     p.score, p.acc = score.data_ptr(), acc.data_ptr()
     p.score_plane_stride = p.acc_plane_stride = p.pixels
-    _capi.check(_capi.load().sigma_seg_accumulate(ctypes.byref(p), _stream(acc.device)), "sigma_seg_accumulate")
+    launch("sigma_seg_accumulate", ctypes.byref(p), device=acc.device)
 
 
 def _launch(p, dev) -> None:
-    rc = _capi.load().sigma_seg_argmax_confusion(ctypes.byref(p), _stream(dev))
+    rc = call("sigma_seg_argmax_confusion", ctypes.byref(p), device=dev)
     if rc != 0:
         raise RuntimeError(f"sigma_seg_argmax_confusion: status {rc}")
 

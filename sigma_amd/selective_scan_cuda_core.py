@@ -21,6 +21,7 @@ from typing import List, Optional
 import torch
 
 from . import _capi
+from ._launch import call, first_use, launch, ptr, workspace
 
 _DTYPES = {torch.float32: _capi.DTYPE_F32, torch.float16: _capi.DTYPE_F16, torch.bfloat16: _capi.DTYPE_BF16}
 
@@ -83,10 +84,6 @@ def _check_common(u, delta, A, B, C, D_, delta_bias_, nrows, u_gshift=0):
             _check(tuple(t.shape) == (dim,), f"{name} must have shape (dim)")
             _check(t.stride(-1) == 1 or dim <= 1, f"{name}.stride(-1) must be 1")
     return batch, dim, seqlen, dstate, n_groups
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _f32_vec4(tensors, any_dtype=()) -> bool:
@@ -164,9 +161,9 @@ def _fill_fwd(fp: _capi.FwdParams, u, delta, A, B, C, D_, delta_bias_, out, x, d
     fp.n_chunks = (seqlen + _capi.SIGMA_SCAN_CHUNK - 1) // _capi.SIGMA_SCAN_CHUNK
     fp.io_dtype = _DTYPES[u.dtype]
     fp.delta_softplus = 1 if delta_softplus else 0
-    fp.u, fp.delta, fp.A, fp.B, fp.C = _ptr(u), _ptr(delta), _ptr(A), _ptr(B), _ptr(C)
-    fp.D, fp.delta_bias = _ptr(D_), _ptr(delta_bias_)
-    fp.out, fp.x = _ptr(out), _ptr(x)
+    fp.u, fp.delta, fp.A, fp.B, fp.C = ptr(u), ptr(delta), ptr(A), ptr(B), ptr(C)
+    fp.D, fp.delta_bias = ptr(D_), ptr(delta_bias_)
+    fp.out, fp.x = ptr(out), ptr(x)
     fp.u_batch_stride, fp.u_d_stride = u.stride(0), u.stride(1)
     fp.delta_batch_stride, fp.delta_d_stride = delta.stride(0), delta.stride(1)
     fp.A_d_stride, fp.A_dstate_stride = A.stride(0), A.stride(1)
@@ -193,18 +190,15 @@ def rowlane_selftest(device=None) -> None:
     memory waits are hand-counted, so a toolchain that schedules them differently must fail here, loudly.
     Allocates and synchronises: never inside a stream capture (graphed steps call this before they capture)."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    if key in _ROWLANE_TESTED:
-        return
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("sigma_amd: the first row-lane scan of this process on this device was issued inside a stream "
-                           "capture; run one step (or selective_scan_cuda_core.rowlane_selftest(device)) eagerly first")
-    with torch.cuda.device(dev):
-        rc = _capi.load().sigma_scan_rowlane_selftest(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"sigma_scan_rowlane_selftest failed on {dev} (status {rc}): {_capi.last_error()} -- rebuild "
-                           f"libsigma_hip.so with the supported ROCm toolchain")
-    _ROWLANE_TESTED.add(key)
+
+    def run():
+        rc = call("sigma_scan_rowlane_selftest", device=dev)
+        if rc != 0:
+            raise RuntimeError(f"sigma_scan_rowlane_selftest failed on {dev} (status {rc}): {_capi.last_error()} -- rebuild "
+                               f"libsigma_hip.so with the supported ROCm toolchain")
+
+    first_use(_ROWLANE_TESTED, dev, "sigma_amd: the first row-lane scan of this process on this device was issued inside a "
+              "stream capture; run one step (or selective_scan_cuda_core.rowlane_selftest(device)) eagerly first", run)
 
 
 def fwd_ext(u, delta, A, B, C, D_, delta_bias_, delta_softplus, nrows: int = 1, rev_mask: int = 0,
@@ -239,19 +233,16 @@ def fwd_ext(u, delta, A, B, C, D_, delta_bias_, delta_softplus, nrows: int = 1, 
     fp = _capi.FwdParams()
     _fill_fwd(fp, u, delta, A, B, C, D_, delta_bias_, out, x if need_x else None, delta_softplus, sizes,
               rev_mask, u_gshift, ckpt_pitch, param_swap)
-    workspace = None
+    scratch = None
     if ckpt_pitch == _capi.SIGMA_SCAN_CKPT_PITCH_16:                # few rows: forward summaries of the sequence segments
         rowlane_selftest(u.device)
         ws_bytes = int(lib.sigma_scan_fwd_workspace_bytes(ctypes.byref(fp)))
-        _check(ws_bytes >= 0, "selective_scan_fwd: " + _capi.last_error())
-        if ws_bytes > 0:
-            workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=u.device)
-            fp.workspace, fp.workspace_bytes = _ptr(workspace), ws_bytes
-    with torch.cuda.device(u.device):                               # CUDAGuard, :240
-        stream = torch.cuda.current_stream(u.device).cuda_stream    # :241
+        scratch = workspace(ws_bytes, u.device, "selective_scan_fwd")
+        fp.workspace, fp.workspace_bytes = ptr(scratch), ws_bytes
+    with torch.cuda.device(u.device):                               # CUDAGuard, :240: the hook's events need it too
         key = (batch, dim, seqlen, dstate, sizes[4], u.element_size())
-        _launch("fwd", key, lambda: _capi.check(
-            lib.sigma_selective_scan_fwd(ctypes.byref(fp), ctypes.c_void_p(stream)), "selective_scan_fwd"))
+        _launch("fwd", key, lambda: launch("sigma_selective_scan_fwd", ctypes.byref(fp), device=u.device,
+                                           what="selective_scan_fwd"))
     return [out, x]
 
 
@@ -324,8 +315,8 @@ def bwd_ext(u, delta, A, B, C, D_, delta_bias_, dout, x_, delta_softplus, nrows:
                   ckpt_pitch, param_swap)
         bp.dout_group_shift = int(dout_gshift)
         bp.flags = _capi.SIGMA_SCAN_BWD_DETERMINISTIC if det else 0
-        bp.dout, bp.du, bp.ddelta = _ptr(dout), _ptr(du), _ptr(ddelta)
-        bp.dA, bp.dB, bp.dC, bp.dD, bp.ddelta_bias = _ptr(dA), _ptr(dB), _ptr(dC), _ptr(dD), _ptr(ddelta_bias)
+        bp.dout, bp.du, bp.ddelta = ptr(dout), ptr(du), ptr(ddelta)
+        bp.dA, bp.dB, bp.dC, bp.dD, bp.ddelta_bias = ptr(dA), ptr(dB), ptr(dC), ptr(dD), ptr(ddelta_bias)
         bp.dout_batch_stride, bp.dout_d_stride = dout.stride(0), dout.stride(1)
         bp.du_batch_stride, bp.du_d_stride = du.stride(0), du.stride(1)
         bp.ddelta_batch_stride, bp.ddelta_d_stride = ddelta.stride(0), ddelta.stride(1)
@@ -333,16 +324,13 @@ def bwd_ext(u, delta, A, B, C, D_, delta_bias_, dout, x_, delta_softplus, nrows:
         bp.dB_batch_stride, bp.dB_group_stride, bp.dB_dstate_stride = dB.stride(0), dB.stride(1), dB.stride(2)
         bp.dC_batch_stride, bp.dC_group_stride, bp.dC_dstate_stride = dC.stride(0), dC.stride(1), dC.stride(2)
         ws_bytes = int(lib.sigma_scan_bwd_workspace_bytes(ctypes.byref(bp)))
-        _check(ws_bytes >= 0, "selective_scan_bwd: " + _capi.last_error())
-        workspace = None
-        if ws_bytes > 0:                                 # per-workgroup dB/dC (and deterministic dA/dD/ddelta_bias) partials
-            workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=u.device)
-            bp.workspace, bp.workspace_bytes = _ptr(workspace), ws_bytes
+        # per-workgroup dB/dC (and deterministic dA/dD/ddelta_bias) partials
+        scratch = workspace(ws_bytes, u.device, "selective_scan_bwd")
+        bp.workspace, bp.workspace_bytes = ptr(scratch), ws_bytes
         with torch.cuda.device(u.device):
-            stream = torch.cuda.current_stream(u.device).cuda_stream
             key = (batch, dim, seqlen, dstate, n_groups, u.element_size())
-            _launch("bwd", key, lambda: _capi.check(
-                lib.sigma_selective_scan_bwd(ctypes.byref(bp), ctypes.c_void_p(stream)), "selective_scan_bwd"))
+            _launch("bwd", key, lambda: launch("sigma_selective_scan_bwd", ctypes.byref(bp), device=u.device,
+                                               what="selective_scan_bwd"))
     if dB_out is None:
         dB, dC = dB.to(B.dtype), dC.to(C.dtype)                                  # :360
     return [du, ddelta, dA, dB, dC, dD, ddelta_bias]

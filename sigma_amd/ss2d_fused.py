@@ -26,12 +26,15 @@ these small tensors.
 """
 from __future__ import annotations
 
+import ctypes
+import os
+
 import torch
 
-import os as _os_early
-
+from . import _capi
 from . import gemm as _gemm
 from ._handoff import claim_xz_grad_buffer
+from ._launch import launch, ptr
 from . import selective_scan_cuda_core as _core
 
 # kernel group g -> reference direction k.  g = 2*j + i with j = memory order (0 row-major,
@@ -40,7 +43,7 @@ _PERM = (0, 2, 1, 3)
 _REV_MASK = 0b1010
 # bf16 pieces of the x_proj / dt_proj GEMMs on the split-operand kernels (2 / 3), 0 = the vendor fp32 batched GEMM
 # (SIGMA_GEMM_XPROJ=fp32, or SIGMA_GEMM=fp32 for every GEMM of the model)
-_XPROJ_ALL = _os_early.environ.get("SIGMA_GEMM_XPROJ", "") == "all"
+_XPROJ_ALL = os.environ.get("SIGMA_GEMM_XPROJ", "") == "all"
 _XPROJ = 0 if _gemm.gemm_mode() == "fp32" else (2 if _XPROJ_ALL else _gemm._pieces("SIGMA_GEMM_XPROJ", "2"))
 
 
@@ -53,8 +56,7 @@ def _perm4(t: torch.Tensor) -> torch.Tensor:
 # One state checkpoint per backward tile (no forward sweep in the backward kernel, second-generation
 # backward csrc/scan_bwd2.hip): 640-element tiles, 320 for short sequences (L = 300 pads to 320 instead of
 # 640).  SIGMA_CKPT_PITCH = 0 / 320 / 640 forces one pitch for A/B runs (0 = reference-shaped x, 1280).
-import os as _os
-_CKPT_ENV = _os.environ.get("SIGMA_CKPT_PITCH", "auto")
+_CKPT_ENV = os.environ.get("SIGMA_CKPT_PITCH", "auto")
 
 
 def rowlane_possible() -> bool:
@@ -149,9 +151,6 @@ class DwConvSiLUTwoOrdersFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, n_orders=2):
-        import ctypes
-        from . import _capi
-        lib = _capi.load()
         if not x.is_cuda:
             raise RuntimeError("dwconv3x3_silu: GPU tensors only (no fallback)")
         x = x.float()
@@ -168,18 +167,13 @@ class DwConvSiLUTwoOrdersFn(torch.autograd.Function):
         p.batch, p.channels, p.height, p.width, p.n_orders = B, d, H, W, n_orders
         p.x, p.weight, p.bias, p.out2 = x.data_ptr(), w.data_ptr(), (b.data_ptr() if b is not None else None), out2.data_ptr()
         p.x_batch_stride, p.x_channel_stride = x.stride(0), x.stride(1)
-        with torch.cuda.device(x.device):
-            _capi.check(lib.sigma_dwconv3x3_silu_fwd(ctypes.byref(p), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                        "dwconv3x3_silu_fwd")
+        launch("sigma_dwconv3x3_silu_fwd", ctypes.byref(p), device=x.device, what="dwconv3x3_silu_fwd")
         ctx.save_for_backward(x, w, b if b is not None else x.new_empty(0))
         ctx.has_bias = b is not None
         return out2
 
     @staticmethod
     def backward(ctx, g2):
-        import ctypes
-        from . import _capi
-        lib = _capi.load()
         x, w, b = ctx.saved_tensors
         B, d, H, W = x.shape
         g2 = g2.float().contiguous()
@@ -201,14 +195,12 @@ class DwConvSiLUTwoOrdersFn(torch.autograd.Function):
         p.dbias = db.data_ptr() if db is not None else None
         workspace = None
         if det:
-            ws_bytes = int(lib.sigma_dwconv3x3_silu_bwd_workspace_bytes(ctypes.byref(p)))
+            ws_bytes = int(_capi.load().sigma_dwconv3x3_silu_bwd_workspace_bytes(ctypes.byref(p)))
             if ws_bytes < 0:
                 raise RuntimeError("dwconv3x3_silu_bwd: invalid sizes")
             workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
             p.workspace, p.workspace_bytes = workspace.data_ptr(), ws_bytes
-        with torch.cuda.device(x.device):
-            _capi.check(lib.sigma_dwconv3x3_silu_bwd(ctypes.byref(p), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                        "dwconv3x3_silu_bwd")
+        launch("sigma_dwconv3x3_silu_bwd", ctypes.byref(p), device=x.device, what="dwconv3x3_silu_bwd")
         return dx, dw, db, None
 
 
@@ -223,15 +215,11 @@ def dwconv_silu(x, weight, bias):
 
 
 def _transpose2d(src, dst, B, R, C, src_bs, src_rs, dst_bs, dst_rs):
-    import ctypes
-    from . import _capi
     p = _capi.TransposeParams()
     p.batch, p.rows, p.cols = B, R, C
     p.src, p.dst = src.data_ptr(), dst.data_ptr()
     p.src_batch_stride, p.src_row_stride, p.dst_batch_stride, p.dst_row_stride = src_bs, src_rs, dst_bs, dst_rs
-    with torch.cuda.device(src.device):
-        _capi.check(_capi.load().sigma_transpose2d(ctypes.byref(p), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                    "transpose2d")
+    launch("sigma_transpose2d", ctypes.byref(p), device=src.device, what="transpose2d")
 
 
 class SplitXZFn(torch.autograd.Function):
@@ -326,7 +314,6 @@ def selective_scan_ext(u, delta, A, B, C, D, delta_bias, rev_mask=0, u_gshift=0,
 
 
 def _merge_params(B, d, H, W):
-    from . import _capi
     p = _capi.MergeParams()
     p.batch, p.channels, p.height, p.width = B, d, H, W
     return p
@@ -334,41 +321,29 @@ def _merge_params(B, d, H, W):
 
 def cross_merge_nhwc(ys: torch.Tensor, H: int, W: int) -> torch.Tensor:
     """(B, 4, d, L) scan planes (group order g = 2*order + flipped, natural positions) -> (B, H, W, d)."""
-    import ctypes
-    from . import _capi
     B, _, d, L = ys.shape
     y = torch.empty(B, H, W, d, device=ys.device, dtype=torch.float32)
     p = _merge_params(B, d, H, W)
     p.planes4, p.nhwc = ys.data_ptr(), y.data_ptr()
-    with torch.cuda.device(ys.device):
-        _capi.check(_capi.load().sigma_cross_merge_nhwc(ctypes.byref(p), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                    "cross_merge_nhwc")
+    launch("sigma_cross_merge_nhwc", ctypes.byref(p), device=ys.device, what="cross_merge_nhwc")
     return y
 
 
 def cross_split_nhwc(dy: torch.Tensor) -> torch.Tensor:
     """(B, H, W, d) -> (B, 2, d, L): the gradient once in row-major and once in column-major order."""
-    import ctypes
-    from . import _capi
     B, H, W, d = dy.shape
     g2 = torch.empty(B, 2, d, H * W, device=dy.device, dtype=torch.float32)
     p = _merge_params(B, d, H, W)
     p.planes2, p.nhwc = g2.data_ptr(), dy.data_ptr()
-    with torch.cuda.device(dy.device):
-        _capi.check(_capi.load().sigma_cross_split_nhwc(ctypes.byref(p), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                    "cross_split_nhwc")
+    launch("sigma_cross_split_nhwc", ctypes.byref(p), device=dy.device, what="cross_split_nhwc")
     return g2
 
 
 def _pair_sum_add(src: torch.Tensor, acc: torch.Tensor, n_outer: int, inner: int) -> None:
     """acc (n_outer, inner) += src (n_outer, 2, inner).sum(1), one HIP pass (include/sigma_ops.h)."""
-    import ctypes
-    from . import _capi
     if not (src.is_contiguous() and acc.is_contiguous() and src.dtype == torch.float32 and acc.dtype == torch.float32):
         raise RuntimeError("pair_sum_add: contiguous fp32 tensors only")
-    with torch.cuda.device(src.device):
-        _capi.check(_capi.load().sigma_pair_sum_add(ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(acc.data_ptr()), n_outer, inner,
-                                                    ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "pair_sum_add")
+    launch("sigma_pair_sum_add", ptr(src), ptr(acc), n_outer, inner, device=src.device, what="pair_sum_add")
 
 
 # Tensors derived from the SS2D parameters alone (permuted / stacked / transposed weight copies, A = -exp(A_logs)): a
@@ -382,7 +357,7 @@ def _pair_sum_add(src: torch.Tensor, acc: torch.Tensor, n_outer: int, inner: int
 # version counter) -- code that updates these parameters that way calls ``invalidate_derived_params()`` afterwards, or
 # runs with SIGMA_CACHE_DERIVED=0 (rebuild on every call, the behaviour up to round 3).
 _DERIVED = {}
-_CACHE_DERIVED = _os_early.environ.get("SIGMA_CACHE_DERIVED", "1") != "0"
+_CACHE_DERIVED = os.environ.get("SIGMA_CACHE_DERIVED", "1") != "0"
 
 
 def invalidate_derived_params() -> None:

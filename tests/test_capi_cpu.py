@@ -41,10 +41,13 @@ def test_struct_layout_matches_header(tmp_path):
     ctypes mirror in sigma_amd/_capi.py."""
     import subprocess
     lines = []
-    structs = (("sigma_scan_fwd_params", _capi.FwdParams), ("sigma_scan_bwd_params", _capi.BwdParams),
-               ("sigma_dwconv_params", _capi.DwConvParams), ("sigma_merge_params", _capi.MergeParams),
-               ("sigma_layernorm_params", _capi.LayerNormParams), ("sigma_transpose_params", _capi.TransposeParams),
-               ("sigma_gemm_params", _capi.GemmParams), ("sigma_gate_bwd_params", _capi.GateBwdParams))
+    structs = tuple(_capi.STRUCTS.items())
+    # every struct the three headers define has a mirror, each mirror stands under one name, and no mirror is left out
+    typedefs = {n for h in ("sigma_scan.h", "sigma_ops.h", "sigma_gemm.h")
+                for n in re.findall(r"^\}\s*(sigma_\w+)\s*;", open(os.path.join(ROOT, "include", h)).read(), flags=re.M)}
+    assert typedefs == set(_capi.STRUCTS) and len(typedefs) >= 13, typedefs ^ set(_capi.STRUCTS)
+    mirrors = {v for v in vars(_capi).values() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure}
+    assert mirrors == set(_capi.STRUCTS.values()) and len(mirrors) == len(structs)
     for cname, cls in structs:
         lines.append(f'printf("%s %zu\\n", "{cname}", sizeof({cname}));')
         for fname, _ in cls._fields_:
@@ -58,6 +61,58 @@ def test_struct_layout_matches_header(tmp_path):
         assert int(got[cname]) == ctypes.sizeof(cls)
         for fname, _ in cls._fields_:
             assert int(got[f"{cname}.{fname}"]) == getattr(cls, fname).offset, fname
+
+
+HEADERS = ("sigma_scan.h", "sigma_ops.h", "sigma_gemm.h")
+_RESTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char *": ctypes.c_char_p}
+
+
+def _prototypes():
+    """{name: (return type, [parameter declarations])} of every function the three headers declare"""
+    out = {}
+    for h in HEADERS:
+        text = open(os.path.join(ROOT, "include", h)).read()
+        text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+        text = re.sub(r"//[^\n]*", " ", text)
+        for ret, name, params in re.findall(r"^\s*(const\s+char\s*\*|int64_t|int)\s*(sigma_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+            params = " ".join(params.split())
+            assert name not in out, name
+            out[name] = (" ".join(ret.split()), [] if params in ("", "void") else [q.strip() for q in params.split(",")])
+    return out
+
+
+def test_signature_table_matches_the_prototypes():
+    """Every row of _capi.SIGNATURES against its prototype: the parameter count, the struct behind every
+    ``const sigma_X *`` parameter, the return type -- and no row without a prototype, no prototype without a row."""
+    protos = _prototypes()
+    assert set(protos) == set(_capi.SIGNATURES), set(protos) ^ set(_capi.SIGNATURES)
+    assert len(protos) >= 50
+    n_struct = 0
+    for name, (ret, params) in protos.items():
+        restype, argtypes = _capi.SIGNATURES[name]
+        assert restype is _RESTYPES[ret], name
+        assert len(argtypes) == len(params), (name, params)
+        for i, decl in enumerate(params):
+            m = re.fullmatch(r"(?:const\s+)?(sigma_\w+)\s*\*\s*\w+", decl)
+            if m:
+                assert argtypes[i] is ctypes.POINTER(_capi.STRUCTS[m.group(1)]), (name, i, decl)
+                n_struct += 1
+            else:
+                assert "sigma_" not in decl, (name, decl)          # a struct parameter the pattern above did not take
+                assert not any(argtypes[i] is ctypes.POINTER(cls) for cls in _capi.STRUCTS.values()), (name, i, decl)
+    pointers = {ctypes.POINTER(cls) for cls in _capi.STRUCTS.values()}
+    assert n_struct == sum(a in pointers for _, args in _capi.SIGNATURES.values() for a in args) > 0
+    # the public tuples are the table's groups: a symbol cannot be listed without a signature, or the reverse
+    groups = (_capi.EXPORTED_SYMBOLS, _capi.OPS_SYMBOLS, _capi.OPS_AUX_SYMBOLS, _capi.GEMM_SYMBOLS, _capi.GEMM_AUX_SYMBOLS)
+    assert sorted(n for g in groups for n in g) == sorted(_capi.SIGNATURES)
+
+
+def test_binding_is_complete_after_load():
+    lib = _capi.load()
+    for name, (restype, argtypes) in _capi.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, name
+        assert list(fn.argtypes) == list(argtypes) and all(a is b for a, b in zip(fn.argtypes, argtypes)), name
 
 
 def _params(**kw):
