@@ -71,13 +71,21 @@ def make_optimizer(model: nn.Module, lr: float = 6e-5, weight_decay: float = 0.0
 def _tensor_lrs(opt) -> None:
     """Before a capture: every group's learning rate becomes a device tensor (a Python float -- an optimizer not built by
     ``make_optimizer(capturable=True)``, a float-lr checkpoint loaded with ``load_state_dict``, a manual
-    ``param_groups[i]['lr'] = v`` -- would be baked into the graph and ``set_lr`` would silently do nothing)."""
+    ``param_groups[i]['lr'] = v`` -- would be baked into the graph and ``set_lr`` would silently do nothing).
+    So does a tensor that lives elsewhere than the group's parameters: ``Optimizer.load_state_dict`` of a checkpoint read
+    with ``map_location="cpu"`` moves the state to the parameters' device but leaves ``param_groups[i]['lr']`` a CPU tensor,
+    which the fused AdamW reads once, as a scalar."""
     for g in opt.param_groups:
-        if not torch.is_tensor(g["lr"]):
+        lr = g["lr"]
+        if not torch.is_tensor(lr):
             dev = next((p.device for p in g["params"] if p.is_cuda), None)
             if dev is None:
                 raise RuntimeError("graphed step: optimizer group without GPU parameters")
-            g["lr"] = torch.tensor(float(g["lr"]), device=dev, dtype=torch.float32)
+            g["lr"] = torch.tensor(float(lr), device=dev, dtype=torch.float32)
+        else:
+            dev = next((p.device for p in g["params"]), lr.device)
+            if lr.device != dev:
+                g["lr"] = lr.detach().to(device=dev, dtype=torch.float32)
 
 
 def set_lr(opt, lr: float) -> None:
