@@ -123,14 +123,18 @@ int sigma_gemm_tn_split3(const sigma_gemm_params *params, void *stream);
 
 /*   sigma_gemm_workspace_bytes
  *       bytes of params->workspace with which the launch described by `params` (form 0 = nt, 1 = nn, 2 = tn) sums its
- *       partial results in two stages; 0 = every work item owns its output (no scratch needed); -1 = bad arguments.
+ *       partial results in two stages; 0 = every work item owns its output (no scratch needed); -1 = the launch would be
+ *       refused (whatever sigma_gemm_plan refuses, e.g. a residual with pieces = 3 or more than 2^31 - 1 work items).
  *       params->workspace / workspace_bytes themselves are ignored by the query.                                     */
 int64_t sigma_gemm_workspace_bytes(const sigma_gemm_params *params, int form);
 
 /*   sigma_gemm_plan
- *       host-only: which kernel the launch described by `params` (form 0 = nt, 1 = nn, 2 = tn) runs and how, from the
- *       same planning code as the entry points (nothing is launched, no pointer is dereferenced; params->workspace /
- *       workspace_bytes decide between the two-stage sum and the atomics as they do in the launch).  0 and
+ *       host-only: which kernel the launch described by `params` (form 0 = nt, 1 = nn, 2 = tn) runs and how: the plan
+ *       the entry point makes and launches from, printed (nothing is launched, no pointer is dereferenced;
+ *       params->workspace / workspace_bytes decide between the two-stage sum and the atomics as they do in the launch).
+ *       Every refusal belongs to the plan, so the launch, this query and sigma_gemm_workspace_bytes (-1) agree on it before
+ *       any kernel is enqueued -- among them a residual with pieces = 3 (the kernels that load residuals are two-piece) and
+ *       more than 2^31 - 1 work items: both SIGMA_OPS_ERR_ARG.  0 and
  *           out[0]  tile width (128, 96 or 64 columns; a tile has 128 rows)
  *           out[1], out[2]  row tiles, column tiles          out[3], out[4]  reduction slices, elements per slice
  *           out[5]  work items = problems x tiles x slices (the persistent grid runs at most 1024 at once)

@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "../../include/sigma_gemm.h"
 #include "../../include/sigma_ops.h"
 #include "scan_device.h"
@@ -63,6 +65,17 @@ struct GemmArgs {
     // part_stride floats apart; reduce_parts_kernel then sums the parts of every output into the caller's C
     int nparts; long part_stride;
 };
+
+__host__ __device__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// The two epilogue predicates of gemm_split3_kernel, on the arguments it receives; the planner calls the same two
+// functions to say which path a launch takes (GemmPlan).
+// rows_ok: C rows take 16-byte stores (the row-contiguous epilogue; a second stage with four columns per thread)
+__host__ __device__ inline bool rows_ok(const GemmArgs& g) { return (g.N & 3) == 0 && (g.ldc & 3) == 0 && aligned16(g.C) && (g.sC & 3) == 0; }
+// res_rows: the epilogue addends are read with 16-byte loads
+__host__ __device__ inline bool res_rows(const GemmArgs& g) {
+    return (g.N & 3) == 0 && (g.ldr & 3) == 0 && (g.sR & 3) == 0 && aligned16(g.R) && (g.R2 == nullptr || aligned16(g.R2));
+}
 
 // P bf16 pieces of two floats (packed pairs): piece[0] = bf16(x), piece[1] = bf16(x - piece[0]), piece[2] = bf16 of the
 // next residual: 8 significant bits each, round to nearest even (v_cvt_pk_bf16_f32)
@@ -337,15 +350,14 @@ gemm_split3_kernel(const GemmArgs g) {
     // RES: the accumulators of a tile START as its epilogue addends (C = residual (+ residual2) + A B): the loads land
     // straight in the accumulator registers while the first k-steps are staged, no registers of their own and nothing
     // added to the epilogue.  Wave-uniform base + 32-bit element offsets (host: M * ldr < 2^31); rows / columns past the
-    // matrix are clamped (their sums are never stored).  (res_rows: evaluated again on the host by host_res_rows, below)
-    const bool res_rows = RES && (g.N & 3) == 0 && (g.ldr & 3) == 0 && (g.sR & 3) == 0 && (reinterpret_cast<uintptr_t>(g.R) & 15) == 0 &&
-                          (g.R2 == nullptr || (reinterpret_cast<uintptr_t>(g.R2) & 15) == 0);
+    // matrix are clamped (their sums are never stored).
+    const bool vec_res = RES && res_rows(g);
     auto init_acc = [&](const Item& it) {
         if constexpr (!RES) { zero_acc(); return; }
         const float* __restrict__ r1 = g.R + it.r_off;
         const float* __restrict__ r2 = g.R2 ? g.R2 + it.r_off : nullptr;
         const unsigned ldr = (unsigned)g.ldr;
-        if (res_rows) {
+        if (vec_res) {
             // the mirror image of epilogue_rows: 16-byte loads of 8 x 128 contiguous bytes (both addends summed in
             // registers), one 32 x 32 block at a time through the wave's 4 KB of LDS into accumulator order -- the
             // direct form below is 64 (128 with two addends) dword loads per thread and tile.  The operand image is
@@ -521,8 +533,7 @@ gemm_split3_kernel(const GemmArgs g) {
             }
         }
     };
-    // (rows_ok: evaluated again on the host by host_rows_ok, below)
-    const bool rows_ok = (g.N & 3) == 0 && (g.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(g.C) & 15) == 0 && (g.sC & 3) == 0;
+    const bool vec_rows = rows_ok(g);
 
     while (c_on) {
 #pragma unroll
@@ -591,7 +602,7 @@ gemm_split3_kernel(const GemmArgs g) {
                 // a transposed column range ALWAYS takes the row epilogue (the direct one below knows no t_cols and would
                 // write all N columns into the (N - t_cols)-wide C); plan_nt admits t_cols only with the row epilogue's
                 // preconditions (N % 4, ldc % 4, aligned C, sC = 0 for the single problem, plain stores)
-                if (g.t_cols != 0 || (g.mode != 2 && rows_ok)) {
+                if (g.t_cols != 0 || (g.mode != 2 && vec_rows)) {
                     epilogue_rows(cit, g.mode == 1);
                     lds_barrier();                     // staging areas free before the next tile's operands are written
                 } else if (g.mode == 0) epilogue(cit, [](float* dst, float v) { *dst = v; });
@@ -605,25 +616,29 @@ gemm_split3_kernel(const GemmArgs g) {
     }
 }
 
-template <int BM, int BN, int WM, int WN, bool A_KS, bool B_KS, int P, bool RES>
-hipError_t launch_cfg(const GemmArgs& g, int batch, hipStream_t stream) {
-    const long items = (long)batch * g.ntm * g.ntn * g.slices;
-    if (items <= 0 || items > 0x7fffffffL) return hipErrorInvalidValue;
-    GemmArgs ga = g;
-    ga.batch = batch;
-    // persistent workgroups: as many as are resident at once (register-limited: 2 per CU at 128 x 128, 3-4 for the
-    // narrower tiles); a multiple of the 8 XCDs so that the XCD remap of the item ids keeps its meaning
-    static int per_cu = 0;                              // resident workgroups per CU of this instantiation
-    if (per_cu == 0) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_split3_kernel<BM, BN, WM, WN, A_KS, B_KS, P, RES>, 256, 0) != hipSuccess || n < 1) n = 2;
-        per_cu = n > 4 ? 4 : n;
-    }
-    long grid = 256L * per_cu;
-    if (grid > items) grid = items;
-    hipLaunchKernelGGL((gemm_split3_kernel<BM, BN, WM, WN, A_KS, B_KS, P, RES>), dim3((unsigned)grid), dim3(256), 0, stream, ga);
-    return hipGetLastError();
-}
+// The 24 instantiations, one row each: form (0 = nt, 1 = nn, 2 = tn: which operands are transposed on the way in) x bf16
+// pieces x residual variant x tile width.  Epilogue addends exist for the two-piece nt / nn kernels (the forward and
+// input-gradient GEMMs of the model).
+struct KernelRow {
+    int form, pieces;
+    bool res;
+    int bn;
+    void (*kernel)(const GemmArgs);
+    // resident workgroups per CU of this instantiation, asked once (0: not yet).  Atomic: the forward and the autograd
+    // thread both launch GEMMs.
+    std::atomic<int> per_cu{0};
+};
+
+#define SIGMA_GEMM_ROWS(form, A_KS, B_KS, P, RES)                                     \
+    {form, P, RES, 128, gemm_split3_kernel<128, 128, 2, 2, A_KS, B_KS, P, RES>},      \
+    {form, P, RES, 96, gemm_split3_kernel<128, 96, 4, 1, A_KS, B_KS, P, RES>},        \
+    {form, P, RES, 64, gemm_split3_kernel<128, 64, 2, 2, A_KS, B_KS, P, RES>}
+KernelRow kernel_rows[24] = {
+    SIGMA_GEMM_ROWS(0, false, false, 2, false), SIGMA_GEMM_ROWS(0, false, false, 2, true), SIGMA_GEMM_ROWS(0, false, false, 3, false),
+    SIGMA_GEMM_ROWS(1, false, true, 2, false),  SIGMA_GEMM_ROWS(1, false, true, 2, true),  SIGMA_GEMM_ROWS(1, false, true, 3, false),
+    SIGMA_GEMM_ROWS(2, true, true, 2, false),   SIGMA_GEMM_ROWS(2, true, true, 3, false),
+};
+#undef SIGMA_GEMM_ROWS
 
 // tile width for N columns: 128 unless a narrower tile wastes less ((N = 96, 192: 96-wide tiles are exact)
 int pick_bn(int N) {
@@ -635,33 +650,6 @@ int pick_bn(int N) {
     const int w128 = (N + 127) / 128 * 128 - N, w96 = (N + 95) / 96 * 96 - N;
     return w96 < w128 ? 96 : 128;
 }
-
-template <bool A_KS, bool B_KS, int P, bool RES>
-hipError_t launch_r(GemmArgs& g, int batch, hipStream_t stream) {
-    const int bn = pick_bn(g.N);
-    g.ntm = (int)((g.M + 127) / 128);
-    g.ntn = (g.N + bn - 1) / bn;
-    if (bn == 128) return launch_cfg<128, 128, 2, 2, A_KS, B_KS, P, RES>(g, batch, stream);
-    if (bn == 96) return launch_cfg<128, 96, 4, 1, A_KS, B_KS, P, RES>(g, batch, stream);
-    return launch_cfg<128, 64, 2, 2, A_KS, B_KS, P, RES>(g, batch, stream);
-}
-
-// epilogue addends exist for the two-piece nt / nn kernels (the forward and input-gradient GEMMs of the model)
-template <bool A_KS, bool B_KS, int P>
-hipError_t launch_p(GemmArgs& g, int batch, hipStream_t stream) {
-    if constexpr (P == 2 && !(A_KS && B_KS)) {
-        if (g.R != nullptr) return launch_r<A_KS, B_KS, P, true>(g, batch, stream);
-    }
-    if (g.R != nullptr) return hipErrorInvalidValue;
-    return launch_r<A_KS, B_KS, P, false>(g, batch, stream);
-}
-
-template <bool A_KS, bool B_KS>
-hipError_t launch_any(GemmArgs& g, int batch, int pieces, hipStream_t stream) {
-    return pieces == 3 ? launch_p<A_KS, B_KS, 3>(g, batch, stream) : launch_p<A_KS, B_KS, 2>(g, batch, stream);
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // Second stage of a sliced / shared-output product: C[c] (+)= sum over its nparts compact (M x N) partial results, in a fixed
 // order (deterministic, unlike the atomic sums it replaces).  VEC: four columns per thread (N % 4 == 0, aligned rows).
@@ -708,60 +696,28 @@ reduce_parts_kernel(const float* __restrict__ ws, float* __restrict__ C, long M,
     }
 }
 
-// problem groups of a shared-output launch, ceil(batch / c_mod): with batch % c_mod != 0 the last group is short and the
-// outputs z % c_mod >= batch % c_mod have one group (g.slices parts) less, whose slots in the scratch stay unwritten
-int groups(const GemmArgs& g, int batch) { return g.c_mod > 0 ? (batch + g.c_mod - 1) / g.c_mod : 1; }
-
-// bytes of scratch the two-stage sum of a launch needs (0: a single part per output -- no second stage)
-int64_t parts_bytes(const GemmArgs& g, int batch) {
-    const int per_out = g.slices * groups(g, batch);
-    if (per_out <= 1) return 0;
-    const long outs = g.c_mod > 0 ? g.c_mod : batch;
-    return (int64_t)outs * per_out * g.M * g.N * (int64_t)sizeof(float);
-}
-
-// A launch whose items do not each own their output (reduction slices, problems sharing an output): with enough scratch
-// (ws / ws_bytes from the caller) as plain partial stores + reduce_parts_kernel, otherwise with fp32 atomics into C (which
-// the caller then zero-filled or accumulates into).  Round 6: the 64 dword atomics per thread and item were HALF of a
-// weight-gradient launch (profiles/r06_gemm_phases.jsonl) and its shape-independent floor of ~50 us.
-// the scratch a caller passed carries the two-stage sum of a summed launch (launch_summed; reported by sigma_gemm_plan)
-bool two_stage_ok(const GemmArgs& g, int batch, const void* ws, int64_t ws_bytes) {
-    const int64_t need = parts_bytes(g, batch);
-    return need != 0 && ws != nullptr && ws_bytes >= need && aligned16(ws);
-}
-
-template <bool A_KS, bool B_KS>
-hipError_t launch_summed(GemmArgs& g, int batch, int pieces, void* ws, int64_t ws_bytes, bool accumulate, hipStream_t stream) {
-    if (!two_stage_ok(g, batch, ws, ws_bytes)) {
-        g.mode = 2;
-        g.nparts = 0;
-        return launch_any<A_KS, B_KS>(g, batch, pieces, stream);
-    }
-    float* const C = g.C;
-    const long ldc = g.ldc, sC = g.sC;
-    const int outs = g.c_mod > 0 ? g.c_mod : batch;
-    g.nparts = g.slices * groups(g, batch);
-    const int rag = g.c_mod > 0 ? batch % g.c_mod : 0;
-    const int full_outs = rag ? rag : outs, nparts_short = rag ? g.nparts - g.slices : g.nparts;
-    g.part_stride = g.M * g.N;
-    g.C = static_cast<float*>(ws);
-    g.ldc = g.N;
-    g.sC = 0;
-    g.mode = 0;
-    hipError_t e = launch_any<A_KS, B_KS>(g, batch, pieces, stream);
-    if (e != hipSuccess) return e;
-    const bool vec = (g.N & 3) == 0 && (ldc & 3) == 0 && (sC & 3) == 0 && aligned16(C);
-    const long n_el = g.M * g.N / (vec ? 4 : 1);
-    const long blocks = (n_el + 63) / 64;
-    int pg = 1;                                          // part groups per block: until ~2 waves per SIMD are in flight
-    while (pg < 16 && 2 * pg <= g.nparts && blocks * outs * pg < 2048) pg *= 2;
-    const dim3 grid((unsigned)blocks, (unsigned)outs), block(64, pg);
-    if (vec) hipLaunchKernelGGL(reduce_parts_kernel<true>, grid, block, 0, stream, (const float*)g.C, C, g.M, g.N, ldc, sC, g.nparts, full_outs, nparts_short,
-                                    g.part_stride, accumulate ? 1 : 0);
-    else hipLaunchKernelGGL(reduce_parts_kernel<false>, grid, block, 0, stream, (const float*)g.C, C, g.M, g.N, ldc, sC, g.nparts, full_outs, nparts_short,
-                                    g.part_stride, accumulate ? 1 : 0);
-    return hipGetLastError();
-}
+// ---- the plan of one launch -------------------------------------------------------------------------------------------
+// Everything a launch decides, decided once by plan_gemm (which makes no HIP call): the entry points launch from the
+// plan, sigma_gemm_workspace_bytes and sigma_gemm_plan report it.  Nothing changes the arguments after planning.
+struct GemmPlan {
+    int status;             // SIGMA_OPS_OK, or the code with which the launch is refused
+    bool empty;             // nothing to do
+    int form, pieces, bn;   // the instantiation (KernelRow): form, bf16 pieces, tile width ...
+    bool res;               // ... and the variant that loads the epilogue addends
+    GemmArgs g;             // as the first-stage kernel receives them (two-stage sum: C / ldc / sC are the scratch)
+    long items;             // problems x tiles x slices
+    bool summed;            // the items do not each own their output (reduction slices, problems sharing an output) ...
+    bool two_stage;         // ... and are summed through the scratch by reduce_parts_kernel; otherwise with fp32 atomics
+    int64_t scratch_bytes;  // what the two-stage sum needs, whether or not the caller passed it (0: not summed)
+    struct {                // the second stage: the caller's output and the geometry of reduce_parts_kernel
+        float* C; long ldc, sC;
+        int outs, full_outs, nparts_short;      // (parts per output: g.nparts)
+        bool vec;
+        int part_groups; long blocks;
+        int add;
+    } sum;
+    int epilogue, res_load; // the paths the kernel takes, numbered as out[7] of sigma_gemm_plan (sigma_gemm.h)
+};
 
 int fill_common(const sigma_gemm_params* p, GemmArgs& g) {
     if (!p || !p->A || !p->Bt || !p->C) return SIGMA_OPS_ERR_ARG;
@@ -775,11 +731,10 @@ int fill_common(const sigma_gemm_params* p, GemmArgs& g) {
     g.lda = p->lda; g.ldb = p->ldb; g.ldc = p->ldc;
     // a single problem never steps by strideC: ignored there, so that a stale value cannot unalign the row epilogue
     g.sA = p->strideA; g.sB = p->strideB; g.sC = p->batch > 1 ? p->strideC : 0;
-    g.slices = 1; g.a_mod = 0; g.c_mod = 0;
+    g.batch = p->batch > 0 ? p->batch : 1;
+    g.slices = 1;       // (a_mod, c_mod, the transposed column range and the two-stage fields stay 0: plan_gemm zero-fills)
     g.mode = p->accumulate ? 1 : 0;
     g.R = p->residual; g.R2 = p->residual ? p->residual2 : nullptr; g.ldr = p->ldr; g.sR = p->strideR;
-    g.Ct = nullptr; g.ldct = 0; g.t_cols = 0;
-    g.nparts = 0; g.part_stride = 0;
     if (p->workspace_bytes < 0 || (p->workspace_bytes > 0 && !p->workspace)) return SIGMA_OPS_ERR_ARG;
     if (!p->residual && p->residual2) return SIGMA_OPS_ERR_ARG;
     if (p->residual && (p->ldr <= 0 || p->M * p->ldr >= 0x7fffffffL)) return SIGMA_OPS_ERR_ARG;
@@ -787,101 +742,33 @@ int fill_common(const sigma_gemm_params* p, GemmArgs& g) {
     return SIGMA_OPS_OK;
 }
 
-}  // namespace
-}  // namespace sigma
-
-namespace sigma {
-namespace {
-
-// The three forms: argument checks and launch geometry (shared by the entry points and sigma_gemm_workspace_bytes).
-// `summed`: the items of the launch do not each own their output (launch_summed); `empty`: nothing to do.
-struct Planned { GemmArgs g; int batch; bool summed; bool empty; };
-
-int plan_nt(const sigma_gemm_params* p, Planned& pl) {
+// the kernel's view of the product (rows and columns of C, reduction length), unsliced, and its tiles
+void set_dims(GemmPlan& pl, long M, int N, int K) {
     GemmArgs& g = pl.g;
-    int rc = fill_common(p, g);
-    if (rc) return rc;
-    if (p->K % 4 != 0) return SIGMA_OPS_ERR_ARG;
-    pl.batch = p->batch > 0 ? p->batch : 1;
-    pl.summed = false;
-    pl.empty = p->M == 0 || p->N == 0;
-    if (pl.empty) return SIGMA_OPS_OK;
-    g.M = p->M; g.N = p->N; g.K = p->K;
-    if (p->K == 0) return SIGMA_OPS_ERR_ARG;
-    g.slice_k = (p->K + 31) / 32 * 32;
-    g.a_mod = p->a_mod;
-    if (p->c_mod > 0 && pl.batch > p->c_mod) {       // several problems per output: summed
+    g.M = M; g.N = N; g.K = K;
+    g.slice_k = (K + 31) / 32 * 32;
+    pl.bn = pick_bn(N);
+    g.ntm = (int)((M + 127) / 128);
+    g.ntn = (N + pl.bn - 1) / pl.bn;
+}
+
+// shared outputs (nt / nn): several problems per output are summed
+int share_outputs(const sigma_gemm_params* p, GemmPlan& pl) {
+    if (p->c_mod > 0 && pl.g.batch > p->c_mod) {
         if (p->residual || p->bias) return SIGMA_OPS_ERR_ARG;
-        g.c_mod = p->c_mod; pl.summed = true;
+        pl.g.c_mod = p->c_mod; pl.summed = true;
     }   // batch <= c_mod: problem z owns output z (z % c_mod == z), i.e. the same as c_mod = 0 -- kept at 0 here, so that
         // the scratch of k_slices is sized and reduced for the `batch` outputs that exist, not for c_mod of them
-    if (p->t_cols != 0) {                                // transposed column range: row-contiguous epilogue, plain stores only
-        if (p->t_cols < 0 || p->t_cols > p->N || p->t_cols % 32 != 0 || !p->Ct || !aligned16(p->Ct) || p->ldct % 4 != 0 ||
-            p->ldct < p->M || p->M % 4 != 0 || p->N % 4 != 0 || p->ldc % 4 != 0 || !aligned16(p->C) || pl.batch != 1 ||
-            p->accumulate || p->residual || pl.summed)
-            return SIGMA_OPS_ERR_ARG;
-        g.Ct = p->Ct; g.ldct = p->ldct; g.t_cols = p->t_cols;
-    }
     return SIGMA_OPS_OK;
 }
 
-int plan_nn(const sigma_gemm_params* p, Planned& pl) {
-    // C = A B with B = (K, N) row-major (params->Bt, row stride ldb): the B operand's reduction index is its slow index
+// Reduction slices (tn; nn with k_slices: few output tiles, long reduction): each a multiple of 32 elements and at least 8
+// k-steps long, and no more items than ONE round of resident workgroups (2 per CU): 768 items on 512 slots ran 1.5
+// rounds (round 6: 144 -> 132 us at enc_s2_in_proj, 92 -> 71 us at the small shapes).  One slice leaves the plan as it was.
+void slice_reduction(GemmPlan& pl) {
     GemmArgs& g = pl.g;
-    int rc = fill_common(p, g);
-    if (rc) return rc;
-    if (p->K % 4 != 0 || p->N % 4 != 0) return SIGMA_OPS_ERR_ARG;
-    pl.batch = p->batch > 0 ? p->batch : 1;
-    pl.summed = false;
-    pl.empty = p->M == 0 || p->N == 0;
-    if (pl.empty) return SIGMA_OPS_OK;
-    g.M = p->M; g.N = p->N; g.K = p->K;
-    if (p->K == 0) return SIGMA_OPS_ERR_ARG;
-    g.slice_k = (p->K + 31) / 32 * 32;
-    g.a_mod = p->a_mod;
-    if (p->c_mod > 0 && pl.batch > p->c_mod) {       // several problems per output: summed
-        if (p->residual || p->bias) return SIGMA_OPS_ERR_ARG;
-        g.c_mod = p->c_mod; pl.summed = true;
-    }   // batch <= c_mod: problem z owns output z (z % c_mod == z), i.e. the same as c_mod = 0 -- kept at 0 here, so that
-        // the scratch of k_slices is sized and reduced for the `batch` outputs that exist, not for c_mod of them
-    if (p->k_slices == 1 && !pl.summed && !p->residual && !p->bias && pl.batch == 1) {
-        // few output tiles, long reduction: reduction slices, one round of resident workgroups (as tn)
-        const int bn = pick_bn(g.N);
-        const long tiles = ((g.M + 127) / 128) * ((g.N + bn - 1) / bn);
-        const long steps = (p->K + 31) / 32;
-        long want = 512 / (tiles > 0 ? tiles : 1);
-        if (want > steps / 8) want = steps / 8;
-        if (want > 1) {
-            const long per = (steps + want - 1) / want;
-            g.slice_k = (int)(per * 32);
-            g.slices = (int)((steps + per - 1) / per);
-            if (g.slices > 1) pl.summed = true;
-        }
-    }
-    return SIGMA_OPS_OK;
-}
-
-int plan_tn(const sigma_gemm_params* p, Planned& pl) {
-    // C (N_out x K_in) (+)= A^T B with A = (M, N_out), Bt = (M, K_in): both operands have the reduction (token) index
-    // as the slow memory index.  Kernel view: rows of C = N_out, columns = K_in, reduction = M.
-    GemmArgs& g = pl.g;
-    int rc = fill_common(p, g);
-    if (rc) return rc;
-    if (p->N % 4 != 0 || p->K % 4 != 0) return SIGMA_OPS_ERR_ARG;
-    // nt / nn only; a weight gradient has no bias either (sigma_gemm.h: the tn formula has none)
-    if (p->c_mod != 0 || p->residual || p->bias) return SIGMA_OPS_ERR_ARG;
-    pl.batch = p->batch > 0 ? p->batch : 1;
-    pl.summed = false;
-    pl.empty = p->N == 0 || p->K == 0 || p->M == 0;
-    if (pl.empty) return SIGMA_OPS_OK;
-    g.M = p->N; g.N = p->K; g.K = (int)p->M;
-    if (p->M > 0x7fffff00L) return SIGMA_OPS_ERR_ARG;
-    // reduction slices: each a multiple of 32 tokens and at least 8 k-steps long, and no more items than ONE round of
-    // resident workgroups (2 per CU): 768 items on 512 slots ran 1.5 rounds (round 6: 144 -> 132 us at enc_s2_in_proj,
-    // 92 -> 71 us at the small shapes)
-    const int bn = pick_bn(g.N);
-    const long tiles = (long)pl.batch * ((g.M + 127) / 128) * ((g.N + bn - 1) / bn);
-    const long steps = (p->M + 31) / 32;
+    const long tiles = (long)g.batch * ((g.M + 127) / 128) * g.ntn;
+    const long steps = ((long)g.K + 31) / 32;
     constexpr long target_items = 512;
     long want = target_items / tiles;
     if (want > steps / 8) want = steps / 8;
@@ -890,92 +777,166 @@ int plan_tn(const sigma_gemm_params* p, Planned& pl) {
     g.slice_k = (int)(per * 32);
     g.slices = (int)((steps + per - 1) / per);
     pl.summed = g.slices > 1;
+}
+
+// The three forms: argument checks and the kernel's view of the operands
+int plan_nt(const sigma_gemm_params* p, GemmPlan& pl) {
+    GemmArgs& g = pl.g;
+    if (const int rc = fill_common(p, g)) return rc;
+    if (p->K % 4 != 0) return SIGMA_OPS_ERR_ARG;
+    pl.empty = p->M == 0 || p->N == 0;
+    if (pl.empty) return SIGMA_OPS_OK;
+    if (p->K == 0) return SIGMA_OPS_ERR_ARG;
+    set_dims(pl, p->M, p->N, p->K);
+    g.a_mod = p->a_mod;
+    if (const int rc = share_outputs(p, pl)) return rc;
+    if (p->t_cols != 0) {                                // transposed column range: row-contiguous epilogue, plain stores only
+        if (p->t_cols < 0 || p->t_cols > p->N || p->t_cols % 32 != 0 || !p->Ct || !aligned16(p->Ct) || p->ldct % 4 != 0 ||
+            p->ldct < p->M || p->M % 4 != 0 || p->N % 4 != 0 || p->ldc % 4 != 0 || !aligned16(p->C) || g.batch != 1 ||
+            p->accumulate || p->residual || pl.summed)
+            return SIGMA_OPS_ERR_ARG;
+        g.Ct = p->Ct; g.ldct = p->ldct; g.t_cols = p->t_cols;
+    }
     return SIGMA_OPS_OK;
 }
 
-template <bool A_KS, bool B_KS>
-int run_planned(const sigma_gemm_params* p, Planned& pl, void* stream) {
+int plan_nn(const sigma_gemm_params* p, GemmPlan& pl) {
+    // C = A B with B = (K, N) row-major (params->Bt, row stride ldb): the B operand's reduction index is its slow index
+    GemmArgs& g = pl.g;
+    if (const int rc = fill_common(p, g)) return rc;
+    if (p->K % 4 != 0 || p->N % 4 != 0) return SIGMA_OPS_ERR_ARG;
+    pl.empty = p->M == 0 || p->N == 0;
     if (pl.empty) return SIGMA_OPS_OK;
+    if (p->K == 0) return SIGMA_OPS_ERR_ARG;
+    set_dims(pl, p->M, p->N, p->K);
+    g.a_mod = p->a_mod;
+    if (const int rc = share_outputs(p, pl)) return rc;
+    if (p->k_slices == 1 && !pl.summed && !p->residual && !p->bias && g.batch == 1) slice_reduction(pl);
+    return SIGMA_OPS_OK;
+}
+
+int plan_tn(const sigma_gemm_params* p, GemmPlan& pl) {
+    // C (N_out x K_in) (+)= A^T B with A = (M, N_out), Bt = (M, K_in): both operands have the reduction (token) index
+    // as the slow memory index.  Kernel view: rows of C = N_out, columns = K_in, reduction = M.
+    if (const int rc = fill_common(p, pl.g)) return rc;
+    if (p->N % 4 != 0 || p->K % 4 != 0) return SIGMA_OPS_ERR_ARG;
+    // nt / nn only; a weight gradient has no bias either (sigma_gemm.h: the tn formula has none)
+    if (p->c_mod != 0 || p->residual || p->bias) return SIGMA_OPS_ERR_ARG;
+    pl.empty = p->N == 0 || p->K == 0 || p->M == 0;
+    if (pl.empty) return SIGMA_OPS_OK;
+    if (p->M > 0x7fffff00L) return SIGMA_OPS_ERR_ARG;
+    set_dims(pl, p->N, p->K, (int)p->M);
+    slice_reduction(pl);
+    return SIGMA_OPS_OK;
+}
+
+// What the forms share: the instantiation, the item count and, for a summed launch, how its parts meet.
+// A launch whose items do not each own their output: with enough scratch (params->workspace) as plain partial stores +
+// reduce_parts_kernel, otherwise with fp32 atomics into C (which the caller then zero-filled or accumulates into).
+// Round 6: the 64 dword atomics per thread and item were HALF of a weight-gradient launch
+// (profiles/r06_gemm_phases.jsonl) and its shape-independent floor of ~50 us.
+int plan_launch(const sigma_gemm_params* p, GemmPlan& pl) {
+    GemmArgs& g = pl.g;
+    pl.pieces = p->pieces == 3 ? 3 : 2;
+    pl.res = g.R != nullptr;
+    if (pl.res && (pl.pieces != 2 || pl.form == 2)) return SIGMA_OPS_ERR_ARG;         // no such kernel (kernel_rows)
+    pl.items = (long)g.batch * g.ntm * g.ntn * g.slices;
+    if (pl.items <= 0 || pl.items > 0x7fffffffL) return SIGMA_OPS_ERR_ARG;           // the kernel counts them in an int
+    if (pl.summed) {
+        // problem groups of a shared-output launch, ceil(batch / c_mod): with batch % c_mod != 0 the last group is short and
+        // the outputs z % c_mod >= batch % c_mod have one group (g.slices parts) less, whose slots in the scratch stay unwritten
+        const int groups = g.c_mod > 0 ? (g.batch + g.c_mod - 1) / g.c_mod : 1;
+        const int outs = g.c_mod > 0 ? g.c_mod : g.batch;
+        const int nparts = g.slices * groups;
+        pl.scratch_bytes = (int64_t)outs * nparts * g.M * g.N * (int64_t)sizeof(float);
+        pl.two_stage = p->workspace != nullptr && p->workspace_bytes >= pl.scratch_bytes && aligned16(p->workspace);
+        if (pl.two_stage) {
+            const int rag = g.c_mod > 0 ? g.batch % g.c_mod : 0;
+            auto& s = pl.sum;
+            s.C = g.C; s.ldc = g.ldc; s.sC = g.sC;
+            s.outs = outs;
+            s.full_outs = rag ? rag : outs;
+            s.nparts_short = rag ? nparts - g.slices : nparts;
+            s.vec = rows_ok(g);                          // of the caller's C: the second stage stores there
+            s.blocks = (g.M * g.N / (s.vec ? 4 : 1) + 63) / 64;
+            s.part_groups = 1;                           // per block: until ~2 waves per SIMD are in flight
+            while (s.part_groups < 16 && 2 * s.part_groups <= nparts && s.blocks * outs * s.part_groups < 2048) s.part_groups *= 2;
+            s.add = p->accumulate ? 1 : 0;
+            g.nparts = nparts;
+            g.part_stride = g.M * g.N;
+            g.C = static_cast<float*>(p->workspace); g.ldc = g.N; g.sC = 0;
+            g.mode = 0;
+        } else {
+            g.mode = 2;
+        }
+    }
+    // the epilogue choice at the end of a tile in gemm_split3_kernel, and init_acc's
+    pl.epilogue = g.t_cols != 0 ? 2 : (g.mode != 2 && rows_ok(g)) ? 0 : 1;
+    pl.res_load = !pl.res ? 0 : res_rows(g) ? 1 : 2;
+    return SIGMA_OPS_OK;
+}
+
+GemmPlan plan_gemm(const sigma_gemm_params* p, int form) {
+    GemmPlan pl{};
+    pl.form = form;
+    pl.status = form == 0 ? plan_nt(p, pl) : form == 1 ? plan_nn(p, pl) : form == 2 ? plan_tn(p, pl) : SIGMA_OPS_ERR_ARG;
+    if (pl.status == SIGMA_OPS_OK && !pl.empty) pl.status = plan_launch(p, pl);
+    return pl;
+}
+
+int launch(const GemmPlan& pl, void* stream) {
+    if (pl.status != SIGMA_OPS_OK || pl.empty) return pl.status;
+    KernelRow* row = nullptr;
+    for (KernelRow& r : kernel_rows)
+        if (r.form == pl.form && r.pieces == pl.pieces && r.res == pl.res && r.bn == pl.bn) { row = &r; break; }
+    if (row == nullptr) return SIGMA_OPS_ERR_LAUNCH;      // (the plan refuses what has no row)
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = pl.summed ? launch_summed<A_KS, B_KS>(pl.g, pl.batch, p->pieces, p->workspace, p->workspace_bytes, p->accumulate != 0, s)
-                             : launch_any<A_KS, B_KS>(pl.g, pl.batch, p->pieces, s);
-    return e == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    // persistent workgroups: as many as are resident at once (register-limited: 2 per CU at 128 x 128, 3-4 for the
+    // narrower tiles); a multiple of the 8 XCDs so that the XCD remap of the item ids keeps its meaning
+    int per_cu = row->per_cu.load(std::memory_order_relaxed);
+    if (per_cu == 0) {
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, row->kernel, 256, 0) != hipSuccess || n < 1) n = 2;
+        per_cu = n > 4 ? 4 : n;
+        row->per_cu.store(per_cu, std::memory_order_relaxed);
+    }
+    long grid = 256L * per_cu;
+    if (grid > pl.items) grid = pl.items;
+    hipLaunchKernelGGL(row->kernel, dim3((unsigned)grid), dim3(256), 0, s, pl.g);
+    if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+    if (pl.two_stage) {
+        const GemmArgs& g = pl.g;
+        const auto& r = pl.sum;
+        const auto reduce = r.vec ? reduce_parts_kernel<true> : reduce_parts_kernel<false>;
+        hipLaunchKernelGGL(reduce, dim3((unsigned)r.blocks, (unsigned)r.outs), dim3(64, r.part_groups), 0, s, (const float*)g.C, r.C, g.M, g.N,
+                           r.ldc, r.sC, g.nparts, r.full_outs, r.nparts_short, g.part_stride, r.add);
+        if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+    }
+    return SIGMA_OPS_OK;
 }
 
 }  // namespace
 }  // namespace sigma
 
-extern "C" int sigma_gemm_nt_split3(const sigma_gemm_params* p, void* stream) {
-    sigma::Planned pl;
-    const int rc = sigma::plan_nt(p, pl);
-    return rc ? rc : sigma::run_planned<false, false>(p, pl, stream);
-}
-
-extern "C" int sigma_gemm_nn_split3(const sigma_gemm_params* p, void* stream) {
-    sigma::Planned pl;
-    const int rc = sigma::plan_nn(p, pl);
-    return rc ? rc : sigma::run_planned<false, true>(p, pl, stream);
-}
-
-extern "C" int sigma_gemm_tn_split3(const sigma_gemm_params* p, void* stream) {
-    sigma::Planned pl;
-    const int rc = sigma::plan_tn(p, pl);
-    return rc ? rc : sigma::run_planned<true, true>(p, pl, stream);
-}
+extern "C" int sigma_gemm_nt_split3(const sigma_gemm_params* p, void* stream) { return sigma::launch(sigma::plan_gemm(p, 0), stream); }
+extern "C" int sigma_gemm_nn_split3(const sigma_gemm_params* p, void* stream) { return sigma::launch(sigma::plan_gemm(p, 1), stream); }
+extern "C" int sigma_gemm_tn_split3(const sigma_gemm_params* p, void* stream) { return sigma::launch(sigma::plan_gemm(p, 2), stream); }
 
 extern "C" int64_t sigma_gemm_workspace_bytes(const sigma_gemm_params* p, int form) {
-    sigma::Planned pl;
-    const int rc = form == 0 ? sigma::plan_nt(p, pl) : form == 1 ? sigma::plan_nn(p, pl) : form == 2 ? sigma::plan_tn(p, pl) : SIGMA_OPS_ERR_ARG;
-    if (rc) return -1;
-    return (pl.empty || !pl.summed) ? 0 : sigma::parts_bytes(pl.g, pl.batch);
+    const sigma::GemmPlan pl = sigma::plan_gemm(p, form);
+    return pl.status != SIGMA_OPS_OK ? -1 : pl.scratch_bytes;
 }
-
-namespace sigma {
-namespace {
-
-// The two epilogue predicates the kernel evaluates on its arguments, evaluated on the host for sigma_gemm_plan: the same
-// expressions as `rows_ok` and `res_rows` in gemm_split3_kernel (keep the two places equal), on the GemmArgs the
-// kernel would receive.
-bool host_rows_ok(const GemmArgs& g) { return (g.N & 3) == 0 && (g.ldc & 3) == 0 && aligned16(g.C) && (g.sC & 3) == 0; }
-bool host_res_rows(const GemmArgs& g) {
-    return (g.N & 3) == 0 && (g.ldr & 3) == 0 && (g.sR & 3) == 0 && aligned16(g.R) && (g.R2 == nullptr || aligned16(g.R2));
-}
-
-}  // namespace
-}  // namespace sigma
 
 extern "C" int sigma_gemm_plan(const sigma_gemm_params* p, int form, int32_t out[8]) {
     if (!out) return SIGMA_OPS_ERR_ARG;
     for (int i = 0; i < 8; ++i) out[i] = 0;
-    sigma::Planned pl;
-    const int rc = form == 0 ? sigma::plan_nt(p, pl) : form == 1 ? sigma::plan_nn(p, pl) : form == 2 ? sigma::plan_tn(p, pl) : SIGMA_OPS_ERR_ARG;
-    if (rc) return rc;
-    if (pl.empty) return SIGMA_OPS_OK;
-    sigma::GemmArgs& g = pl.g;
-    const int pieces = p->pieces == 3 ? 3 : 2;                       // launch_any
-    const bool res = g.R != nullptr;
-    if (res && (pieces != 2 || form == 2)) return SIGMA_OPS_ERR_ARG; // launch_p: no such kernel (the launch fails)
-    const int bn = sigma::pick_bn(g.N);                              // launch_r
-    g.ntm = (int)((g.M + 127) / 128);
-    g.ntn = (g.N + bn - 1) / bn;
-    const long items = (long)pl.batch * g.ntm * g.ntn * g.slices;    // launch_cfg
-    if (items <= 0 || items > 0x7fffffffL) return SIGMA_OPS_ERR_ARG;
-    // launch_summed: the arguments the first-stage kernel receives
-    const bool two_stage = pl.summed && sigma::two_stage_ok(g, pl.batch, p->workspace, p->workspace_bytes);
-    bool reduce_vec = false;
-    if (pl.summed && two_stage) {
-        reduce_vec = (g.N & 3) == 0 && (g.ldc & 3) == 0 && (g.sC & 3) == 0 && sigma::aligned16(g.C);
-        g.C = static_cast<float*>(p->workspace); g.ldc = g.N; g.sC = 0; g.mode = 0;
-    } else if (pl.summed) {
-        g.mode = 2;
-    }
-    // the epilogue choice at the end of a tile in gemm_split3_kernel
-    const int epilogue = g.t_cols != 0 ? 2 : (g.mode != 2 && sigma::host_rows_ok(g)) ? 0 : 1;
-    const int res_load = !res ? 0 : sigma::host_res_rows(g) ? 1 : 2;
-    out[0] = bn; out[1] = g.ntm; out[2] = g.ntn; out[3] = g.slices; out[4] = g.slice_k;
-    out[5] = (int32_t)items;
-    out[6] = pieces | (res ? 16 : 0);
-    out[7] = epilogue | (res_load << 2) | (pl.summed ? 16 : 0) | (two_stage ? 32 : 0) | (g.mode << 6) | (reduce_vec ? 256 : 0);
+    const sigma::GemmPlan pl = sigma::plan_gemm(p, form);
+    if (pl.status != SIGMA_OPS_OK || pl.empty) return pl.status;
+    const sigma::GemmArgs& g = pl.g;
+    out[0] = pl.bn; out[1] = g.ntm; out[2] = g.ntn; out[3] = g.slices; out[4] = g.slice_k;
+    out[5] = (int32_t)pl.items;
+    out[6] = pl.pieces | (pl.res ? 16 : 0);
+    out[7] = pl.epilogue | (pl.res_load << 2) | (pl.summed ? 16 : 0) | (pl.two_stage ? 32 : 0) | (g.mode << 6) | (pl.sum.vec ? 256 : 0);
     return SIGMA_OPS_OK;
 }
 

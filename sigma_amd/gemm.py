@@ -82,7 +82,6 @@ def selftest(device=None) -> None:
     _selftest(torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device))
 
 
-_FORMS = {"sigma_gemm_nt_split3": 0, "sigma_gemm_nn_split3": 1, "sigma_gemm_tn_split3": 2}
 # A/B knob: SIGMA_GEMM_TWO_STAGE=0 keeps the round-5 path -- atomic sums into an output the wrappers zero-fill first
 _TWO_STAGE = os.environ.get("SIGMA_GEMM_TWO_STAGE", "1") != "0"
 
@@ -100,6 +99,7 @@ def _atomic_path(out: torch.Tensor, accumulate: bool) -> bool:
 
 
 def _run(name, p, dev):
+    form = _capi.GEMM_FORMS[name[len("sigma_gemm_"):-len("_split3")]]
     _selftest(dev)
     lib = _capi.load()
     # Launches whose work items do not each own their output (reduction slices of a weight gradient, problems sharing an
@@ -107,7 +107,7 @@ def _run(name, p, dev):
     # dword atomics per thread and item (half of such a launch, round 6) -- and the output needs no zero fill.  The
     # buffer comes from torch's caching allocator and goes back when this call returns: stream-ordered, so the kernels
     # enqueued here finish with it before a later allocation on this stream can reuse it.
-    need = int(lib.sigma_gemm_workspace_bytes(ctypes.byref(p), _FORMS[name])) if _two_stage() else 0   # < 0: bad arguments -- the call below says so
+    need = int(lib.sigma_gemm_workspace_bytes(ctypes.byref(p), form)) if _two_stage() else 0   # < 0: bad arguments -- the call below says so
     if need == 0 and p.c_mod > 0 and p.batch > p.c_mod and torch.are_deterministic_algorithms_enabled():
         # problems share an output but the query offers no scratch (ragged c_mod): the kernel would add with fp32 atomics
         from .deterministic import no_deterministic_implementation

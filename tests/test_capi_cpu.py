@@ -342,3 +342,22 @@ def test_gemm_plan_reports_the_kernel_variant_on_the_host():
     assert plan(params(300, 768, 1536, 768, 1536, 1536, bias=0x70000), "tn") is None
     assert plan(params(300, 768, 1536, 768, 1536, 1536), "tn") is not None
     assert plan(params(0, 768, 1536, 1536, 1536, 768), "nt")["items"] == 0       # empty: nothing is launched
+    # Refusals that belong to the plan, so the launch, the plan query and the size query give ONE answer, before any HIP
+    # call (the pointers are fake): SIGMA_OPS_ERR_ARG, SIGMA_OPS_ERR_ARG, -1.  The launch used to find out on its own way
+    # to the kernel (SIGMA_OPS_ERR_LAUNCH) and the size query answered 0, "fine, no scratch".
+    lib = _capi.load()
+
+    def answers(p, form):
+        f, out = _capi.GEMM_FORMS[form], (ctypes.c_int32 * 8)()
+        planned = int(lib.sigma_gemm_plan(ctypes.byref(p), f, ctypes.byref(out)))
+        assert planned != 0, "accepted: not launched on the fake pointers"
+        return (int(getattr(lib, f"sigma_gemm_{form}_split3")(ctypes.byref(p), None)), planned, int(lib.sigma_gemm_workspace_bytes(ctypes.byref(p), f)))
+
+    for form, ldb in (("nt", 1536), ("nn", 768)):
+        # a residual with three pieces: no such kernel
+        assert answers(params(300, 768, 1536, 1536, ldb, 768, residual=0x60000, ldr=768, pieces=3), form) == (1, 1, -1), form
+        assert plan(params(300, 768, 1536, 1536, ldb, 768, residual=0x60000, ldr=768), form)["res"], form    # two pieces: fine
+        # more than 2^31 - 1 work items: 2^30 + 1 tiny problems of two row tiles each (2^30 - 1 of them are 2^31 - 2 items)
+        many = dict(strideA=256 * 4, strideB=4 * 4, strideC=256 * 4)
+        assert answers(params(256, 4, 4, 4, 4, 4, batch=2**30 + 1, **many), form) == (1, 1, -1), form
+        assert plan(params(256, 4, 4, 4, 4, 4, batch=2**30 - 1, **many), form)["items"] == 2**31 - 2, form

@@ -2,6 +2,7 @@
 sensitivity controls on reference code only, and the coverage table -- the GPU file's case list planned with
 sigma_gemm_plan (host only) must reach all 24 kernel instantiations in every regime their form admits."""
 import collections
+import ctypes
 
 import pytest
 import torch
@@ -301,6 +302,13 @@ def coverage(cases):
             wrong.append(f"{c.name}: refused by the planner")
             continue
         inst = (c.form, plan["pieces"], plan["bn"], plan["res"])
+        # the relation the `stage` labels rest on: the size query asks for scratch exactly for the summed launches, and a
+        # summed launch is two-stage exactly when it is given all of that scratch
+        need = int(lib.sigma_gemm_workspace_bytes(ctypes.byref(c.params(c.FAKE)), _capi.GEMM_FORMS[c.form]))
+        if (need > 0) != plan["summed"]:
+            wrong.append(f"{c.name}: the size query answers {need} for a launch planned with summed={plan['summed']}")
+        if plan["two_stage"] != (plan["summed"] and c.ws == "query"):
+            wrong.append(f"{c.name}: two_stage={plan['two_stage']} with summed={plan['summed']} and the scratch {c.ws!r}")
         if (plan["bn"], plan["res"]) != tuple(c.variant) or plan["pieces"] != c.pieces:
             wrong.append(f"{c.name}: plans to {inst}, not to the variant it names {c.variant}")
         table[inst] |= regimes(c, plan)

@@ -107,9 +107,9 @@ def launch_key(lib, name, args):
     if name in ("sigma_gemm_nt_split3", "sigma_gemm_nn_split3", "sigma_gemm_tn_split3"):
         p = args[0]._obj
         form = name[11:13]
-        need = int(lib.sigma_gemm_workspace_bytes(ctypes.byref(p), {"nt": 0, "nn": 1, "tn": 2}[form]))   # gemm_split.hip plan_*
-        stage = "own" if need == 0 else ("two-stage" if p.workspace and p.workspace_bytes >= need else "atomic")
         from sigma_amd import _capi
+        need = int(lib.sigma_gemm_workspace_bytes(ctypes.byref(p), _capi.GEMM_FORMS[form]))   # gemm_split.hip plan_gemm
+        stage = "own" if need == 0 else ("two-stage" if p.workspace and p.workspace_bytes >= need else "atomic")
         plan = _capi.gemm_plan(p, form, lib) or {}                  # sigma_gemm_plan: which kernel runs, with which epilogue
         return ("gemm", form, p.pieces or 2, p.batch > 1, p.a_mod > 0, bool(p.c_mod > 0 and p.batch > p.c_mod),
                 bool(p.k_slices), p.t_cols > 0, int(bool(p.residual)) + int(bool(p.residual2)), bool(p.bias),
