@@ -326,6 +326,56 @@ typedef struct sigma_upsample_ce_params {
 int sigma_upsample_ce_fwd(const sigma_upsample_ce_params *params, void *stream);
 int sigma_upsample_ce_bwd(const sigma_upsample_ce_params *params, void *stream);
 
+/*   sigma_upsample_loss_fwd / sigma_upsample_loss_bwd  (csrc/deepsup.hip; additions only -- a struct and two functions of
+ *   their own, nothing above changes -- the ABI version stays 13)
+ *       The criteria with options on the same interpolated rows z^ (geometry, index function, pad and validity as for
+ *       sigma_upsample_ce_*, whose kernels and bits are untouched): with l = lse(z^(P)), p = softmax(z^(P)), y = labels[P],
+ *       w the class weights (all ones when NULL), W = sum_c w_c,
+ *         kind SIGMA_UPSAMPLE_LOSS_OPTIONS   the row formulas of sigma_softmax_ce_opt_*:
+ *           row_loss[P] = (1 - eps) w_y (l - z^_y) + (eps / classes) (W l - sum_c w_c z^_c)
+ *           d row_loss / d z^_c = (1 - eps) w_y (p_c - [c == y]) + (eps / classes) (W p_c - w_c)
+ *         kind SIGMA_UPSAMPLE_LOSS_FOCAL     those of sigma_softmax_focal_* (q = 1 - p_y, nll = l - z^_y):
+ *           row_loss[P] = w_y q^gamma nll,   d row_loss / d z^_c = w_y m (p_c - [c == y]),  m = q^gamma + gamma q^(gamma - 1) p_y nll
+ *           fwd : lse[P]; row_loss[P] for valid pixels and 0 otherwise (written when row_loss != NULL: reduction 'none', and --
+ *                 OPTIONS with weight = NULL and eps = 0 -- the nll that sigma_ohem_select takes); FOCAL also writes
+ *                 coef[P] = w_y m(P) (0 at pixels that are not valid); partial = SIGMA_CE_BLOCKS pairs (sum of row_loss, sum
+ *                 of w_y), workgroups and pixel order of sigma_upsample_ce_fwd, all written.
+ *           bwd : dlogits[b, i, j, c] = sum over the valid fine pixels P of wgt(P -> (i, j)) g_P d row_loss(P) / d z^_c(P), the
+ *                 gather of sigma_upsample_ce_bwd (same lanes per item, same butterfly; no atomics, bitwise reproducible,
+ *                 exact zeros in columns [classes, ld), fully written).  g_P = scale_grad[0], a DEVICE scalar (upstream / sum
+ *                 of w_y for 'mean', upstream for 'sum'), or row_grad[P] ('none'): exactly one of the two is non-NULL.  FOCAL
+ *                 reads coef and lse as the forward wrote them and does not gather the label's column again.  OHEM: the
+ *                 backward of OPTIONS on the mined labels.
+ *       SIGMA_OPS_ERR_ARG before any launch: everything sigma_upsample_ce_* refuses on the geometry, a kind other than the
+ *       two, label_smoothing outside [0, 1] (NaN included) or non-zero with FOCAL, gamma (FOCAL only) NaN, infinite, negative
+ *       or in (0, 1), a missing or misaligned pointer (logits / dlogits 16 bytes, labels 8, the rest 4; both directions need
+ *       logits, labels, lse and, with FOCAL, coef; fwd needs partial, bwd dlogits), both or neither of scale_grad and
+ *       row_grad in the backward.                                                                                       */
+#define SIGMA_UPSAMPLE_LOSS_OPTIONS 0
+#define SIGMA_UPSAMPLE_LOSS_FOCAL 1
+typedef struct sigma_upsample_loss_params {
+    int32_t batch, height, width;  /* of the COARSE logits                                                   */
+    int32_t scale;                 /* s in [1, 32]: fine size (height * s, width * s)                        */
+    int32_t classes, ld;           /* ld % 4 == 0, ld >= classes, 1 <= classes <= 64                         */
+    int64_t ignore_index;
+    int32_t kind;                  /* SIGMA_UPSAMPLE_LOSS_OPTIONS or SIGMA_UPSAMPLE_LOSS_FOCAL               */
+    float label_smoothing;         /* eps in [0, 1]; 0 with FOCAL                                            */
+    float gamma;                   /* FOCAL: 0 or >= 1; not read otherwise                                   */
+    int32_t reserved_;
+    const float *logits;           /* coarse pixel (b, i, j) at logits + ((b * height + i) * width + j) * ld */
+    const int64_t *labels;         /* (batch, height * s, width * s)                                         */
+    const float *weight;           /* (classes) or NULL = all ones                                           */
+    float *lse;                    /* one float per fine pixel: fwd out, bwd in                              */
+    float *row_loss;               /* fwd out, one float per fine pixel, or NULL                             */
+    float *coef;                   /* FOCAL: one float per fine pixel, fwd out, bwd in; not touched otherwise */
+    float *partial;                /* fwd out: SIGMA_CE_BLOCKS pairs (sum of row_loss, sum of w_y)           */
+    const float *scale_grad;       /* bwd in: device scalar g, or NULL                                       */
+    const float *row_grad;         /* bwd in: g_P per fine pixel, or NULL                                    */
+    float *dlogits;                /* bwd out: coarse, pitch ld, fully written                               */
+} sigma_upsample_loss_params;
+int sigma_upsample_loss_fwd(const sigma_upsample_loss_params *params, void *stream);
+int sigma_upsample_loss_bwd(const sigma_upsample_loss_params *params, void *stream);
+
 /*   sigma_colscale_bwd
  *       backward of  y = a + x * scale with a per-channel `scale` on contiguous channels-last rows (rows, C): the residual
  *       of the decoder block, x * scale1 + op(norm1(x)) and x * scale2 + conv_blk(norm2(x)) (vmamba.py:1800-1805):

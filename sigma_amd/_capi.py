@@ -193,7 +193,20 @@ class UpsampleCeParams(ctypes.Structure):
     ]
 
 
+class UpsampleLossParams(ctypes.Structure):
+    """mirror of sigma_upsample_loss_params (include/sigma_ops.h)"""
+    _fields_ = [
+        ("batch", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("scale", ctypes.c_int32),
+        ("classes", ctypes.c_int32), ("ld", ctypes.c_int32), ("ignore_index", ctypes.c_int64),
+        ("kind", ctypes.c_int32), ("label_smoothing", ctypes.c_float), ("gamma", ctypes.c_float), ("reserved_", ctypes.c_int32),
+        ("logits", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("lse", ctypes.c_void_p),
+        ("row_loss", ctypes.c_void_p), ("coef", ctypes.c_void_p), ("partial", ctypes.c_void_p),
+        ("scale_grad", ctypes.c_void_p), ("row_grad", ctypes.c_void_p), ("dlogits", ctypes.c_void_p),
+    ]
+
+
 SIGMA_CE_BLOCKS = 1024      # include/sigma_ops.h
+SIGMA_UPSAMPLE_LOSS_OPTIONS, SIGMA_UPSAMPLE_LOSS_FOCAL = 0, 1      # include/sigma_ops.h: sigma_upsample_loss_params.kind
 SIGMA_OHEM_HIST_BLOCKS = 512        # include/sigma_ops.h
 SIGMA_SEG_LDS_HIST_BYTES = 32768    # include/sigma_ops.h
 
@@ -209,6 +222,7 @@ STRUCTS = {
     "sigma_layernorm_params": LayerNormParams, "sigma_gate_bwd_params": GateBwdParams,
     "sigma_seg_accumulate_params": SegAccumulateParams, "sigma_seg_confusion_params": SegConfusionParams,
     "sigma_ce_opt_params": CeOptParams, "sigma_ohem_params": OhemParams, "sigma_upsample_ce_params": UpsampleCeParams,
+    "sigma_upsample_loss_params": UpsampleLossParams,
     "sigma_gemm_params": GemmParams,
 }
 
@@ -266,6 +280,7 @@ _OPS_SIGNATURES = {
     "sigma_softmax_focal_fwd": (_INT, [_P(CeOptParams), _F32, _VP]),
     "sigma_softmax_focal_bwd": (_INT, [_P(CeOptParams), _F32, _VP]),
     **_params_stream(UpsampleCeParams, "sigma_upsample_ce_fwd", "sigma_upsample_ce_bwd"),
+    **_params_stream(UpsampleLossParams, "sigma_upsample_loss_fwd", "sigma_upsample_loss_bwd"),
 }
 # ... and its size queries (int64_t results)
 _OPS_AUX_SIGNATURES = {

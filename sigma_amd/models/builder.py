@@ -121,7 +121,8 @@ class EncoderDecoder(nn.Module):
     def _forward_deep(self, rgb, modal_x, label):
         """builder.py:158-166: criterion(x_last) + sum of criterion(x_output_i), every term against the unscaled label.  An
         aux term takes the fused upsample + loss kernels where they apply (pointwise.upsampled_cross_entropy: the plain
-        criterion, up to 64 classes), else the expansion of its coarse logits and the route of the main logits.  Without a
+        criterion; pointwise.upsampled_loss: weights, smoothing, 'sum' / 'none', FocalLoss2d, ProbOhemCrossEntropy2d; up to 64
+        classes), else the expansion of its coarse logits and the route of the main logits.  Without a
         label: x_last alone, the aux heads are not run."""
         self._check_deep_size(rgb.shape[2], rgb.shape[3])
         head = self.decode_head
@@ -129,12 +130,14 @@ class EncoderDecoder(nn.Module):
         if label is None:
             out = head.up_x4(head.forward_up_features(feats), head.patch_size)
             return out if out.is_contiguous() else out.contiguous()
-        from ..pointwise import upsampled_cross_entropy
+        from ..pointwise import upsampled_cross_entropy, upsampled_loss
         from .decoders.MambaDecoder import expand_logits
         x_last, aux = head.forward_deep(feats)
         loss = self._loss(x_last, label)
         for z, s in aux:
             term = upsampled_cross_entropy(self.criterion, z, s, label) if z.is_cuda else None
+            if term is None and z.is_cuda:
+                term = upsampled_loss(self.criterion, z, s, label)
             loss = loss + (term if term is not None else self._loss(expand_logits(z, s), label))
         return loss
 

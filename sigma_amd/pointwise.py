@@ -19,6 +19,10 @@
                    the loss of a deep-supervision head (MambaDecoder.forward_deep) -- with the interpolation inside the
                    loss kernels of csrc/deepsup.hip: no full-size logits exist in either direction (``UpsampledCEFn``).
 
+``upsampled_loss``  the same for the criteria with options -- class weights, label smoothing, 'sum' / 'none', FocalLoss2d and
+                   ProbOhemCrossEntropy2d -- on sigma_upsample_loss_fwd / _bwd and, for OHEM, the selection kernels in
+                   between (``UpsampledLossFn``).
+
 The three front-ends share their checks (``_loss_rows``); the three Functions with options share one forward
 (``_rows_forward`` / ``_rows_finish``: buffers, parameters, saved tensors, reduction) and one backward (``_dlogits``), and
 differ in the entry point they name.
@@ -297,32 +301,42 @@ def ohem_stages(logits2, labels, weight, ignore_index, ld, thresh, min_kept, wan
     on nll: tau, (num_valid, kept), the mined labels and, from nll, `weight` and the mined labels alone, the row losses
     and the SIGMA_CE_BLOCKS partial pairs of the weighted cross entropy on them.  Returns a dict of device tensors;
     nothing is read back."""
-    lib = _capi.load()
-    rows, nc = logits2.shape
+    rows = logits2.shape[0]
     dev = logits2.device
     f32 = dict(device=dev, dtype=torch.float32)
     lse, nll = torch.empty(rows, **f32), torch.empty(rows, **f32)
     partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, **f32)
+    p = SoftmaxCEOptFn._params(logits2, labels, None, lse, ignore_index, ld, 0.0)
+    p.row_loss, p.partial = nll.data_ptr(), partial.data_ptr()
+    launch("sigma_softmax_ce_opt_fwd", ctypes.byref(p), device=dev, what="softmax_ce_opt_fwd (ohem nll)")
+    r = _ohem_select(nll, labels, weight, ignore_index, logits2.shape[1], thresh, min_kept, partial, want_row_loss)
+    return dict(lse=lse, nll=nll, partial=partial, **r)
+
+
+def _ohem_select(nll, labels, weight, ignore_index, nc, thresh, min_kept, partial, want_row_loss):
+    """sigma_ohem_select on the flat per-pixel `nll` and `labels` of `nc` classes: new mined labels, tau, counts and (on
+    request) the row losses; `partial` is OVERWRITTEN with the pairs of the weighted cross entropy on the mined labels (the
+    unweighted sums of the nll pass are not used).  Returns a dict of device tensors; nothing is read back."""
+    lib = _capi.load()
+    rows = nll.numel()
+    dev = nll.device
     mined = torch.empty(rows, device=dev, dtype=torch.int64)
-    tau = torch.empty(1, **f32)
+    tau = torch.empty(1, device=dev, dtype=torch.float32)
     counts = torch.empty(2, device=dev, dtype=torch.int64)
-    row_loss = torch.empty(rows, **f32) if want_row_loss else None
+    row_loss = torch.empty(rows, device=dev, dtype=torch.float32) if want_row_loss else None
     ws_bytes = int(lib.sigma_ohem_workspace_bytes(rows))
     if ws_bytes < 0:
         raise RuntimeError(f"ohem: {rows} rows are more than the selection takes (2^31 - 1)")
     ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
-    p = SoftmaxCEOptFn._params(logits2, labels, None, lse, ignore_index, ld, 0.0)
-    p.row_loss, p.partial = nll.data_ptr(), partial.data_ptr()
     q = _capi.OhemParams()
     q.rows, q.ignore_index, q.classes, q.thresh, q.min_kept = rows, int(ignore_index), nc, float(thresh), int(min_kept)
     q.nll, q.labels, q.mined, q.tau, q.counts = nll.data_ptr(), labels.data_ptr(), mined.data_ptr(), tau.data_ptr(), counts.data_ptr()
     q.workspace, q.workspace_bytes = ws.data_ptr(), ws_bytes
     q.weight = weight.data_ptr() if weight is not None else None
     q.row_loss = row_loss.data_ptr() if row_loss is not None else None
-    q.partial = partial.data_ptr()                          # overwritten: the unweighted sums of stage 1 are not used
-    launch("sigma_softmax_ce_opt_fwd", ctypes.byref(p), device=dev, what="softmax_ce_opt_fwd (ohem nll)")
+    q.partial = partial.data_ptr()
     launch("sigma_ohem_select", ctypes.byref(q), device=dev, what="ohem_select")
-    return dict(lse=lse, nll=nll, mined=mined, tau=tau, counts=counts, partial=partial, row_loss=row_loss)
+    return dict(mined=mined, tau=tau, counts=counts, row_loss=row_loss)
 
 
 class OhemCEFn(torch.autograd.Function):
@@ -408,11 +422,24 @@ def upsampled_cross_entropy(criterion, coarse: torch.Tensor, scale: int, label: 
     ``_row_pitch`` accepts (a multiple of 4, 16-byte aligned, every row's last 16-byte chunk inside the storage), more than 64 classes, a scale outside [1, 32], a label that
     is not on the logits' device with the shape (B, h scale, w scale).  Labels outside [0, classes) count as ignored, as in
     ``cross_entropy``."""
+    if coarse.dim() != 4 or criterion_route(criterion, coarse.device, coarse.shape[3]) != "plain":
+        return None
+    args = _upsampled_rows(coarse, scale, label)
+    if args is None:
+        return None
+    logits2, labels, ld, dims = args
+    return UpsampledCEFn.apply(logits2, labels, criterion.ignore_index, ld, dims)
+
+
+def _upsampled_rows(coarse, scale, label):
+    """What the two upsampled front ends hand to their Function: (logits2, labels, ld, dims) -- the (B h w, classes) view of
+    the coarse logits at its pitch `ld`, the contiguous int64 labels (B, h scale, w scale), dims = (B, h, w, scale) -- or None
+    for what the kernels of csrc/deepsup.hip do not take (the list in ``upsampled_cross_entropy``)"""
     if coarse.dim() != 4 or label.dim() != 3 or not (coarse.is_cuda and coarse.dtype == torch.float32):
         return None
     B, h, w, nc = coarse.shape
     scale = int(scale)
-    if criterion_route(criterion, coarse.device, nc) != "plain" or not 1 <= nc <= UPSAMPLED_CE_MAX_CLASSES:
+    if not 1 <= nc <= UPSAMPLED_CE_MAX_CLASSES:
         return None
     if not 1 <= scale <= UPSAMPLED_CE_MAX_SCALE or label.device != coarse.device or tuple(label.shape) != (B, h * scale, w * scale):
         return None
@@ -425,7 +452,129 @@ def upsampled_cross_entropy(criterion, coarse: torch.Tensor, scale: int, label: 
     floats = (B * h * w - 1) * ld + (nc + 3) // 4 * 4
     if coarse.storage_offset() + floats > coarse.untyped_storage().nbytes() // coarse.element_size():
         return None
-    return UpsampledCEFn.apply(coarse.reshape(-1, nc), label.long().contiguous(), criterion.ignore_index, ld, (B, h, w, scale))
+    return coarse.reshape(-1, nc), label.long().contiguous(), ld, (B, h, w, scale)
+
+
+def upsampled_ohem_stages(logits2, labels, weight, ignore_index, ld, dims, thresh, min_kept, want_row_loss=False):
+    """``ohem_stages`` for coarse logits2 (B h w, classes) at pitch `ld` and labels (B, h s, w s), dims = (B, h, w, s), no
+    autograd: (1) the unweighted sigma_upsample_loss_fwd with a row loss -- lse and nll = lse - z^_y per fine pixel; (2)
+    sigma_ohem_select on nll, exactly as for full-size logits.  Returns the dict of ``ohem_stages`` (mined in the labels'
+    shape, row_loss flat); nothing is read back."""
+    dev = logits2.device
+    lse = torch.empty(labels.shape, device=dev, dtype=torch.float32)
+    nll = torch.empty(labels.shape, device=dev, dtype=torch.float32)
+    partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=dev, dtype=torch.float32)
+    p = UpsampledLossFn._params(logits2, labels, None, lse, None, dims, ignore_index, ld, False, 0.0)
+    p.partial, p.row_loss = partial.data_ptr(), nll.data_ptr()
+    launch("sigma_upsample_loss_fwd", ctypes.byref(p), device=dev, what="upsample_loss_fwd (ohem nll)")
+    r = _ohem_select(nll.view(-1), labels.view(-1), weight, ignore_index, logits2.shape[1], thresh, min_kept, partial, want_row_loss)
+    r["mined"] = r["mined"].view(labels.shape)
+    return dict(lse=lse, nll=nll, partial=partial, **r)
+
+
+class UpsampledLossFn(torch.autograd.Function):
+    """The criteria with options on the rows of ``UpsampledCEFn``: sigma_upsample_loss_fwd / _bwd (csrc/deepsup.hip).
+    `kind` "options" (class weights, label smoothing `x`), "focal" (exponent `x`, 0 or >= 1) or "ohem" (`x` = (thresh,
+    min_kept)): the forward of the options without weight writes the per-pixel nll, sigma_ohem_select mines the labels on
+    the device -- the stages of ``ohem_stages`` -- and the backward of the options runs on the mined labels with the
+    weight.  Reductions as in ``SoftmaxCEOptFn``: 'mean' divides by the summed weights ON THE DEVICE, a zero denominator
+    gives a NaN loss and an all-zero gradient; 'none' returns the per-pixel losses (B, h s, w s).  Saved for the backward:
+    the coarse logits, the (mined) labels, lse and, for focal, coef per fine pixel.  Nothing is read back."""
+
+    @staticmethod
+    def _params(logits2, labels, weight, lse, coef, dims, ignore_index, ld, focal, x):
+        p = _capi.UpsampleLossParams()
+        p.batch, p.height, p.width, p.scale = dims
+        p.classes, p.ld, p.ignore_index = logits2.shape[1], ld, int(ignore_index)
+        p.kind = _capi.SIGMA_UPSAMPLE_LOSS_FOCAL if focal else _capi.SIGMA_UPSAMPLE_LOSS_OPTIONS
+        p.label_smoothing, p.gamma = (0.0, float(x)) if focal else (float(x), 0.0)
+        p.logits, p.labels, p.lse = logits2.data_ptr(), labels.data_ptr(), lse.data_ptr()
+        p.weight = weight.data_ptr() if weight is not None else None
+        p.coef = coef.data_ptr() if coef is not None else None
+        return p
+
+    @staticmethod
+    def forward(ctx, logits2, labels, weight, ignore_index, ld, dims, kind, x, reduction):
+        dev = logits2.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        focal, coef = kind == "focal", None
+        if kind == "ohem":
+            r = upsampled_ohem_stages(logits2, labels, weight, ignore_index, ld, dims, x[0], x[1], want_row_loss=reduction == "none")
+            labels, lse, partial, row_loss, x = r["mined"], r["lse"], r["partial"], r["row_loss"], 0.0
+        else:
+            lse = torch.empty(labels.shape, **f32)
+            partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, **f32)
+            coef = torch.empty(labels.shape, **f32) if focal else None
+            row_loss = torch.empty(labels.shape, **f32) if reduction == "none" else None
+            p = UpsampledLossFn._params(logits2, labels, weight, lse, coef, dims, ignore_index, ld, focal, x)
+            p.partial, p.row_loss = partial.data_ptr(), row_loss.data_ptr() if row_loss is not None else None
+            launch("sigma_upsample_loss_fwd", ctypes.byref(p), device=dev, what=f"upsample_loss_fwd ({kind})")
+        tot = partial.sum(0)
+        ctx.save_for_backward(logits2, labels, lse, tot, weight, coef)
+        ctx.ignore_index, ctx.ld, ctx.dims, ctx.reduction = int(ignore_index), ld, dims, reduction
+        ctx.focal, ctx.x = focal, float(x)
+        if reduction == "none":
+            return row_loss.view(labels.shape)
+        return tot[0] / tot[1] if reduction == "mean" else tot[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        logits2, labels, lse, tot, weight, coef = ctx.saved_tensors
+        rows, nc = logits2.shape
+        ld = ctx.ld
+        p = UpsampledLossFn._params(logits2, labels, weight, lse, coef, ctx.dims, ctx.ignore_index, ld, ctx.focal, ctx.x)
+        if ctx.reduction == "none":
+            grad = g.float().contiguous().view(-1)
+            p.row_grad = grad.data_ptr()
+        else:
+            grad = g.float().reshape(1)
+            if ctx.reduction == "mean":
+                grad = torch.where(tot[1:2] > 0, grad / tot[1:2], torch.zeros_like(grad))      # zero denominator: zero gradient
+            grad = grad.contiguous()
+            p.scale_grad = grad.data_ptr()
+        full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
+        p.dlogits = full.data_ptr()
+        launch("sigma_upsample_loss_bwd", ctypes.byref(p), device=logits2.device, what="upsample_loss_bwd")
+        return (_hand_off_padded(full, nc),) + (None,) * 8
+
+
+def upsampled_loss(criterion, coarse: torch.Tensor, scale: int, label: torch.Tensor):
+    """criterion(upsample(coarse), label) as ``upsampled_cross_entropy`` gives it, for the criteria that function leaves to
+    the expansion (``UpsampledLossFn``): an nn.CrossEntropyLoss with ``criterion_route(...) == "options"`` (class weights,
+    label smoothing, 'sum' / 'none'), a ``FocalLoss2d`` with exponent 0 or >= 1 and a ``ProbOhemCrossEntropy2d`` (thresh in
+    (0, 1]), each with the weight ``_class_weight`` takes.  None where this route does not apply: the plain criterion
+    (it belongs to ``upsampled_cross_entropy``), any other criterion, exponent or weight, and every shape, pitch, alignment,
+    class count, scale and label that function declines.  'none' returns (B, h scale, w scale)."""
+    from .utils.loss_opr import FocalLoss2d, ProbOhemCrossEntropy2d
+    if coarse.dim() != 4:
+        return None
+    nc = coarse.shape[3]
+    if type(criterion) is FocalLoss2d:
+        crit = criterion.loss
+        gamma = float(criterion.exponent)
+        if not (gamma == 0.0 or 1.0 <= gamma < float("inf")):
+            return None
+        kind, x, weight, reduction, ignore = "focal", gamma, crit.weight, crit.reduction, crit.ignore_index
+    elif type(criterion) is ProbOhemCrossEntropy2d:
+        if not 0.0 < criterion.thresh <= 1.0:
+            return None
+        kind, x, weight = "ohem", (criterion.thresh, criterion.min_kept), criterion.criterion.weight
+        reduction, ignore = criterion.reduction, criterion.ignore_label
+    elif criterion_route(criterion, coarse.device, nc) == "options":
+        kind, x, weight = "options", float(criterion.label_smoothing), criterion.weight
+        reduction, ignore = criterion.reduction, criterion.ignore_index
+    else:
+        return None
+    if reduction not in CE_REDUCTIONS:
+        return None
+    args = _upsampled_rows(coarse, scale, label)
+    if args is None:
+        return None
+    ok, w = _class_weight(weight, nc, coarse.device)
+    if not ok:
+        return None
+    logits2, labels, ld, dims = args
+    return UpsampledLossFn.apply(logits2, labels, w, int(ignore), ld, dims, kind, x, reduction)
 
 
 CE_REDUCTIONS = ("mean", "sum", "none")

@@ -52,6 +52,11 @@ fused    ``pointwise.upsampled_cross_entropy`` (csrc/deepsup.hip: the interpolat
 general  the expansion of the coarse logits to full size with two constant interpolation matrices (torch matmul) and the
          plain loss Function on the result (``pointwise.cross_entropy``), i.e. what the model does where the fused route
          declines.
+``--criterion weighted | smoothed | focal | ohem`` (with --deepsup; the default is the plain criterion) times the same two
+routes for a criterion with options: fused is ``pointwise.upsampled_loss``, general the criterion's own route on the expanded
+logits, as the model runs it; class weights in [0.1, 2.1], smoothing 0.1 on top of them, the focal exponent 2, OHEM with
+thresh 0.7 and min_kept 100000.  The lines carry ``criterion`` and ``fused_beats_general_2iqr`` (the gap above twice the
+larger inter-quartile range: the rule by which the model routes a criterion to the fused kernels).
 One line per (shape, classes) and one per class count for the sum over the three heads.  ``fused_beats_general``: the
 difference of the medians is larger than the larger of the two inter-quartile ranges.  ``bytes``: what each route moves
 algorithmically (see ``deepsup_bytes``).  A process runs at its own level (0.04 - 0.06 ms apart on these streams), which the
@@ -263,6 +268,7 @@ def focal_main(a, dev):
 
 
 DEEPSUP_SHAPES = [(8, 30, 40, 16), (8, 60, 80, 8), (8, 120, 160, 4)]
+DEEPSUP_CRITERIA = ("plain", "weighted", "smoothed", "focal", "ohem")
 
 
 def deepsup_bytes(B, h, w, s, ld):
@@ -277,11 +283,28 @@ def deepsup_bytes(B, h, w, s, ld):
 
 def deepsup_main(a, dev):
     from sigma_amd.models.decoders.MambaDecoder import expand_logits
-    from sigma_amd.pointwise import cross_entropy, upsampled_cross_entropy
-    plain = nn.CrossEntropyLoss(reduction="mean", ignore_index=IGNORE)
+    from sigma_amd.pointwise import cross_entropy, upsampled_cross_entropy, upsampled_loss
+    from sigma_amd.utils.loss_opr import FocalLoss2d, ProbOhemCrossEntropy2d
+    kind = a.criterion[0]
+    if len(a.criterion) != 1 or kind not in DEEPSUP_CRITERIA:
+        raise SystemExit(f"--deepsup takes one --criterion of {', '.join(DEEPSUP_CRITERIA)}")
     tag = {} if a.run is None else {"run": a.run}
+    if kind != "plain":
+        tag["criterion"] = kind
     lines = []
     for nc, ld in ((40, 40), (9, 12)):
+        cw = (torch.rand(nc, generator=torch.Generator().manual_seed(7)) * 2.0 + 0.1).to(dev)
+        plain = {"plain": lambda: nn.CrossEntropyLoss(reduction="mean", ignore_index=IGNORE),
+                 "weighted": lambda: nn.CrossEntropyLoss(weight=cw, ignore_index=IGNORE),
+                 "smoothed": lambda: nn.CrossEntropyLoss(weight=cw, ignore_index=IGNORE, label_smoothing=0.1),
+                 "focal": lambda: FocalLoss2d(weight=cw, ignore_index=IGNORE).to(dev),
+                 "ohem": lambda: ProbOhemCrossEntropy2d(IGNORE, thresh=0.7, min_kept=100000, weight=cw).to(dev)}[kind]()
+        fused_fn = upsampled_cross_entropy if kind == "plain" else upsampled_loss
+        # the general route is the model's: the criterion's own route on the expanded logits (EncoderDecoder._loss)
+        general_fn = (lambda crit, out, lab: crit(out, lab)) if kind in ("focal", "ohem") else cross_entropy
+        names = {"plain": ("UpsampledCEFn", "SoftmaxCEFn"), "weighted": ("UpsampledLossFn", "SoftmaxCEOptFn"),
+                 "smoothed": ("UpsampledLossFn", "SoftmaxCEOptFn"), "focal": ("UpsampledLossFn", "SoftmaxFocalFn"),
+                 "ohem": ("UpsampledLossFn", "OhemCEFn")}[kind]
         total = {"fused": [0.0] * a.reps, "general": [0.0] * a.reps}
         for B, h, w, s in DEEPSUP_SHAPES:
             g = torch.Generator().manual_seed(1234)
@@ -291,8 +314,8 @@ def deepsup_main(a, dev):
             label = torch.randint(0, nc, (B, h * s, w * s), generator=g)
             label[torch.rand(label.shape, generator=g) < 0.1] = IGNORE
             label = label.to(dev)
-            routes = {"fused": lambda: upsampled_cross_entropy(plain, buf[..., :nc], s, label),
-                      "general": lambda: cross_entropy(plain, expand_logits(buf[..., :nc], s), label)}
+            routes = {"fused": lambda: fused_fn(plain, buf[..., :nc], s, label),
+                      "general": lambda: general_fn(plain, expand_logits(buf[..., :nc], s), label)}
             times = {k: [] for k in routes}
             losses, grads = {}, {}
             for i in range(a.warmup + a.reps):
@@ -307,8 +330,8 @@ def deepsup_main(a, dev):
                     if i >= a.warmup:
                         times[k].append(t0.elapsed_time(t1))
                     losses[k], grads[k] = float(loss.detach()), buf.grad
-            assert type(routes["fused"]().grad_fn).__name__.startswith("UpsampledCEFn")
-            assert type(routes["general"]().grad_fn).__name__.startswith("SoftmaxCEFn")
+            assert type(routes["fused"]().grad_fn).__name__.startswith(names[0])
+            assert type(routes["general"]().grad_fn).__name__.startswith(names[1])
             for k in total:
                 total[k] = [x + y for x, y in zip(total[k], times[k])]
             sp = {k: spread(v) for k, v in times.items()}
@@ -319,6 +342,8 @@ def deepsup_main(a, dev):
                     "loss_fused": losses["fused"], "loss_general": losses["general"],
                     "max_grad_diff": float((grads["fused"] - grads["general"]).abs().max()), "max_grad": float(grads["general"].abs().max()),
                     "bytes": deepsup_bytes(B, h, w, s, ld), "device": torch.cuda.get_device_name(0)}
+            if kind != "plain":            # the routing rule of DESIGN.md 4.4: the gap above twice the larger spread
+                line["fused_beats_general_2iqr"] = bool(gap > 2 * max(sp["fused"]["iqr_ms"], sp["general"]["iqr_ms"]))
             print(json.dumps(line), flush=True)
             lines.append(line)
             del buf, label, grads
@@ -383,7 +408,8 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default="")
-    ap.add_argument("--criterion", nargs="+", default=["plain"], choices=["plain", "weight", "weight_eps"])
+    ap.add_argument("--criterion", nargs="+", default=["plain"], choices=["plain", "weight", "weight_eps", "weighted", "smoothed", "focal", "ohem"],
+                    help="plain / weight / weight_eps: the head shapes; --deepsup: one of plain, weighted, smoothed, focal, ohem")
     ap.add_argument("--ohem", action="store_true", help="time the OHEM loss against the plain loss and a torch composition")
     ap.add_argument("--focal", action="store_true", help="time the focal loss against the plain loss and the torch formulation")
     ap.add_argument("--deepsup", action="store_true", help="time the fused upsample + loss of a deep-supervision head against the expansion")
@@ -402,6 +428,8 @@ def main():
                 for line in lines:
                     f.write(json.dumps(line) + "\n")
         return
+    if not set(a.criterion) <= {"plain", "weight", "weight_eps"}:
+        ap.error("weighted, smoothed, focal and ohem are criteria of --deepsup")
     plain = nn.CrossEntropyLoss(reduction="mean", ignore_index=IGNORE)
     lines = []
     for B, H, W, C, nc, kind in [(*shape, kind) for kind in a.criterion for shape in SHAPES]:
