@@ -293,6 +293,7 @@ int sigma_ohem_select(const sigma_ohem_params *params, void *stream);
 int64_t sigma_ohem_workspace_bytes(int64_t rows);
 
 /*   sigma_upsample_ce_fwd / sigma_upsample_ce_bwd  (csrc/deepsup.hip; additions only, the ABI version stays 13)
+ *       The plain kind of the one forward and the one backward kernel template that also serve sigma_upsample_loss_* below.
  *       nn.CrossEntropyLoss(reduction='mean', ignore_index) of the bilinear x `scale` upsampling (align_corners=False) of
  *       COARSE channels-last logits: the loss of the deep-supervision heads of MambaDecoder (models/decoders/
  *       MambaDecoder.py:264-270, models/builder.py:158-166) with the bias-free 1x1 head run BEFORE the interpolation -- the
@@ -329,7 +330,8 @@ int sigma_upsample_ce_bwd(const sigma_upsample_ce_params *params, void *stream);
 /*   sigma_upsample_loss_fwd / sigma_upsample_loss_bwd  (csrc/deepsup.hip; additions only -- a struct and two functions of
  *   their own, nothing above changes -- the ABI version stays 13)
  *       The criteria with options on the same interpolated rows z^ (geometry, index function, pad and validity as for
- *       sigma_upsample_ce_*, whose kernels and bits are untouched): with l = lse(z^(P)), p = softmax(z^(P)), y = labels[P],
+ *       sigma_upsample_ce_*: further kinds of the same two kernel templates, which apply the upstream gradient per fine
+ *       pixel where the plain kind scales the finished sum once): with l = lse(z^(P)), p = softmax(z^(P)), y = labels[P],
  *       w the class weights (all ones when NULL), W = sum_c w_c,
  *         kind SIGMA_UPSAMPLE_LOSS_OPTIONS   the row formulas of sigma_softmax_ce_opt_*:
  *           row_loss[P] = (1 - eps) w_y (l - z^_y) + (eps / classes) (W l - sum_c w_c z^_c)

@@ -17,11 +17,12 @@
 
 ``upsampled_cross_entropy``  the plain mean cross entropy of the bilinear x s upsampling of COARSE channels-last logits --
                    the loss of a deep-supervision head (MambaDecoder.forward_deep) -- with the interpolation inside the
-                   loss kernels of csrc/deepsup.hip: no full-size logits exist in either direction (``UpsampledCEFn``).
+                   loss kernels of csrc/deepsup.hip: no full-size logits exist in either direction (``UpsampledLossFn``, kind
+                   "plain").
 
 ``upsampled_loss``  the same for the criteria with options -- class weights, label smoothing, 'sum' / 'none', FocalLoss2d and
                    ProbOhemCrossEntropy2d -- on sigma_upsample_loss_fwd / _bwd and, for OHEM, the selection kernels in
-                   between (``UpsampledLossFn``).
+                   between (the other kinds of ``UpsampledLossFn``).
 
 The three front-ends share their checks (``_loss_rows``); the three Functions with options share one forward
 (``_rows_forward`` / ``_rows_finish``: buffers, parameters, saved tensors, reduction) and one backward (``_dlogits``), and
@@ -369,54 +370,13 @@ class SoftmaxFocalFn(torch.autograd.Function):
         return (_dlogits(ctx, g),) + (None,) * 7
 
 
-class UpsampledCEFn(torch.autograd.Function):
-    """mean over the non-ignored pixels of -log softmax(upsample_s(logits))[label] for coarse logits2 (B h w, classes) at a
-    pitch of `ld` floats and labels (B, h s, w s): sigma_upsample_ce_fwd / _bwd (csrc/deepsup.hip).  Saved for the backward:
-    the coarse logits, the labels and one lse per fine pixel.  Nothing is read back; nothing labelled gives a NaN loss
-    (0 / 0) and an all-zero gradient, as ``SoftmaxCEFn`` / ``_dlogits`` do."""
-
-    @staticmethod
-    def _params(logits2, labels, lse, dims, ignore_index, ld):
-        p = _capi.UpsampleCeParams()
-        p.batch, p.height, p.width, p.scale = dims
-        p.classes, p.ld, p.ignore_index = logits2.shape[1], ld, int(ignore_index)
-        p.logits, p.labels, p.lse = logits2.data_ptr(), labels.data_ptr(), lse.data_ptr()
-        return p
-
-    @staticmethod
-    def forward(ctx, logits2, labels, ignore_index, ld, dims):
-        dev = logits2.device
-        lse = torch.empty(labels.shape, device=dev, dtype=torch.float32)
-        partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=dev, dtype=torch.float32)
-        p = UpsampledCEFn._params(logits2, labels, lse, dims, ignore_index, ld)
-        p.partial = partial.data_ptr()
-        launch("sigma_upsample_ce_fwd", ctypes.byref(p), device=dev, what="upsample_ce_fwd")
-        tot = partial.sum(0)
-        ctx.save_for_backward(logits2, labels, lse, tot)
-        ctx.ignore_index, ctx.ld, ctx.dims = int(ignore_index), ld, dims
-        return tot[0] / tot[1]
-
-    @staticmethod
-    def backward(ctx, g):
-        logits2, labels, lse, tot = ctx.saved_tensors
-        rows, nc = logits2.shape
-        ld = ctx.ld
-        grad = g.float().reshape(1)
-        grad = torch.where(tot[1:2] > 0, grad / tot[1:2], torch.zeros_like(grad)).contiguous()      # nothing labelled: zeros
-        full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
-        p = UpsampledCEFn._params(logits2, labels, lse, ctx.dims, ctx.ignore_index, ld)
-        p.scale_grad, p.dlogits = grad.data_ptr(), full.data_ptr()
-        launch("sigma_upsample_ce_bwd", ctypes.byref(p), device=logits2.device, what="upsample_ce_bwd")
-        return _hand_off_padded(full, nc), None, None, None, None
-
-
 UPSAMPLED_CE_MAX_CLASSES = 64      # include/sigma_ops.h: sigma_upsample_ce_params.classes
 UPSAMPLED_CE_MAX_SCALE = 32
 
 
 def upsampled_cross_entropy(criterion, coarse: torch.Tensor, scale: int, label: torch.Tensor):
     """criterion(upsample(coarse), label) for the bilinear x `scale` upsampling (align_corners=False) of channels-last
-    logits `coarse` (B, h, w, classes), without the upsampled tensor (``UpsampledCEFn``) -- or None when this route does
+    logits `coarse` (B, h, w, classes), without the upsampled tensor (``UpsampledLossFn``, kind "plain") -- or None when this route does
     not apply: anything but the plain criterion (``criterion_route(...) == "plain"``: weights, smoothing, 'sum' / 'none',
     OHEM and focal take the expansion, MambaDecoder.expand_logits), logits that are not fp32 GPU rows at a pitch
     ``_row_pitch`` accepts (a multiple of 4, 16-byte aligned, every row's last 16-byte chunk inside the storage), more than 64 classes, a scale outside [1, 32], a label that
@@ -428,11 +388,11 @@ def upsampled_cross_entropy(criterion, coarse: torch.Tensor, scale: int, label: 
     if args is None:
         return None
     logits2, labels, ld, dims = args
-    return UpsampledCEFn.apply(logits2, labels, criterion.ignore_index, ld, dims)
+    return UpsampledLossFn.apply(logits2, labels, None, criterion.ignore_index, ld, dims, "plain", 0.0, "mean")
 
 
 def _upsampled_rows(coarse, scale, label):
-    """What the two upsampled front ends hand to their Function: (logits2, labels, ld, dims) -- the (B h w, classes) view of
+    """What the two upsampled front ends hand to ``UpsampledLossFn``: (logits2, labels, ld, dims) -- the (B h w, classes) view of
     the coarse logits at its pitch `ld`, the contiguous int64 labels (B, h scale, w scale), dims = (B, h, w, scale) -- or None
     for what the kernels of csrc/deepsup.hip do not take (the list in ``upsampled_cross_entropy``)"""
     if coarse.dim() != 4 or label.dim() != 3 or not (coarse.is_cuda and coarse.dtype == torch.float32):
@@ -464,55 +424,63 @@ def upsampled_ohem_stages(logits2, labels, weight, ignore_index, ld, dims, thres
     lse = torch.empty(labels.shape, device=dev, dtype=torch.float32)
     nll = torch.empty(labels.shape, device=dev, dtype=torch.float32)
     partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, device=dev, dtype=torch.float32)
-    p = UpsampledLossFn._params(logits2, labels, None, lse, None, dims, ignore_index, ld, False, 0.0)
+    name, p = UpsampledLossFn._params("options", logits2, labels, None, lse, None, dims, ignore_index, ld, 0.0)
     p.partial, p.row_loss = partial.data_ptr(), nll.data_ptr()
-    launch("sigma_upsample_loss_fwd", ctypes.byref(p), device=dev, what="upsample_loss_fwd (ohem nll)")
+    launch(f"sigma_{name}_fwd", ctypes.byref(p), device=dev, what=f"{name}_fwd (ohem nll)")
     r = _ohem_select(nll.view(-1), labels.view(-1), weight, ignore_index, logits2.shape[1], thresh, min_kept, partial, want_row_loss)
     r["mined"] = r["mined"].view(labels.shape)
     return dict(lse=lse, nll=nll, partial=partial, **r)
 
 
 class UpsampledLossFn(torch.autograd.Function):
-    """The criteria with options on the rows of ``UpsampledCEFn``: sigma_upsample_loss_fwd / _bwd (csrc/deepsup.hip).
-    `kind` "options" (class weights, label smoothing `x`), "focal" (exponent `x`, 0 or >= 1) or "ohem" (`x` = (thresh,
-    min_kept)): the forward of the options without weight writes the per-pixel nll, sigma_ohem_select mines the labels on
-    the device -- the stages of ``ohem_stages`` -- and the backward of the options runs on the mined labels with the
-    weight.  Reductions as in ``SoftmaxCEOptFn``: 'mean' divides by the summed weights ON THE DEVICE, a zero denominator
-    gives a NaN loss and an all-zero gradient; 'none' returns the per-pixel losses (B, h s, w s).  Saved for the backward:
-    the coarse logits, the (mined) labels, lse and, for focal, coef per fine pixel.  Nothing is read back."""
+    """Every criterion of a deep-supervision head on coarse logits2 (B h w, classes) at a pitch of `ld` floats and labels
+    (B, h s, w s), dims = (B, h, w, s): the kernels of csrc/deepsup.hip.  `kind` "plain" (the mean cross entropy: no weight,
+    reduction 'mean'; sigma_upsample_ce_fwd / _bwd), or, on sigma_upsample_loss_fwd / _bwd, "options" (class weights, label
+    smoothing `x`), "focal" (exponent `x`, 0 or >= 1) or "ohem" (`x` = (thresh, min_kept)): the forward of the options
+    without weight writes the per-pixel nll, sigma_ohem_select mines the labels on the device -- the stages of
+    ``ohem_stages`` -- and the backward of the options runs on the mined labels with the weight.  Reductions as in
+    ``SoftmaxCEOptFn``: 'mean' divides by the summed weights ON THE DEVICE, a zero denominator (nothing labelled) gives a
+    NaN loss and an all-zero gradient; 'none' returns the per-pixel losses (B, h s, w s).  Saved for the backward: the coarse
+    logits, the (mined) labels, lse and, for focal, coef per fine pixel.  Nothing is read back."""
 
     @staticmethod
-    def _params(logits2, labels, weight, lse, coef, dims, ignore_index, ld, focal, x):
-        p = _capi.UpsampleLossParams()
+    def _params(kind, logits2, labels, weight, lse, coef, dims, ignore_index, ld, x):
+        """(name, params) of `kind` ("plain", "options" or "focal"): sigma_<name>_fwd / _bwd take `params`"""
+        plain, focal = kind == "plain", kind == "focal"
+        p = _capi.UpsampleCeParams() if plain else _capi.UpsampleLossParams()
         p.batch, p.height, p.width, p.scale = dims
         p.classes, p.ld, p.ignore_index = logits2.shape[1], ld, int(ignore_index)
+        p.logits, p.labels, p.lse = logits2.data_ptr(), labels.data_ptr(), lse.data_ptr()
+        if plain:
+            return "upsample_ce", p
         p.kind = _capi.SIGMA_UPSAMPLE_LOSS_FOCAL if focal else _capi.SIGMA_UPSAMPLE_LOSS_OPTIONS
         p.label_smoothing, p.gamma = (0.0, float(x)) if focal else (float(x), 0.0)
-        p.logits, p.labels, p.lse = logits2.data_ptr(), labels.data_ptr(), lse.data_ptr()
         p.weight = weight.data_ptr() if weight is not None else None
         p.coef = coef.data_ptr() if coef is not None else None
-        return p
+        return "upsample_loss", p
 
     @staticmethod
     def forward(ctx, logits2, labels, weight, ignore_index, ld, dims, kind, x, reduction):
         dev = logits2.device
         f32 = dict(device=dev, dtype=torch.float32)
-        focal, coef = kind == "focal", None
+        coef = None
         if kind == "ohem":
             r = upsampled_ohem_stages(logits2, labels, weight, ignore_index, ld, dims, x[0], x[1], want_row_loss=reduction == "none")
-            labels, lse, partial, row_loss, x = r["mined"], r["lse"], r["partial"], r["row_loss"], 0.0
+            labels, lse, partial, row_loss, kind, x = r["mined"], r["lse"], r["partial"], r["row_loss"], "options", 0.0
         else:
             lse = torch.empty(labels.shape, **f32)
             partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, **f32)
-            coef = torch.empty(labels.shape, **f32) if focal else None
+            coef = torch.empty(labels.shape, **f32) if kind == "focal" else None
             row_loss = torch.empty(labels.shape, **f32) if reduction == "none" else None
-            p = UpsampledLossFn._params(logits2, labels, weight, lse, coef, dims, ignore_index, ld, focal, x)
-            p.partial, p.row_loss = partial.data_ptr(), row_loss.data_ptr() if row_loss is not None else None
-            launch("sigma_upsample_loss_fwd", ctypes.byref(p), device=dev, what=f"upsample_loss_fwd ({kind})")
+            name, p = UpsampledLossFn._params(kind, logits2, labels, weight, lse, coef, dims, ignore_index, ld, x)
+            p.partial = partial.data_ptr()
+            if row_loss is not None:
+                p.row_loss = row_loss.data_ptr()
+            launch(f"sigma_{name}_fwd", ctypes.byref(p), device=dev, what=f"{name}_fwd ({kind})")
         tot = partial.sum(0)
         ctx.save_for_backward(logits2, labels, lse, tot, weight, coef)
         ctx.ignore_index, ctx.ld, ctx.dims, ctx.reduction = int(ignore_index), ld, dims, reduction
-        ctx.focal, ctx.x = focal, float(x)
+        ctx.kind, ctx.x = kind, float(x)
         if reduction == "none":
             return row_loss.view(labels.shape)
         return tot[0] / tot[1] if reduction == "mean" else tot[0].clone()
@@ -522,7 +490,7 @@ class UpsampledLossFn(torch.autograd.Function):
         logits2, labels, lse, tot, weight, coef = ctx.saved_tensors
         rows, nc = logits2.shape
         ld = ctx.ld
-        p = UpsampledLossFn._params(logits2, labels, weight, lse, coef, ctx.dims, ctx.ignore_index, ld, ctx.focal, ctx.x)
+        name, p = UpsampledLossFn._params(ctx.kind, logits2, labels, weight, lse, coef, ctx.dims, ctx.ignore_index, ld, ctx.x)
         if ctx.reduction == "none":
             grad = g.float().contiguous().view(-1)
             p.row_grad = grad.data_ptr()
@@ -534,7 +502,7 @@ class UpsampledLossFn(torch.autograd.Function):
             p.scale_grad = grad.data_ptr()
         full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
         p.dlogits = full.data_ptr()
-        launch("sigma_upsample_loss_bwd", ctypes.byref(p), device=logits2.device, what="upsample_loss_bwd")
+        launch(f"sigma_{name}_bwd", ctypes.byref(p), device=logits2.device, what=f"{name}_bwd ({ctx.kind})")
         return (_hand_off_padded(full, nc),) + (None,) * 8
 
 

@@ -1,8 +1,11 @@
 """Deep supervision without a GPU: the fp64 twin against F.interpolate and against the reference's own output
 (tests/golden/model_tiny_64x96_ds.npz), the fp32 emulation of the kernels inside the bounds the GPU test uses, the wrong
-variants of the twin outside them, the product model's keys and size check, and the C ABI's struct and argument checks."""
+variants of the twin outside them, the product model's keys and size check, the C ABI's struct and argument checks, and
+the count of the kernels csrc/deepsup.hip compiles to."""
 import ctypes
 import os
+import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -213,6 +216,30 @@ def test_refused_sizes_and_direction_specific_pointers():
         p = _good_params()
         setattr(p, field, bad)
         assert fn(ctypes.byref(p), None) == 1
+
+
+def test_kernel_family_is_one_forward_and_one_backward_template(tmp_path):
+    """deepsup.hip compiles to ten kernels: upsample_loss_fwd_kernel and upsample_loss_bwd_kernel, each instantiated for
+    the plain criterion (without weights only) and for the option and focal criteria without and with class weights --
+    and no second pair of templates beside them.  None of the ten keeps anything in scratch memory."""
+    from sigma_amd import build
+    if not os.path.exists(build.HIPCC):
+        pytest.skip(f"no hipcc at {build.HIPCC}")
+    if shutil.which("c++filt") is None:
+        pytest.skip("no c++filt")
+    out = tmp_path / "deepsup.s"
+    flags = [f for f in build.FLAGS if f != "-fPIC"]
+    subprocess.check_call([build.HIPCC, *flags, "--offload-device-only", "-S", os.path.join(build.CSRC, "deepsup.hip"), "-o", str(out)],
+                          stderr=subprocess.DEVNULL)
+    kernels = re.findall(r"^\t\.amdhsa_kernel (\S+)\n(.*?)^\t\.end_amdhsa_kernel", out.read_text(), re.M | re.S)
+    assert len(kernels) == len({n for n, _ in kernels}) == 10 == 2 * (1 + 2 * 2)
+    names = subprocess.run(["c++filt"], input="\n".join(n for n, _ in kernels), capture_output=True, text=True).stdout.split("\n")
+    inst = sorted(m.groups() for n in names for m in [re.search(r"::(\w+)<\(.*?UpLoss\)(\d), (true|false)>\(", n)] if m)
+    kinds = [("0", "false"), ("1", "false"), ("1", "true"), ("2", "false"), ("2", "true")]       # kUpPlain, kUpOpt, kUpFocal
+    assert inst == [(t, k, hw) for t in ("upsample_loss_bwd_kernel", "upsample_loss_fwd_kernel") for k, hw in kinds]
+    for name, desc in kernels:
+        (size,) = re.findall(r"\.amdhsa_private_segment_fixed_size (\d+)", desc)
+        assert int(size) == 0 and ".amdhsa_uses_dynamic_stack 0" in desc, name
 
 
 def test_front_end_declines_cpu_tensors():

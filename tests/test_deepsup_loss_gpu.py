@@ -5,7 +5,7 @@ upsampled nll; determinism, no host synchronisation, memory; and the product mod
 
 Scale 1: the issue asks for the bits of the non-upsampled Functions where attainable.  They are not: the upsampled forward
 forms lse with the ONLINE maximum (chunk by chunk, rescaling the sum when the maximum rises: the loop of
-upsample_ce_fwd_kernel, which cannot hold an interpolated row of up to 64 classes in registers), the row kernels up to 64
+upsample_loss_fwd_kernel, which cannot hold an interpolated row of up to 64 classes in registers), the row kernels up to 64
 classes take the maximum of the whole row FIRST.  The rescale s *= exp(m - m') rounds, so lse differs in its last bits and
 everything after it does.  Scale 1 is therefore a case of the bounds like every other ((1, 4, 4, 1, 9, 12) in CASES), and
 ``test_scale_one_is_the_row_functions_up_to_the_bounds`` holds the two routes to the sum of their bounds."""

@@ -302,7 +302,7 @@ def deepsup_main(a, dev):
         fused_fn = upsampled_cross_entropy if kind == "plain" else upsampled_loss
         # the general route is the model's: the criterion's own route on the expanded logits (EncoderDecoder._loss)
         general_fn = (lambda crit, out, lab: crit(out, lab)) if kind in ("focal", "ohem") else cross_entropy
-        names = {"plain": ("UpsampledCEFn", "SoftmaxCEFn"), "weighted": ("UpsampledLossFn", "SoftmaxCEOptFn"),
+        names = {"plain": ("UpsampledLossFn", "SoftmaxCEFn"), "weighted": ("UpsampledLossFn", "SoftmaxCEOptFn"),
                  "smoothed": ("UpsampledLossFn", "SoftmaxCEOptFn"), "focal": ("UpsampledLossFn", "SoftmaxFocalFn"),
                  "ohem": ("UpsampledLossFn", "OhemCEFn")}[kind]
         total = {"fused": [0.0] * a.reps, "general": [0.0] * a.reps}
