@@ -30,6 +30,8 @@
  *
  * Conventions as sigma_scan.h: device pointers, fp32, the callee enqueues on `stream` (hipStream_t as void*) of
  * the current device, never allocates, never synchronises; returns 0 or a SIGMA_OPS_ERR_* code (sigma_ops.h).
+ * A non-zero status of a launch or of sigma_gemm_plan, and a sigma_gemm_workspace_bytes of -1, leave their reason in the
+ * library's thread-local error text: sigma_scan_last_error() (sigma_scan.h), on the same thread right after the call.
  */
 #ifndef SIGMA_GEMM_H_
 #define SIGMA_GEMM_H_

@@ -14,6 +14,11 @@
  * Same conventions as sigma_scan.h: device pointers, float32, contiguous tensors, the callee
  * enqueues on `stream` (hipStream_t as void*) of the current device, never allocates, never
  * synchronises; returns 0 or a SIGMA_OPS_ERR_* code.
+ *
+ * The reason of a refusal: every non-zero status, and every *_workspace_bytes query that answers -1,
+ * leaves its reason -- what was tested and the offending values, or the kernel and HIP's error for
+ * SIGMA_OPS_ERR_LAUNCH -- in the library's thread-local error text, read with sigma_scan_last_error()
+ * (sigma_scan.h) on the same thread right after the call.  A success does not touch the text.
  */
 #ifndef SIGMA_OPS_H_
 #define SIGMA_OPS_H_

@@ -22,7 +22,9 @@
  *
  * Return value: 0 on success, a SIGMA_ERR_* code otherwise; the host wrapper
  * turns non-zero into RuntimeError like TORCH_CHECK does in the reference.
- * sigma_scan_last_error() returns a thread-local human-readable message.
+ * sigma_scan_last_error() returns a thread-local human-readable message: the error
+ * text of the whole library, written by the entry points of sigma_ops.h and
+ * sigma_gemm.h as well.
  */
 #ifndef SIGMA_SCAN_H_
 #define SIGMA_SCAN_H_
@@ -201,7 +203,9 @@ int64_t sigma_scan_fwd_workspace_bytes(const sigma_scan_fwd_params *params);
  * negative = invalid params. */
 int64_t sigma_scan_bwd_workspace_bytes(const sigma_scan_bwd_params *params);
 
-/* Thread-local description of the last non-zero status returned on this thread. */
+/* Thread-local description of the last non-zero status (or negative size) returned on this thread by an
+ * entry point of ANY of the three headers -- sigma_scan.h, sigma_ops.h, sigma_gemm.h: the library has one
+ * error text.  A success leaves it as it was, so read it right after the call that failed. */
 const char *sigma_scan_last_error(void);
 
 /* ABI version of the loaded library (== SIGMA_SCAN_ABI_VERSION it was built with). */

@@ -347,10 +347,16 @@ def gemm_plan(p: GemmParams, form, lib=None) -> Optional[dict]:
 
 
 def last_error() -> str:
+    """The library's error text: the reason of the non-zero status (or negative size) that an entry point of any of the
+    three headers -- sigma_scan.h, sigma_ops.h, sigma_gemm.h -- just returned ON THIS THREAD.  Every refusal and every
+    failed launch writes it and no success does, so read it right after the call it belongs to: after a success it
+    still holds the text of an earlier failure."""
     return load().sigma_scan_last_error().decode("utf-8", "replace")
 
 
 def check(rc: int, what: str) -> None:
+    """raise ``RuntimeError("{what}: {last_error()} (sigma_status {rc})")`` for the non-zero status `rc` that an entry
+    point of any of the three headers just returned on this thread"""
     if rc != 0:
         raise RuntimeError(f"{what}: {last_error()} (sigma_status {rc})")
 

@@ -27,7 +27,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/sigma_ops.h"
+#include "ops_host.h"
 #include "loss_rows.h"
 #include "scan_device.h"
 
@@ -264,10 +264,6 @@ upsample_loss_bwd_kernel(const float* __restrict__ logits, const int64_t* __rest
     }
 }
 
-bool al(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-int done() { return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH; }
-
 // what sigma_upsample_ce_* hand to the shared check and launchers: no weight, row_loss, coef or row_grad
 sigma_upsample_loss_params up_plain(const sigma_upsample_ce_params& p) {
     sigma_upsample_loss_params q = {};
@@ -280,36 +276,46 @@ sigma_upsample_loss_params up_plain(const sigma_upsample_ce_params& p) {
 // everything all four entry points refuse on the geometry and the three pointers of both directions, before any launch;
 // *fine = the number of fine pixels
 int upsample_check(const sigma_upsample_loss_params& p, int64_t* fine) {
-    if (p.classes < 1 || p.classes > 64 || p.ld % 4 != 0 || p.ld < p.classes) return SIGMA_OPS_ERR_ARG;
-    if (p.scale < 1 || p.scale > 32 || p.batch <= 0 || p.height <= 0 || p.width <= 0) return SIGMA_OPS_ERR_ARG;
+    if (p.classes < 1 || p.classes > 64 || p.ld % 4 != 0 || p.ld < p.classes)
+        return fail(SIGMA_OPS_ERR_ARG, "classes %d must be in [1, 64] and ld %d a multiple of 4, at least classes", p.classes, p.ld);
+    if (p.scale < 1 || p.scale > 32 || p.batch <= 0 || p.height <= 0 || p.width <= 0)
+        return fail(SIGMA_OPS_ERR_ARG, "scale %d must be in [1, 32] and batch %d, height %d, width %d positive", p.scale, p.batch, p.height, p.width);
     // three factors below 2^31 and one below 2^6: the products of the first two pairs fit in 64 bits, the last is tested by division
     const int64_t coarse = (int64_t)p.batch * p.height;
-    if (coarse > 2147483647LL / p.width) return SIGMA_OPS_ERR_ARG;
+    if (coarse > 2147483647LL / p.width)
+        return fail(SIGMA_OPS_ERR_ARG, "batch %d x height %d x width %d coarse pixels exceed 2^31 - 1", p.batch, p.height, p.width);
     const int64_t ss = (int64_t)p.scale * p.scale;
-    if (coarse * p.width > 2147483647LL / ss) return SIGMA_OPS_ERR_ARG;
+    if (coarse * p.width > 2147483647LL / ss)
+        return fail(SIGMA_OPS_ERR_ARG, "batch %d x height %d x width %d x scale %d^2 fine pixels exceed 2^31 - 1", p.batch, p.height, p.width, p.scale);
     *fine = coarse * p.width * ss;
-    if (!p.logits || !p.labels || !p.lse || !al(p.logits, 16) || !al(p.labels, 8) || !al(p.lse, 4)) return SIGMA_OPS_ERR_ARG;
+    if (!p.logits || !p.labels || !p.lse || !aligned(p.logits, 16) || !aligned(p.labels, 8) || !aligned(p.lse, 4))
+        return fail(SIGMA_OPS_ERR_ARG, "logits, labels and lse must be non-NULL device pointers aligned to 16, 8 and 4 bytes");
     return SIGMA_OPS_OK;
 }
 
 // what sigma_upsample_loss_* refuse on top of that in both directions: what the option and focal row kernels refuse on eps
 // and gamma, the kind and the optional pointers
 int upsample_loss_check(const sigma_upsample_loss_params* p, int64_t* fine) {
-    if (!p) return SIGMA_OPS_ERR_ARG;
+    if (!p) return fail(SIGMA_OPS_ERR_ARG, "params is NULL");
     if (const int rc = upsample_check(*p, fine)) return rc;
-    if (p->kind != SIGMA_UPSAMPLE_LOSS_OPTIONS && p->kind != SIGMA_UPSAMPLE_LOSS_FOCAL) return SIGMA_OPS_ERR_ARG;
-    if (!(p->label_smoothing >= 0.0f && p->label_smoothing <= 1.0f)) return SIGMA_OPS_ERR_ARG;
+    if (p->kind != SIGMA_UPSAMPLE_LOSS_OPTIONS && p->kind != SIGMA_UPSAMPLE_LOSS_FOCAL)
+        return fail(SIGMA_OPS_ERR_ARG, "kind must be SIGMA_UPSAMPLE_LOSS_OPTIONS (0) or SIGMA_UPSAMPLE_LOSS_FOCAL (1) (got %d)", p->kind);
+    if (!(p->label_smoothing >= 0.0f && p->label_smoothing <= 1.0f))
+        return fail(SIGMA_OPS_ERR_ARG, "label_smoothing %g must be in [0, 1]", (double)p->label_smoothing);
     if (p->kind == SIGMA_UPSAMPLE_LOSS_FOCAL) {
-        if (p->label_smoothing != 0.0f || !(p->gamma == 0.0f || (p->gamma >= 1.0f && p->gamma < INFINITY))) return SIGMA_OPS_ERR_ARG;
-        if (!p->coef || !al(p->coef, 4)) return SIGMA_OPS_ERR_ARG;
+        if (p->label_smoothing != 0.0f || !(p->gamma == 0.0f || (p->gamma >= 1.0f && p->gamma < INFINITY)))
+            return fail(SIGMA_OPS_ERR_ARG, "the focal kind needs label_smoothing 0 (got %g) and gamma 0 or finite >= 1 (got %g)",
+                        (double)p->label_smoothing, (double)p->gamma);
+        if (!p->coef || !aligned(p->coef, 4)) return fail(SIGMA_OPS_ERR_ARG, "the focal kind needs coef, a non-NULL 4-byte aligned device pointer");
     }
-    if (!al(p->weight, 4)) return SIGMA_OPS_ERR_ARG;
+    if (!aligned(p->weight, 4)) return fail(SIGMA_OPS_ERR_ARG, "weight must be 4-byte aligned");
     return SIGMA_OPS_OK;
 }
 
 template <UpLoss KIND>
 int up_launch_fwd(const sigma_upsample_loss_params& p, int64_t fine, float x, void* stream) {
-    if (!p.partial || !al(p.partial, 4) || !al(p.row_loss, 4)) return SIGMA_OPS_ERR_ARG;
+    if (!p.partial || !aligned(p.partial, 4) || !aligned(p.row_loss, 4))
+        return fail(SIGMA_OPS_ERR_ARG, "partial must be non-NULL, partial and row_loss 4-byte aligned");
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(SIGMA_CE_BLOCKS), dim3(256), 0, static_cast<hipStream_t>(stream), p.logits, p.labels, p.weight,
                            (int)p.height, (int)p.width, (int)p.scale, (int)p.classes, (int)p.ld, (long)p.ignore_index, (unsigned)fine, x,
@@ -317,13 +323,15 @@ int up_launch_fwd(const sigma_upsample_loss_params& p, int64_t fine, float x, vo
     };
     if (KIND != kUpPlain && p.weight) launch(upsample_loss_fwd_kernel<KIND, KIND != kUpPlain>);
     else launch(upsample_loss_fwd_kernel<KIND, false>);
-    return done();
+    return launched("upsample_loss_fwd_kernel");
 }
 
 template <UpLoss KIND>
 int up_launch_bwd(const sigma_upsample_loss_params& p, float x, void* stream) {
-    if ((p.scale_grad != nullptr) == (p.row_grad != nullptr)) return SIGMA_OPS_ERR_ARG;
-    if (!p.dlogits || !al(p.scale_grad, 4) || !al(p.row_grad, 4) || !al(p.dlogits, 16)) return SIGMA_OPS_ERR_ARG;
+    if ((p.scale_grad != nullptr) == (p.row_grad != nullptr))
+        return fail(SIGMA_OPS_ERR_ARG, "exactly one of scale_grad (%p) and row_grad (%p) must be given", (const void*)p.scale_grad, (const void*)p.row_grad);
+    if (!p.dlogits || !aligned(p.scale_grad, 4) || !aligned(p.row_grad, 4) || !aligned(p.dlogits, 16))
+        return fail(SIGMA_OPS_ERR_ARG, "dlogits must be non-NULL and 16-byte aligned, scale_grad and row_grad 4-byte aligned");
     const long items = (long)p.batch * p.height * p.width * (p.ld / 4);
     // lanes per item: as many as fill the device (2^19 resident threads), never more than the 2 s rows of a footprint.  A
     // function of the shape alone, so the order of the sums is too.
@@ -338,7 +346,7 @@ int up_launch_bwd(const sigma_upsample_loss_params& p, float x, void* stream) {
     };
     if (KIND != kUpPlain && p.weight) launch(upsample_loss_bwd_kernel<KIND, KIND != kUpPlain>);
     else launch(upsample_loss_bwd_kernel<KIND, false>);
-    return done();
+    return launched("upsample_loss_bwd_kernel");
 }
 
 }  // namespace
@@ -361,7 +369,7 @@ int sigma_upsample_loss_bwd(const sigma_upsample_loss_params* p, void* stream) {
 }
 
 int sigma_upsample_ce_fwd(const sigma_upsample_ce_params* p, void* stream) {
-    if (!p) return SIGMA_OPS_ERR_ARG;
+    if (!p) return sigma::fail(SIGMA_OPS_ERR_ARG, "params is NULL");
     const sigma_upsample_loss_params q = sigma::up_plain(*p);
     int64_t fine = 0;
     if (const int rc = sigma::upsample_check(q, &fine)) return rc;
@@ -369,7 +377,7 @@ int sigma_upsample_ce_fwd(const sigma_upsample_ce_params* p, void* stream) {
 }
 
 int sigma_upsample_ce_bwd(const sigma_upsample_ce_params* p, void* stream) {
-    if (!p) return SIGMA_OPS_ERR_ARG;
+    if (!p) return sigma::fail(SIGMA_OPS_ERR_ARG, "params is NULL");
     const sigma_upsample_loss_params q = sigma::up_plain(*p);
     int64_t fine = 0;
     if (const int rc = sigma::upsample_check(q, &fine)) return rc;

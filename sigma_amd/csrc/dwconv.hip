@@ -28,7 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/sigma_ops.h"
+#include "ops_host.h"
 #include "scan_device.h"
 
 namespace sigma {
@@ -574,12 +574,14 @@ size_t plane_compact_lds_bytes(const sigma_dwconv_params* p) {
 }
 
 int check(const sigma_dwconv_params* p) {
-    if (!p) return SIGMA_OPS_ERR_ARG;
-    if (p->flags & ~SIGMA_DWCONV_DETERMINISTIC) return SIGMA_OPS_ERR_ARG;
-    if (p->batch < 0 || p->channels <= 0 || p->height <= 0 || p->width <= 0) return SIGMA_OPS_ERR_ARG;
-    if (p->n_orders != 1 && p->n_orders != 2) return SIGMA_OPS_ERR_ARG;
+    if (!p) return fail(SIGMA_OPS_ERR_ARG, "params is NULL");
+    if (p->flags & ~SIGMA_DWCONV_DETERMINISTIC) return fail(SIGMA_OPS_ERR_ARG, "unknown bits in flags (0x%x)", (unsigned)p->flags);
+    if (p->batch < 0 || p->channels <= 0 || p->height <= 0 || p->width <= 0)
+        return fail(SIGMA_OPS_ERR_ARG, "bad sizes batch=%d channels=%d height=%d width=%d", p->batch, p->channels, p->height, p->width);
+    if (p->n_orders != 1 && p->n_orders != 2) return fail(SIGMA_OPS_ERR_ARG, "n_orders must be 1 or 2 (got %d)", p->n_orders);
     const long tiles = (long)((p->width + kTile - 1) / kTile) * ((p->height + kTile - 1) / kTile);
-    if ((long)p->batch * p->channels * tiles > 2147483647L) return SIGMA_OPS_ERR_ARG;
+    if ((long)p->batch * p->channels * tiles > 2147483647L)
+        return fail(SIGMA_OPS_ERR_ARG, "batch %d x channels %d x %ld tiles exceed the grid limit of 2^31 - 1", p->batch, p->channels, tiles);
     return SIGMA_OPS_OK;
 }
 
@@ -644,20 +646,20 @@ long det_slots_used(const sigma_dwconv_params* p) {
     return (long)s.rows * s.nblk * p->batch;
 }
 
-bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
-
 }  // namespace
 
 }  // namespace sigma
 
 namespace sigma {
 // plane strides of x / dx: 0 / 0 = packed (B, d, H, W); otherwise both given, planes contiguous and non-overlapping
-bool plane_strides(const sigma_dwconv_params* p, DwArgs& a) {
+int plane_strides(const sigma_dwconv_params* p, DwArgs& a) {
     const long L = (long)p->height * p->width;
-    if (p->x_batch_stride == 0 && p->x_channel_stride == 0) { a.x_bs = (long)p->channels * L; a.x_cs = L; return true; }
-    if (p->x_batch_stride < L || p->x_channel_stride < L) return false;
+    if (p->x_batch_stride == 0 && p->x_channel_stride == 0) { a.x_bs = (long)p->channels * L; a.x_cs = L; return SIGMA_OPS_OK; }
+    if (p->x_batch_stride < L || p->x_channel_stride < L)
+        return fail(SIGMA_OPS_ERR_ARG, "x_batch_stride %lld and x_channel_stride %lld must both be 0 or at least one plane (%ld)",
+                    (long long)p->x_batch_stride, (long long)p->x_channel_stride, L);
     a.x_bs = p->x_batch_stride; a.x_cs = p->x_channel_stride;
-    return true;
+    return SIGMA_OPS_OK;
 }
 }  // namespace sigma
 
@@ -667,17 +669,17 @@ int sigma_dwconv3x3_silu_fwd(const sigma_dwconv_params* p, void* stream) {
     int rc = sigma::check(p);
     if (rc) return rc;
     if (p->batch == 0) return SIGMA_OPS_OK;
-    if (!p->x || !p->weight || !p->out2) return SIGMA_OPS_ERR_ARG;
+    if (!p->x || !p->weight || !p->out2) return sigma::fail(SIGMA_OPS_ERR_ARG, "x, weight and out2 must be non-NULL device pointers");
     sigma::DwArgs a{};
     a.x = p->x; a.w = p->weight; a.bias = p->bias; a.out2 = p->out2;
     a.B = p->batch; a.d = p->channels; a.H = p->height; a.W = p->width; a.orders = p->n_orders;
-    if (!sigma::plane_strides(p, a)) return SIGMA_OPS_ERR_ARG;
+    if ((rc = sigma::plane_strides(p, a))) return rc;
     sigma::set_strips(p, a);
     // 16-byte accesses: every row of every plane starts on a 16-byte boundary (W % 4 == 0 makes L % 4 == 0)
-    a.vec = (p->width & 3) == 0 && (a.x_bs & 3) == 0 && (a.x_cs & 3) == 0 && sigma::aligned16(p->x) && sigma::aligned16(p->out2);
+    a.vec = (p->width & 3) == 0 && (a.x_bs & 3) == 0 && (a.x_cs & 3) == 0 && sigma::aligned(p->x, 16) && sigma::aligned(p->out2, 16);
     hipLaunchKernelGGL(sigma::dwconv_silu_fwd_kernel, sigma::grid_for(p), dim3(sigma::strip_threads(p)), sigma::strip_lds_bytes(p, true, false),
                        static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    return sigma::launched("dwconv_silu_fwd_kernel");
 }
 
 int64_t sigma_dwconv3x3_silu_bwd_workspace_bytes(const sigma_dwconv_params* p) {
@@ -692,26 +694,29 @@ int sigma_dwconv3x3_silu_bwd(const sigma_dwconv_params* p, void* stream) {
     if (p->batch == 0) {
         // deterministic mode: dweight / dbias are written -- with no batch, as zeros
         if (!(p->flags & SIGMA_DWCONV_DETERMINISTIC)) return SIGMA_OPS_OK;
-        if (!p->dweight) return SIGMA_OPS_ERR_ARG;
+        if (!p->dweight) return sigma::fail(SIGMA_OPS_ERR_ARG, "dweight is NULL (deterministic mode writes it for an empty batch too)");
         hipStream_t s = static_cast<hipStream_t>(stream);
         hipError_t e = hipMemsetAsync(p->dweight, 0, (size_t)p->channels * 9 * sizeof(float), s);
         if (e == hipSuccess && p->dbias) e = hipMemsetAsync(p->dbias, 0, (size_t)p->channels * sizeof(float), s);
-        return e == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+        return sigma::launched("hipMemsetAsync of dweight / dbias", e);
     }
-    if (!p->x || !p->weight || !p->g2 || !p->gpre || !p->dweight || !p->dx) return SIGMA_OPS_ERR_ARG;
+    if (!p->x || !p->weight || !p->g2 || !p->gpre || !p->dweight || !p->dx)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "x, weight, g2, gpre, dweight and dx must be non-NULL device pointers");
     const bool det = (p->flags & SIGMA_DWCONV_DETERMINISTIC) != 0;
     const int64_t need = sigma_dwconv3x3_silu_bwd_workspace_bytes(p);
-    if (det && (!p->workspace || p->workspace_bytes < need || (reinterpret_cast<uintptr_t>(p->workspace) & 15u))) return SIGMA_OPS_ERR_ARG;
+    if (det && (!p->workspace || p->workspace_bytes < need || !sigma::aligned(p->workspace, 16)))
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "deterministic mode needs a 16-byte aligned workspace of %lld bytes (got %p, %lld bytes)",
+                           (long long)need, p->workspace, (long long)p->workspace_bytes);
     sigma::DwArgs a{};
     a.x = p->x; a.w = p->weight; a.bias = p->bias; a.g2 = p->g2; a.gpre = p->gpre;
     a.dw = p->dweight; a.dbias = p->dbias; a.dx = p->dx;
     a.B = p->batch; a.d = p->channels; a.H = p->height; a.W = p->width; a.orders = p->n_orders;
     a.part = det ? static_cast<float*>(p->workspace) : nullptr;
-    if (!sigma::plane_strides(p, a)) return SIGMA_OPS_ERR_ARG;
+    if ((rc = sigma::plane_strides(p, a))) return rc;
     sigma::set_strips(p, a);
     const bool plane = sigma::plane_below_line(p);
-    a.vec = (p->width & 3) == 0 && (a.x_bs & 3) == 0 && (a.x_cs & 3) == 0 && sigma::aligned16(p->x) && sigma::aligned16(p->dx) &&
-            sigma::aligned16(p->g2) && (plane || sigma::aligned16(p->gpre));
+    a.vec = (p->width & 3) == 0 && (a.x_bs & 3) == 0 && (a.x_cs & 3) == 0 && sigma::aligned(p->x, 16) && sigma::aligned(p->dx, 16) &&
+            sigma::aligned(p->g2, 16) && (plane || sigma::aligned(p->gpre, 16));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (plane) {                                             // one launch, gpre stays in LDS (p->gpre is not written)
         size_t lds = sigma::plane_rect_lds_bytes(p);
@@ -720,18 +725,18 @@ int sigma_dwconv3x3_silu_bwd(const sigma_dwconv_params* p, void* stream) {
         hipLaunchKernelGGL(det ? sigma::dwconv_silu_bwd_plane_det_kernel : sigma::dwconv_silu_bwd_plane_kernel,
                            dim3((unsigned)(p->batch * p->channels)),
                            dim3(a.compact ? 256u : sigma::threads_for((long)p->height * ((p->width + 3) / 4))), lds, s, a);
-        if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+        if ((rc = sigma::launched(det ? "dwconv_silu_bwd_plane_det_kernel" : "dwconv_silu_bwd_plane_kernel"))) return rc;
     } else {
         hipLaunchKernelGGL(det ? sigma::dwconv_silu_bwd1_det_kernel : sigma::dwconv_silu_bwd1_kernel, sigma::grid_for(p),
                            dim3(sigma::strip_threads(p)), sigma::strip_lds_bytes(p, true, true), s, a);
-        if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+        if ((rc = sigma::launched(det ? "dwconv_silu_bwd1_det_kernel" : "dwconv_silu_bwd1_kernel"))) return rc;
         hipLaunchKernelGGL(sigma::dwconv_bwd2_kernel, sigma::grid_for(p), dim3(sigma::strip_threads(p)), sigma::strip_lds_bytes(p, false, false), s, a);
-        if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+        if ((rc = sigma::launched("dwconv_bwd2_kernel"))) return rc;
     }
     if (det) {
         const int blocks = (p->channels * 10 + 255) / 256;
         hipLaunchKernelGGL(sigma::dwconv_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, (int)sigma::det_slots_used(p));
-        if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+        if ((rc = sigma::launched("dwconv_reduce_kernel"))) return rc;
     }
     return SIGMA_OPS_OK;
 }

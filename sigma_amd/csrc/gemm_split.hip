@@ -26,7 +26,7 @@
 #include <atomic>
 
 #include "../../include/sigma_gemm.h"
-#include "../../include/sigma_ops.h"
+#include "ops_host.h"
 #include "scan_device.h"
 
 namespace sigma {
@@ -720,13 +720,18 @@ struct GemmPlan {
 };
 
 int fill_common(const sigma_gemm_params* p, GemmArgs& g) {
-    if (!p || !p->A || !p->Bt || !p->C) return SIGMA_OPS_ERR_ARG;
-    if (p->M < 0 || p->N < 0 || p->K < 0 || p->batch < 0) return SIGMA_OPS_ERR_ARG;
-    if (p->pieces != 0 && p->pieces != 2 && p->pieces != 3) return SIGMA_OPS_ERR_ARG;
-    if (!aligned16(p->A) || !aligned16(p->Bt) || p->lda % 4 != 0 || p->ldb % 4 != 0) return SIGMA_OPS_ERR_ARG;
+    if (!p) return fail(SIGMA_OPS_ERR_ARG, "params is NULL");
+    if (!p->A || !p->Bt || !p->C) return fail(SIGMA_OPS_ERR_ARG, "A, Bt and C must be non-NULL device pointers");
+    if (p->M < 0 || p->N < 0 || p->K < 0 || p->batch < 0)
+        return fail(SIGMA_OPS_ERR_ARG, "bad sizes M=%lld N=%d K=%d batch=%d", (long long)p->M, p->N, p->K, p->batch);
+    if (p->pieces != 0 && p->pieces != 2 && p->pieces != 3) return fail(SIGMA_OPS_ERR_ARG, "pieces must be 0, 2 or 3 (got %d)", p->pieces);
+    if (!aligned16(p->A) || !aligned16(p->Bt) || p->lda % 4 != 0 || p->ldb % 4 != 0)
+        return fail(SIGMA_OPS_ERR_ARG, "A and Bt must be 16-byte aligned, lda %lld and ldb %lld multiples of 4", (long long)p->lda, (long long)p->ldb);
     // a tile is addressed with 32-bit byte offsets from a wave-uniform base: 127 rows x ld x 4 bytes must fit
-    if (p->lda <= 0 || p->ldb <= 0 || p->lda > (1L << 22) || p->ldb > (1L << 22)) return SIGMA_OPS_ERR_ARG;
-    if (p->batch > 1 && (p->strideA % 4 != 0 || p->strideB % 4 != 0)) return SIGMA_OPS_ERR_ARG;
+    if (p->lda <= 0 || p->ldb <= 0 || p->lda > (1L << 22) || p->ldb > (1L << 22))
+        return fail(SIGMA_OPS_ERR_ARG, "lda %lld and ldb %lld must be in (0, 2^22]", (long long)p->lda, (long long)p->ldb);
+    if (p->batch > 1 && (p->strideA % 4 != 0 || p->strideB % 4 != 0))
+        return fail(SIGMA_OPS_ERR_ARG, "strideA %lld and strideB %lld must be multiples of 4", (long long)p->strideA, (long long)p->strideB);
     g.A = p->A; g.B = p->Bt; g.C = p->C; g.bias = p->bias;
     g.lda = p->lda; g.ldb = p->ldb; g.ldc = p->ldc;
     // a single problem never steps by strideC: ignored there, so that a stale value cannot unalign the row epilogue
@@ -735,10 +740,12 @@ int fill_common(const sigma_gemm_params* p, GemmArgs& g) {
     g.slices = 1;       // (a_mod, c_mod, the transposed column range and the two-stage fields stay 0: plan_gemm zero-fills)
     g.mode = p->accumulate ? 1 : 0;
     g.R = p->residual; g.R2 = p->residual ? p->residual2 : nullptr; g.ldr = p->ldr; g.sR = p->strideR;
-    if (p->workspace_bytes < 0 || (p->workspace_bytes > 0 && !p->workspace)) return SIGMA_OPS_ERR_ARG;
-    if (!p->residual && p->residual2) return SIGMA_OPS_ERR_ARG;
-    if (p->residual && (p->ldr <= 0 || p->M * p->ldr >= 0x7fffffffL)) return SIGMA_OPS_ERR_ARG;
-    if (p->c_mod < 0 || p->reserved != 0) return SIGMA_OPS_ERR_ARG;
+    if (p->workspace_bytes < 0 || (p->workspace_bytes > 0 && !p->workspace))
+        return fail(SIGMA_OPS_ERR_ARG, "workspace_bytes %lld must not be negative, nor positive with a NULL workspace", (long long)p->workspace_bytes);
+    if (!p->residual && p->residual2) return fail(SIGMA_OPS_ERR_ARG, "residual2 needs residual");
+    if (p->residual && (p->ldr <= 0 || p->M * p->ldr >= 0x7fffffffL))
+        return fail(SIGMA_OPS_ERR_ARG, "ldr %lld must be positive and M x ldr below 2^31 - 1 (M=%lld)", (long long)p->ldr, (long long)p->M);
+    if (p->c_mod < 0 || p->reserved != 0) return fail(SIGMA_OPS_ERR_ARG, "c_mod %d must not be negative and reserved %d be 0", p->c_mod, p->reserved);
     return SIGMA_OPS_OK;
 }
 
@@ -755,7 +762,7 @@ void set_dims(GemmPlan& pl, long M, int N, int K) {
 // shared outputs (nt / nn): several problems per output are summed
 int share_outputs(const sigma_gemm_params* p, GemmPlan& pl) {
     if (p->c_mod > 0 && pl.g.batch > p->c_mod) {
-        if (p->residual || p->bias) return SIGMA_OPS_ERR_ARG;
+        if (p->residual || p->bias) return fail(SIGMA_OPS_ERR_ARG, "problems sharing an output (batch %d > c_mod %d) take no residual and no bias", pl.g.batch, p->c_mod);
         pl.g.c_mod = p->c_mod; pl.summed = true;
     }   // batch <= c_mod: problem z owns output z (z % c_mod == z), i.e. the same as c_mod = 0 -- kept at 0 here, so that
         // the scratch of k_slices is sized and reduced for the `batch` outputs that exist, not for c_mod of them
@@ -783,10 +790,10 @@ void slice_reduction(GemmPlan& pl) {
 int plan_nt(const sigma_gemm_params* p, GemmPlan& pl) {
     GemmArgs& g = pl.g;
     if (const int rc = fill_common(p, g)) return rc;
-    if (p->K % 4 != 0) return SIGMA_OPS_ERR_ARG;
+    if (p->K % 4 != 0) return fail(SIGMA_OPS_ERR_ARG, "K %d must be a multiple of 4", p->K);
     pl.empty = p->M == 0 || p->N == 0;
     if (pl.empty) return SIGMA_OPS_OK;
-    if (p->K == 0) return SIGMA_OPS_ERR_ARG;
+    if (p->K == 0) return fail(SIGMA_OPS_ERR_ARG, "K is 0 with a non-empty output");
     set_dims(pl, p->M, p->N, p->K);
     g.a_mod = p->a_mod;
     if (const int rc = share_outputs(p, pl)) return rc;
@@ -794,7 +801,9 @@ int plan_nt(const sigma_gemm_params* p, GemmPlan& pl) {
         if (p->t_cols < 0 || p->t_cols > p->N || p->t_cols % 32 != 0 || !p->Ct || !aligned16(p->Ct) || p->ldct % 4 != 0 ||
             p->ldct < p->M || p->M % 4 != 0 || p->N % 4 != 0 || p->ldc % 4 != 0 || !aligned16(p->C) || g.batch != 1 ||
             p->accumulate || p->residual || pl.summed)
-            return SIGMA_OPS_ERR_ARG;
+            return fail(SIGMA_OPS_ERR_ARG, "t_cols %d must be a multiple of 32 in [0, N], Ct non-NULL, Ct and C 16-byte aligned, ldct %lld a multiple of 4 and at "
+                        "least M, and M, N, ldc multiples of 4, in a single problem without accumulate, residual or shared outputs",
+                        p->t_cols, (long long)p->ldct);
         g.Ct = p->Ct; g.ldct = p->ldct; g.t_cols = p->t_cols;
     }
     return SIGMA_OPS_OK;
@@ -804,10 +813,10 @@ int plan_nn(const sigma_gemm_params* p, GemmPlan& pl) {
     // C = A B with B = (K, N) row-major (params->Bt, row stride ldb): the B operand's reduction index is its slow index
     GemmArgs& g = pl.g;
     if (const int rc = fill_common(p, g)) return rc;
-    if (p->K % 4 != 0 || p->N % 4 != 0) return SIGMA_OPS_ERR_ARG;
+    if (p->K % 4 != 0 || p->N % 4 != 0) return fail(SIGMA_OPS_ERR_ARG, "K %d and N %d must be multiples of 4", p->K, p->N);
     pl.empty = p->M == 0 || p->N == 0;
     if (pl.empty) return SIGMA_OPS_OK;
-    if (p->K == 0) return SIGMA_OPS_ERR_ARG;
+    if (p->K == 0) return fail(SIGMA_OPS_ERR_ARG, "K is 0 with a non-empty output");
     set_dims(pl, p->M, p->N, p->K);
     g.a_mod = p->a_mod;
     if (const int rc = share_outputs(p, pl)) return rc;
@@ -819,12 +828,12 @@ int plan_tn(const sigma_gemm_params* p, GemmPlan& pl) {
     // C (N_out x K_in) (+)= A^T B with A = (M, N_out), Bt = (M, K_in): both operands have the reduction (token) index
     // as the slow memory index.  Kernel view: rows of C = N_out, columns = K_in, reduction = M.
     if (const int rc = fill_common(p, pl.g)) return rc;
-    if (p->N % 4 != 0 || p->K % 4 != 0) return SIGMA_OPS_ERR_ARG;
+    if (p->N % 4 != 0 || p->K % 4 != 0) return fail(SIGMA_OPS_ERR_ARG, "N %d and K %d must be multiples of 4", p->N, p->K);
     // nt / nn only; a weight gradient has no bias either (sigma_gemm.h: the tn formula has none)
-    if (p->c_mod != 0 || p->residual || p->bias) return SIGMA_OPS_ERR_ARG;
+    if (p->c_mod != 0 || p->residual || p->bias) return fail(SIGMA_OPS_ERR_ARG, "the tn form takes no c_mod (got %d), residual or bias", p->c_mod);
     pl.empty = p->N == 0 || p->K == 0 || p->M == 0;
     if (pl.empty) return SIGMA_OPS_OK;
-    if (p->M > 0x7fffff00L) return SIGMA_OPS_ERR_ARG;
+    if (p->M > 0x7fffff00L) return fail(SIGMA_OPS_ERR_ARG, "M %lld exceeds the tn form's reduction limit of 2^31 - 256", (long long)p->M);
     set_dims(pl, p->N, p->K, (int)p->M);
     slice_reduction(pl);
     return SIGMA_OPS_OK;
@@ -839,9 +848,11 @@ int plan_launch(const sigma_gemm_params* p, GemmPlan& pl) {
     GemmArgs& g = pl.g;
     pl.pieces = p->pieces == 3 ? 3 : 2;
     pl.res = g.R != nullptr;
-    if (pl.res && (pl.pieces != 2 || pl.form == 2)) return SIGMA_OPS_ERR_ARG;         // no such kernel (kernel_rows)
+    if (pl.res && (pl.pieces != 2 || pl.form == 2))                                   // no such kernel (kernel_rows)
+        return fail(SIGMA_OPS_ERR_ARG, "residual needs pieces 2 (got %d) and the nt or nn form", pl.pieces);
     pl.items = (long)g.batch * g.ntm * g.ntn * g.slices;
-    if (pl.items <= 0 || pl.items > 0x7fffffffL) return SIGMA_OPS_ERR_ARG;           // the kernel counts them in an int
+    if (pl.items <= 0 || pl.items > 0x7fffffffL)                                     // the kernel counts them in an int
+        return fail(SIGMA_OPS_ERR_ARG, "%ld work items (problems x tiles x slices) must be in [1, 2^31 - 1]", pl.items);
     if (pl.summed) {
         // problem groups of a shared-output launch, ceil(batch / c_mod): with batch % c_mod != 0 the last group is short and
         // the outputs z % c_mod >= batch % c_mod have one group (g.slices parts) less, whose slots in the scratch stay unwritten
@@ -879,7 +890,8 @@ int plan_launch(const sigma_gemm_params* p, GemmPlan& pl) {
 GemmPlan plan_gemm(const sigma_gemm_params* p, int form) {
     GemmPlan pl{};
     pl.form = form;
-    pl.status = form == 0 ? plan_nt(p, pl) : form == 1 ? plan_nn(p, pl) : form == 2 ? plan_tn(p, pl) : SIGMA_OPS_ERR_ARG;
+    pl.status = form == 0 ? plan_nt(p, pl) : form == 1 ? plan_nn(p, pl) : form == 2 ? plan_tn(p, pl)
+              : fail(SIGMA_OPS_ERR_ARG, "form %d must be 0 (nt), 1 (nn) or 2 (tn)", form);
     if (pl.status == SIGMA_OPS_OK && !pl.empty) pl.status = plan_launch(p, pl);
     return pl;
 }
@@ -889,7 +901,8 @@ int launch(const GemmPlan& pl, void* stream) {
     KernelRow* row = nullptr;
     for (KernelRow& r : kernel_rows)
         if (r.form == pl.form && r.pieces == pl.pieces && r.res == pl.res && r.bn == pl.bn) { row = &r; break; }
-    if (row == nullptr) return SIGMA_OPS_ERR_LAUNCH;      // (the plan refuses what has no row)
+    if (row == nullptr)                                   // (the plan refuses what has no row)
+        return fail(SIGMA_OPS_ERR_LAUNCH, "no kernel is built for form %d, pieces %d, residual %d, tile width %d", pl.form, pl.pieces, (int)pl.res, pl.bn);
     hipStream_t s = static_cast<hipStream_t>(stream);
     // persistent workgroups: as many as are resident at once (register-limited: 2 per CU at 128 x 128, 3-4 for the
     // narrower tiles); a multiple of the 8 XCDs so that the XCD remap of the item ids keeps its meaning
@@ -903,14 +916,14 @@ int launch(const GemmPlan& pl, void* stream) {
     long grid = 256L * per_cu;
     if (grid > pl.items) grid = pl.items;
     hipLaunchKernelGGL(row->kernel, dim3((unsigned)grid), dim3(256), 0, s, pl.g);
-    if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+    if (const int rc = launched("gemm_split3_kernel")) return rc;
     if (pl.two_stage) {
         const GemmArgs& g = pl.g;
         const auto& r = pl.sum;
         const auto reduce = r.vec ? reduce_parts_kernel<true> : reduce_parts_kernel<false>;
         hipLaunchKernelGGL(reduce, dim3((unsigned)r.blocks, (unsigned)r.outs), dim3(64, r.part_groups), 0, s, (const float*)g.C, r.C, g.M, g.N,
                            r.ldc, r.sC, g.nparts, r.full_outs, r.nparts_short, g.part_stride, r.add);
-        if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+        if (const int rc = launched("reduce_parts_kernel")) return rc;
     }
     return SIGMA_OPS_OK;
 }
@@ -928,7 +941,7 @@ extern "C" int64_t sigma_gemm_workspace_bytes(const sigma_gemm_params* p, int fo
 }
 
 extern "C" int sigma_gemm_plan(const sigma_gemm_params* p, int form, int32_t out[8]) {
-    if (!out) return SIGMA_OPS_ERR_ARG;
+    if (!out) return sigma::fail(SIGMA_OPS_ERR_ARG, "out is NULL");
     for (int i = 0; i < 8; ++i) out[i] = 0;
     const sigma::GemmPlan pl = sigma::plan_gemm(p, form);
     if (pl.status != SIGMA_OPS_OK || pl.empty) return pl.status;

@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/sigma_ops.h"
+#include "ops_host.h"
 #include "scan_device.h"
 
 namespace sigma {
@@ -350,8 +350,12 @@ int bwd_grid(long rows, int C) {
     return grid_blocks(rows, cap);
 }
 
-bool check(const sigma_layernorm_params* p) {
-    return p && p->rows >= 0 && p->channels > 0 && p->channels % 4 == 0 && p->channels <= 2048;
+int check(const sigma_layernorm_params* p) {
+    if (!p) return fail(SIGMA_OPS_ERR_ARG, "params is NULL");
+    if (p->rows < 0) return fail(SIGMA_OPS_ERR_ARG, "rows %lld must not be negative", (long long)p->rows);
+    if (p->channels <= 0 || p->channels % 4 != 0 || p->channels > 2048)
+        return fail(SIGMA_OPS_ERR_ARG, "channels %d must be a multiple of 4 in (0, 2048]", p->channels);
+    return SIGMA_OPS_OK;
 }
 
 }  // namespace
@@ -365,54 +369,60 @@ int sigma_layernorm_bwd_partial_rows(int64_t rows, int32_t channels) {
 }
 
 int sigma_layernorm_fwd(const sigma_layernorm_params* p, void* stream) {
-    if (!sigma::check(p)) return SIGMA_OPS_ERR_ARG;
+    if (const int rc = sigma::check(p)) return rc;
     if (p->rows == 0) return SIGMA_OPS_OK;
-    if (!p->x || !p->gamma || !p->y) return SIGMA_OPS_ERR_ARG;
+    if (!p->x || !p->gamma || !p->y) return sigma::fail(SIGMA_OPS_ERR_ARG, "x, gamma and y must be non-NULL device pointers");
     sigma::LnArgs a{};
     a.x = p->x; a.gamma = p->gamma; a.beta = p->beta; a.y = p->y; a.mean = p->mean; a.rstd = p->rstd;
     a.z = p->gate; a.z_stride = p->gate_row_stride;
-    if (p->gate && (p->gate_row_stride % 4 != 0 || p->gate_row_stride < p->channels)) return SIGMA_OPS_ERR_ARG;
+    if (p->gate && (p->gate_row_stride % 4 != 0 || p->gate_row_stride < p->channels))
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "gate_row_stride %lld must be a multiple of 4 and at least channels (%d)",
+                           (long long)p->gate_row_stride, p->channels);
     a.rsc = p->row_scale; a.rows_per_scale = p->rows_per_scale;
-    if (p->row_scale && p->rows_per_scale <= 0) return SIGMA_OPS_ERR_ARG;
+    if (p->row_scale && p->rows_per_scale <= 0)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "rows_per_scale %lld must be positive with row_scale", (long long)p->rows_per_scale);
     a.M = p->rows; a.C = p->channels; a.eps = p->eps;
     const int grid = sigma::fwd_grid(p->rows, p->channels);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool ok = sigma::dispatch_nv(p->channels, [&](auto nv) {
         hipLaunchKernelGGL(sigma::ln_fwd_kernel<decltype(nv)::value>, dim3(grid), dim3(256), 0, s, a);
     });
-    if (!ok) return SIGMA_OPS_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    if (!ok) return sigma::fail(SIGMA_OPS_ERR_ARG, "no kernel is built for channels %d", p->channels);
+    return sigma::launched("ln_fwd_kernel");
 }
 
 int sigma_layernorm_bwd(const sigma_layernorm_params* p, void* stream) {
-    if (!sigma::check(p)) return SIGMA_OPS_ERR_ARG;
-    if (!p->dgamma) return SIGMA_OPS_ERR_ARG;
+    if (const int rc = sigma::check(p)) return rc;
+    if (!p->dgamma) return sigma::fail(SIGMA_OPS_ERR_ARG, "dgamma is NULL");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int grid = sigma::bwd_grid(p->rows, p->channels);
     if (p->rows > 0) {
-        if (!p->x || !p->gamma || !p->dy || !p->mean || !p->rstd || !p->dx || !p->workspace) return SIGMA_OPS_ERR_ARG;
+        if (!p->x || !p->gamma || !p->dy || !p->mean || !p->rstd || !p->dx || !p->workspace)
+            return sigma::fail(SIGMA_OPS_ERR_ARG, "x, gamma, dy, mean, rstd, dx and workspace must be non-NULL device pointers");
         sigma::LnArgs a{};
         a.x = p->x; a.gamma = p->gamma; a.beta = p->beta; a.dy = p->dy; a.mean = p->mean; a.rstd = p->rstd; a.dx = p->dx;
         a.ws = p->workspace; a.z = p->gate; a.z_stride = p->gate_row_stride; a.dz = p->dgate;
         a.dz_stride = p->dgate_row_stride > 0 ? p->dgate_row_stride : p->channels;
         a.rsc = p->row_scale; a.rows_per_scale = p->rows_per_scale;
         a.dx_add = p->dx_add;
-        if (p->dx_add && (reinterpret_cast<uintptr_t>(p->dx_add) & 15)) return SIGMA_OPS_ERR_ARG;
-        if (p->row_scale && p->rows_per_scale <= 0) return SIGMA_OPS_ERR_ARG;
+        if (!sigma::aligned(p->dx_add, 16)) return sigma::fail(SIGMA_OPS_ERR_ARG, "dx_add must be 16-byte aligned");
+        if (p->row_scale && p->rows_per_scale <= 0)
+            return sigma::fail(SIGMA_OPS_ERR_ARG, "rows_per_scale %lld must be positive with row_scale", (long long)p->rows_per_scale);
         if (p->gate && (!p->dgate || p->gate_row_stride % 4 != 0 || p->gate_row_stride < p->channels || a.dz_stride % 4 != 0 ||
                         a.dz_stride < p->channels))
-            return SIGMA_OPS_ERR_ARG;
+            return sigma::fail(SIGMA_OPS_ERR_ARG, "a gate needs dgate (%p) and gate_row_stride %lld, dgate_row_stride %lld as multiples of 4, "
+                               "at least channels (%d)", (void*)p->dgate, (long long)p->gate_row_stride, (long long)a.dz_stride, p->channels);
         a.M = p->rows; a.C = p->channels; a.eps = p->eps;
         const bool ok = sigma::dispatch_nv(p->channels, [&](auto nv) {
             hipLaunchKernelGGL(sigma::ln_bwd_kernel<decltype(nv)::value>, dim3(grid), dim3(256), 8 * p->channels * sizeof(float), s, a);
         });
-        if (!ok) return SIGMA_OPS_ERR_ARG;
-        if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+        if (!ok) return sigma::fail(SIGMA_OPS_ERR_ARG, "no kernel is built for channels %d", p->channels);
+        if (const int rc = sigma::launched("ln_bwd_kernel")) return rc;
     }
     const int nw = p->rows > 0 ? grid : 0;                   // partial rows: one per workgroup
     hipLaunchKernelGGL(sigma::ln_reduce_kernel, dim3((2 * p->channels + 15) / 16), dim3(256), 0, s, p->workspace, p->dgamma,
                        p->dbeta, nw, p->channels);
-    return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    return sigma::launched("ln_reduce_kernel");
 }
 
 }  // extern "C"

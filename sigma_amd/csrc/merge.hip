@@ -15,7 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/sigma_ops.h"
+#include "ops_host.h"
 #include "scan_device.h"
 
 namespace sigma {
@@ -189,12 +189,14 @@ __global__ void __launch_bounds__(256) transpose2d_kernel(const TrArgs a) {
     }
 }
 
-bool grid_for(const sigma_merge_params* p, unsigned* grid) {
-    if (!p || p->batch < 0 || p->channels <= 0 || p->height <= 0 || p->width <= 0) return false;
+int grid_for(const sigma_merge_params* p, unsigned* grid) {
+    if (!p) return fail(SIGMA_OPS_ERR_ARG, "params is NULL");
+    if (p->batch < 0 || p->channels <= 0 || p->height <= 0 || p->width <= 0)
+        return fail(SIGMA_OPS_ERR_ARG, "bad sizes batch=%d channels=%d height=%d width=%d", p->batch, p->channels, p->height, p->width);
     const long n = (long)p->batch * ((p->height + kP - 1) / kP) * ((p->width + kP - 1) / kP) * ((p->channels + kC - 1) / kC);
-    if (n > 2147483647L) return false;
+    if (n > 2147483647L) return fail(SIGMA_OPS_ERR_ARG, "%ld workgroups exceed the grid limit of 2^31 - 1", n);
     *grid = (unsigned)n;
-    return true;
+    return SIGMA_OPS_OK;
 }
 
 }  // namespace
@@ -245,7 +247,9 @@ pair_sum_add_kernel(const float* __restrict__ src, float* __restrict__ acc, long
 extern "C" {
 
 int sigma_pair_sum_add(const float* src, float* acc, int64_t n_outer, int64_t inner, void* stream) {
-    if (!src || !acc || n_outer < 0 || inner < 0) return SIGMA_OPS_ERR_ARG;
+    if (!src || !acc || n_outer < 0 || inner < 0)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "src/acc must be non-NULL and n_outer, inner >= 0 (src=%p acc=%p n_outer=%lld inner=%lld)",
+                           (const void*)src, (void*)acc, (long long)n_outer, (long long)inner);
     if (n_outer == 0 || inner == 0) return SIGMA_OPS_OK;
     const int vec = (inner % 4 == 0) && (reinterpret_cast<uintptr_t>(src) % 16 == 0) && (reinterpret_cast<uintptr_t>(acc) % 16 == 0);
     const long per = vec ? inner / 4 : inner;                        // elements (of 16 or 4 bytes) per outer index
@@ -256,43 +260,45 @@ int sigma_pair_sum_add(const float* src, float* acc, int64_t n_outer, int64_t in
     if (gx < 1) gx = 1;
     hipLaunchKernelGGL(sigma::pair_sum_add_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, static_cast<hipStream_t>(stream), src, acc,
                        (long)n_outer, (long)inner, vec);
-    return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    return sigma::launched("pair_sum_add_kernel");
 }
 
 int sigma_cross_merge_nhwc(const sigma_merge_params* p, void* stream) {
     unsigned grid = 0;
-    if (!sigma::grid_for(p, &grid)) return SIGMA_OPS_ERR_ARG;
+    if (const int rc = sigma::grid_for(p, &grid)) return rc;
     if (grid == 0) return SIGMA_OPS_OK;
-    if (!p->planes4 || !p->nhwc) return SIGMA_OPS_ERR_ARG;
+    if (!p->planes4 || !p->nhwc) return sigma::fail(SIGMA_OPS_ERR_ARG, "planes4 and nhwc must be non-NULL device pointers");
     sigma::MergeArgs a{};
     a.ys = p->planes4; a.y = p->nhwc; a.B = p->batch; a.d = p->channels; a.H = p->height; a.W = p->width;
     hipLaunchKernelGGL(sigma::cross_merge_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    return sigma::launched("cross_merge_kernel");
 }
 
 int sigma_cross_split_nhwc(const sigma_merge_params* p, void* stream) {
     unsigned grid = 0;
-    if (!sigma::grid_for(p, &grid)) return SIGMA_OPS_ERR_ARG;
+    if (const int rc = sigma::grid_for(p, &grid)) return rc;
     if (grid == 0) return SIGMA_OPS_OK;
-    if (!p->planes2 || !p->nhwc) return SIGMA_OPS_ERR_ARG;
+    if (!p->planes2 || !p->nhwc) return sigma::fail(SIGMA_OPS_ERR_ARG, "planes2 and nhwc must be non-NULL device pointers");
     sigma::MergeArgs a{};
     a.dy = p->nhwc; a.g2 = p->planes2; a.B = p->batch; a.d = p->channels; a.H = p->height; a.W = p->width;
     hipLaunchKernelGGL(sigma::cross_split_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    return sigma::launched("cross_split_kernel");
 }
 
 int sigma_transpose2d(const sigma_transpose_params* p, void* stream) {
-    if (!p || p->batch < 0 || p->rows <= 0 || p->cols <= 0) return SIGMA_OPS_ERR_ARG;
+    if (!p) return sigma::fail(SIGMA_OPS_ERR_ARG, "params is NULL");
+    if (p->batch < 0 || p->rows <= 0 || p->cols <= 0)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "bad sizes batch=%d rows=%d cols=%d", p->batch, p->rows, p->cols);
     if (p->batch == 0) return SIGMA_OPS_OK;
-    if (!p->src || !p->dst) return SIGMA_OPS_ERR_ARG;
+    if (!p->src || !p->dst) return sigma::fail(SIGMA_OPS_ERR_ARG, "src and dst must be non-NULL device pointers");
     sigma::TrArgs a{};
     a.src = p->src; a.dst = p->dst; a.R = p->rows; a.C = p->cols;
     a.src_bs = p->src_batch_stride; a.src_rs = p->src_row_stride; a.dst_bs = p->dst_batch_stride; a.dst_rs = p->dst_row_stride;
     a.tiles_r = (p->rows + 31) / 32; a.tiles_c = (p->cols + 31) / 32;
     const long n = (long)p->batch * a.tiles_r * a.tiles_c;
-    if (n > 2147483647L) return SIGMA_OPS_ERR_ARG;
+    if (n > 2147483647L) return sigma::fail(SIGMA_OPS_ERR_ARG, "%ld tiles of 32 x 32 exceed the grid limit of 2^31 - 1", n);
     hipLaunchKernelGGL(sigma::transpose2d_kernel, dim3((unsigned)n), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    return sigma::launched("transpose2d_kernel");
 }
 
 }  // extern "C"

@@ -26,7 +26,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/sigma_ops.h"
+#include "ops_host.h"
 #include "scan_device.h"
 
 namespace sigma {
@@ -156,28 +156,30 @@ ohem_final_kernel(const float* __restrict__ nll, const int64_t* __restrict__ lab
 
 constexpr int64_t kOhemWorkspaceBytes = (int64_t)kOhemPasses * kOhemBins * sizeof(uint32_t) + 64;      // histograms + state, 16-byte sized
 
-bool ohem_al(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 }  // namespace sigma
 
 extern "C" {
 
 int64_t sigma_ohem_workspace_bytes(int64_t rows) {
-    if (rows < 0 || rows > 2147483647L) return -1;
+    if (rows < 0 || rows > 2147483647L) return sigma::fail(-1, "rows %lld must be in [0, 2^31 - 1]", (long long)rows);
     return sigma::kOhemWorkspaceBytes;
 }
 
 int sigma_ohem_select(const sigma_ohem_params* p, void* stream) {
     using namespace sigma;
-    if (!p || p->rows < 0 || p->rows > 2147483647L || p->classes < 1) return SIGMA_OPS_ERR_ARG;
-    if (!(p->thresh > 0.0f && p->thresh <= 1.0f)) return SIGMA_OPS_ERR_ARG;                          // NaN fails both
-    if (!p->tau || !p->counts || !p->workspace) return SIGMA_OPS_ERR_ARG;
-    if (p->rows > 0 && (!p->nll || !p->labels || !p->mined)) return SIGMA_OPS_ERR_ARG;
-    if (!ohem_al(p->nll, 4) || !ohem_al(p->tau, 4) || !ohem_al(p->weight, 4) || !ohem_al(p->row_loss, 4) || !ohem_al(p->partial, 4) ||
-        !ohem_al(p->labels, 8) || !ohem_al(p->mined, 8) || !ohem_al(p->counts, 8) || !ohem_al(p->workspace, 16))
-        return SIGMA_OPS_ERR_ARG;
-    if (p->workspace_bytes < kOhemWorkspaceBytes) return SIGMA_OPS_ERR_ARG;
+    if (!p) return fail(SIGMA_OPS_ERR_ARG, "params is NULL");
+    if (p->rows < 0 || p->rows > 2147483647L || p->classes < 1)
+        return fail(SIGMA_OPS_ERR_ARG, "rows %lld must be in [0, 2^31 - 1] and classes %d at least 1", (long long)p->rows, p->classes);
+    if (!(p->thresh > 0.0f && p->thresh <= 1.0f)) return fail(SIGMA_OPS_ERR_ARG, "thresh %g must be in (0, 1]", (double)p->thresh);   // NaN fails both
+    if (!p->tau || !p->counts || !p->workspace) return fail(SIGMA_OPS_ERR_ARG, "tau, counts and workspace must be non-NULL device pointers");
+    if (p->rows > 0 && (!p->nll || !p->labels || !p->mined))
+        return fail(SIGMA_OPS_ERR_ARG, "nll, labels and mined must be non-NULL device pointers when rows > 0");
+    if (!aligned(p->nll, 4) || !aligned(p->tau, 4) || !aligned(p->weight, 4) || !aligned(p->row_loss, 4) || !aligned(p->partial, 4) ||
+        !aligned(p->labels, 8) || !aligned(p->mined, 8) || !aligned(p->counts, 8) || !aligned(p->workspace, 16))
+        return fail(SIGMA_OPS_ERR_ARG, "alignment: nll, tau, weight, row_loss and partial need 4 bytes, labels, mined and counts 8, workspace 16");
+    if (p->workspace_bytes < kOhemWorkspaceBytes)
+        return fail(SIGMA_OPS_ERR_ARG, "workspace of %lld bytes required (got %lld)", (long long)kOhemWorkspaceBytes, (long long)p->workspace_bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint32_t* hist = static_cast<uint32_t*>(p->workspace);
     OhemState* state = reinterpret_cast<OhemState*>(hist + kOhemPasses * kOhemBins);
@@ -192,7 +194,7 @@ int sigma_ohem_select(const sigma_ohem_params* p, void* stream) {
     }
     hipLaunchKernelGGL(ohem_final_kernel, dim3(SIGMA_CE_BLOCKS), dim3(256), 0, st, p->nll, p->labels, p->weight, (long)p->rows,
                        (int)p->classes, (long)p->ignore_index, nl_thresh, state, p->mined, p->tau, p->counts, p->row_loss, p->partial);
-    return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    return launched("ohem kernels");
 }
 
 }  // extern "C"

@@ -26,7 +26,7 @@
 #include <stdint.h>
 #include <type_traits>
 
-#include "../../include/sigma_ops.h"
+#include "ops_host.h"
 #include "loss_rows.h"
 #include "scan_device.h"
 
@@ -445,9 +445,6 @@ void dispatch_flags(bool pad, bool has_w, F&& f) {
     else f(std::false_type(), std::false_type());
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 // ---- backward of  y = a + x * s  with a per-channel s on channels-last rows (CVSSDecoderBlock, vmamba.py:1800-1805) ------
 // dx = dy * s and ds += sum over rows of dy * x, one pass over dy and x.  A thread keeps ONE 16-byte column chunk for the
 // whole kernel (chunk = tid % (C / 4), row slot = tid / (C / 4); 256 / (C / 4) rows per block iteration), so its part of
@@ -529,8 +526,6 @@ unsigned stream_grid(long work_items) {
     return (unsigned)b;
 }
 
-int done() { return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH; }
-
 // the arguments of the plain loss as the launchers take them: no option set (the backward only reads lse)
 sigma_ce_opt_params ce_plain(const float* logits, const int64_t* labels, int64_t rows, int32_t classes, int32_t ld, int64_t ignore_index,
                              const float* lse, float* partial, const float* scale, float* dlogits) {
@@ -556,7 +551,7 @@ int ce_launch_fwd(const sigma_ce_opt_params& p, float x, void* stream) {
         if (!dispatch_nc4((p.classes + 3) / 4, [&](auto n) { launch(softmax_ce_fwd_reg_kernel<decltype(n)::value, PAD, KIND, HAS_W>); }))
             launch(softmax_ce_fwd_kernel<PAD, KIND, HAS_W>);
     });
-    return done();
+    return launched("softmax_ce_fwd_kernel");
 }
 
 template <Loss KIND>
@@ -571,7 +566,7 @@ int ce_launch_bwd(const sigma_ce_opt_params& p, float x, void* stream) {
         if (!dispatch_nc4((p.classes + 3) / 4, [&](auto n) { launch(softmax_ce_bwd_reg_kernel<decltype(n)::value, PAD, KIND, HAS_W>); }))
             launch(softmax_ce_bwd_kernel<PAD, KIND, HAS_W>);
     });
-    return done();
+    return launched("softmax_ce_bwd_kernel");
 }
 
 }  // namespace
@@ -580,111 +575,129 @@ int ce_launch_bwd(const sigma_ce_opt_params& p, float x, void* stream) {
 extern "C" {
 
 int sigma_plane_pool(const float* x, int64_t planes, int64_t hw, float* mean, float* max, float* count, void* stream) {
-    if (planes < 0 || hw <= 0 || planes > 2147483647L) return SIGMA_OPS_ERR_ARG;
+    if (planes < 0 || hw <= 0 || planes > 2147483647L)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "planes %lld must be in [0, 2^31 - 1] and hw %lld positive", (long long)planes, (long long)hw);
     if (planes == 0) return SIGMA_OPS_OK;
-    if (!x || !mean || !max || !count) return SIGMA_OPS_ERR_ARG;
-    const int vec = (hw % 4 == 0 && sigma::al16(x)) ? 1 : 0;
+    if (!x || !mean || !max || !count) return sigma::fail(SIGMA_OPS_ERR_ARG, "x, mean, max and count must be non-NULL device pointers");
+    const int vec = (hw % 4 == 0 && sigma::aligned(x, 16)) ? 1 : 0;
     hipLaunchKernelGGL(sigma::plane_pool_kernel, dim3((unsigned)planes), dim3(256), 0, static_cast<hipStream_t>(stream), x, (long)hw, vec,
                        mean, max, count);
-    return sigma::done();
+    return sigma::launched("plane_pool_kernel");
 }
 
 int sigma_plane_dot(const float* a, const float* b, float* out, int64_t planes, int64_t hw, void* stream) {
-    if (planes < 0 || hw <= 0 || planes > 2147483647L) return SIGMA_OPS_ERR_ARG;
+    if (planes < 0 || hw <= 0 || planes > 2147483647L)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "planes %lld must be in [0, 2^31 - 1] and hw %lld positive", (long long)planes, (long long)hw);
     if (planes == 0) return SIGMA_OPS_OK;
-    if (!a || !b || !out) return SIGMA_OPS_ERR_ARG;
-    const int vec = (hw % 4 == 0 && sigma::al16(a) && sigma::al16(b)) ? 1 : 0;
+    if (!a || !b || !out) return sigma::fail(SIGMA_OPS_ERR_ARG, "a, b and out must be non-NULL device pointers");
+    const int vec = (hw % 4 == 0 && sigma::aligned(a, 16) && sigma::aligned(b, 16)) ? 1 : 0;
     hipLaunchKernelGGL(sigma::plane_dot_kernel, dim3((unsigned)planes), dim3(256), 0, static_cast<hipStream_t>(stream), a, b, (long)hw, vec, out);
-    return sigma::done();
+    return sigma::launched("plane_dot_kernel");
 }
 
 int sigma_plane_scale(const float* x, const float* scale, float* out, int64_t planes, int64_t hw, void* stream) {
-    if (planes < 0 || hw <= 0) return SIGMA_OPS_ERR_ARG;
+    if (planes < 0 || hw <= 0) return sigma::fail(SIGMA_OPS_ERR_ARG, "planes %lld must not be negative and hw %lld be positive", (long long)planes, (long long)hw);
     if (planes == 0) return SIGMA_OPS_OK;
-    if (!x || !scale || !out) return SIGMA_OPS_ERR_ARG;
-    const int vec = (hw % 4 == 0 && sigma::al16(x) && sigma::al16(out)) ? 1 : 0;
+    if (!x || !scale || !out) return sigma::fail(SIGMA_OPS_ERR_ARG, "x, scale and out must be non-NULL device pointers");
+    const int vec = (hw % 4 == 0 && sigma::aligned(x, 16) && sigma::aligned(out, 16)) ? 1 : 0;
     const long work = vec ? planes * (hw / 4) : planes * hw;
     hipLaunchKernelGGL(sigma::plane_scale_kernel, dim3(sigma::stream_grid(work)), dim3(256), 0, static_cast<hipStream_t>(stream), x, scale, out,
                        (long)planes, (long)hw, vec);
-    return sigma::done();
+    return sigma::launched("plane_scale_kernel");
 }
 
 int sigma_colscale_bwd(const float* dy, const float* x, const float* scale, float* dx, float* dscale, int64_t rows, int32_t channels,
                        void* stream) {
-    if (rows < 0 || channels <= 0 || channels % 4 != 0 || channels > 1024) return SIGMA_OPS_ERR_ARG;
+    if (rows < 0 || channels <= 0 || channels % 4 != 0 || channels > 1024)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "rows %lld must not be negative and channels %d be a multiple of 4 in (0, 1024]", (long long)rows, channels);
     if (rows == 0) return SIGMA_OPS_OK;
-    if (!dy || !x || !scale || !dx || !dscale) return SIGMA_OPS_ERR_ARG;
-    if (!sigma::al16(dy) || !sigma::al16(x) || !sigma::al16(scale) || !sigma::al16(dx)) return SIGMA_OPS_ERR_ARG;
+    if (!dy || !x || !scale || !dx || !dscale) return sigma::fail(SIGMA_OPS_ERR_ARG, "dy, x, scale, dx and dscale must be non-NULL device pointers");
+    if (!sigma::aligned(dy, 16) || !sigma::aligned(x, 16) || !sigma::aligned(scale, 16) || !sigma::aligned(dx, 16))
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "dy, x, scale and dx must be 16-byte aligned");
     const int slots = 256 / (channels / 4);
     const long grid = sigma::colscale_grid((long)rows, channels);
     hipLaunchKernelGGL(sigma::colscale_bwd_kernel, dim3((unsigned)grid), dim3(256), (size_t)slots * channels * sizeof(float),
                        static_cast<hipStream_t>(stream), dy, x, scale, dx, dscale, (long)rows, (int)channels);
-    return sigma::done();
+    return sigma::launched("colscale_bwd_kernel");
 }
 
 int64_t sigma_colscale_bwd_workspace_bytes(int64_t rows, int32_t channels) {
-    if (rows < 0 || channels <= 0 || channels % 4 != 0 || channels > 1024) return -1;
+    if (rows < 0 || channels <= 0 || channels % 4 != 0 || channels > 1024)
+        return sigma::fail(-1, "rows %lld must not be negative and channels %d be a multiple of 4 in (0, 1024]", (long long)rows, channels);
     return (int64_t)sigma::colscale_grid((long)rows, channels) * channels * (int64_t)sizeof(float);
 }
 
 int sigma_colscale_bwd_ws(const float* dy, const float* x, const float* scale, float* dx, float* dscale, int64_t rows, int32_t channels,
                           void* workspace, int64_t workspace_bytes, void* stream) {
-    if (rows < 0 || channels <= 0 || channels % 4 != 0 || channels > 1024) return SIGMA_OPS_ERR_ARG;
-    if (!dscale) return SIGMA_OPS_ERR_ARG;
+    if (rows < 0 || channels <= 0 || channels % 4 != 0 || channels > 1024)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "rows %lld must not be negative and channels %d be a multiple of 4 in (0, 1024]", (long long)rows, channels);
+    if (!dscale) return sigma::fail(SIGMA_OPS_ERR_ARG, "dscale is NULL");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (rows == 0) return hipMemsetAsync(dscale, 0, (size_t)channels * sizeof(float), st) == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
-    if (!dy || !x || !scale || !dx) return SIGMA_OPS_ERR_ARG;
-    if (!sigma::al16(dy) || !sigma::al16(x) || !sigma::al16(scale) || !sigma::al16(dx)) return SIGMA_OPS_ERR_ARG;
-    if (!workspace || !sigma::al16(workspace) || workspace_bytes < sigma_colscale_bwd_workspace_bytes(rows, channels)) return SIGMA_OPS_ERR_ARG;
+    if (rows == 0) return sigma::launched("hipMemsetAsync of dscale", hipMemsetAsync(dscale, 0, (size_t)channels * sizeof(float), st));
+    if (!dy || !x || !scale || !dx) return sigma::fail(SIGMA_OPS_ERR_ARG, "dy, x, scale and dx must be non-NULL device pointers");
+    if (!sigma::aligned(dy, 16) || !sigma::aligned(x, 16) || !sigma::aligned(scale, 16) || !sigma::aligned(dx, 16))
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "dy, x, scale and dx must be 16-byte aligned");
+    if (!workspace || !sigma::aligned(workspace, 16) || workspace_bytes < sigma_colscale_bwd_workspace_bytes(rows, channels))
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "a 16-byte aligned workspace of %lld bytes is required (got %p, %lld bytes)",
+                           (long long)sigma_colscale_bwd_workspace_bytes(rows, channels), workspace, (long long)workspace_bytes);
     const int slots = 256 / (channels / 4);
     const long grid = sigma::colscale_grid((long)rows, channels);
     float* ws = static_cast<float*>(workspace);
     hipLaunchKernelGGL(sigma::colscale_bwd_part_kernel, dim3((unsigned)grid), dim3(256), (size_t)slots * channels * sizeof(float),
                        st, dy, x, scale, dx, ws, (long)rows, (int)channels);
-    if (hipGetLastError() != hipSuccess) return SIGMA_OPS_ERR_LAUNCH;
+    if (const int rc = sigma::launched("colscale_bwd_part_kernel")) return rc;
     hipLaunchKernelGGL(sigma::colscale_reduce_kernel, dim3((unsigned)((channels + 63) / 64)), dim3(1024), 0, st, ws, dscale,
                        (int)grid, (int)channels);
-    return sigma::done();
+    return sigma::launched("colscale_reduce_kernel");
 }
 
 int sigma_plane_gate_bwd(const sigma_gate_bwd_params* p, void* stream) {
-    if (!p || p->planes < 0 || p->hw <= 0) return SIGMA_OPS_ERR_ARG;
+    if (!p) return sigma::fail(SIGMA_OPS_ERR_ARG, "params is NULL");
+    if (p->planes < 0 || p->hw <= 0)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "planes %lld must not be negative and hw %lld be positive", (long long)p->planes, (long long)p->hw);
     if (p->planes == 0) return SIGMA_OPS_OK;
-    if (!p->g || !p->x || !p->scale || !p->dmean || !p->dmax || !p->max || !p->count || !p->dx) return SIGMA_OPS_ERR_ARG;
+    if (!p->g || !p->x || !p->scale || !p->dmean || !p->dmax || !p->max || !p->count || !p->dx)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "g, x, scale, dmean, dmax, max, count and dx must be non-NULL device pointers");
     sigma::GateBwdArgs a{p->g, p->x, p->scale, p->dmean, p->dmax, p->max, p->count, p->dx, (long)p->planes, (long)p->hw, 0};
-    a.vec = (p->hw % 4 == 0 && sigma::al16(p->g) && sigma::al16(p->x) && sigma::al16(p->dx)) ? 1 : 0;
+    a.vec = (p->hw % 4 == 0 && sigma::aligned(p->g, 16) && sigma::aligned(p->x, 16) && sigma::aligned(p->dx, 16)) ? 1 : 0;
     const long work = a.vec ? a.planes * (a.hw / 4) : a.planes * a.hw;
     hipLaunchKernelGGL(sigma::plane_gate_bwd_kernel, dim3(sigma::stream_grid(work)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    return sigma::done();
+    return sigma::launched("plane_gate_bwd_kernel");
 }
 
 int sigma_softmax_ce_fwd(const float* logits, const int64_t* labels, int64_t rows, int32_t classes, int64_t ignore_index, float* lse,
                          float* partial, void* stream) {
-    if (classes <= 0 || classes % 4 != 0) return SIGMA_OPS_ERR_ARG;
+    if (classes <= 0 || classes % 4 != 0) return sigma::fail(SIGMA_OPS_ERR_ARG, "classes %d must be a positive multiple of 4 (other counts: the _ld entry points)", classes);
     return sigma_softmax_ce_fwd_ld(logits, labels, rows, classes, classes, ignore_index, lse, partial, stream);
 }
 
 int sigma_softmax_ce_bwd(const float* logits, const int64_t* labels, const float* lse, const float* scale, int64_t rows, int32_t classes,
                          int64_t ignore_index, float* dlogits, void* stream) {
-    if (classes <= 0 || classes % 4 != 0) return SIGMA_OPS_ERR_ARG;
+    if (classes <= 0 || classes % 4 != 0) return sigma::fail(SIGMA_OPS_ERR_ARG, "classes %d must be a positive multiple of 4 (other counts: the _ld entry points)", classes);
     return sigma_softmax_ce_bwd_ld(logits, labels, lse, scale, rows, classes, classes, ignore_index, dlogits, stream);
 }
 
 // ld == classes: the PAD = false kernels, i.e. what sigma_softmax_ce_fwd / _bwd have always launched
 int sigma_softmax_ce_fwd_ld(const float* logits, const int64_t* labels, int64_t rows, int32_t classes, int32_t ld, int64_t ignore_index,
                             float* lse, float* partial, void* stream) {
-    if (rows < 0 || classes < 1 || ld % 4 != 0 || ld < classes) return SIGMA_OPS_ERR_ARG;
-    if (!partial) return SIGMA_OPS_ERR_ARG;
-    if (rows > 0 && (!logits || !labels || !lse || !sigma::al16(logits))) return SIGMA_OPS_ERR_ARG;
+    if (rows < 0 || classes < 1 || ld % 4 != 0 || ld < classes)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "rows %lld must not be negative, classes %d be at least 1 and ld %d a multiple of 4, at least classes",
+                           (long long)rows, classes, ld);
+    if (!partial) return sigma::fail(SIGMA_OPS_ERR_ARG, "partial is NULL");
+    if (rows > 0 && (!logits || !labels || !lse || !sigma::aligned(logits, 16)))
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "logits, labels and lse must be non-NULL device pointers, logits 16-byte aligned");
     const sigma_ce_opt_params p = sigma::ce_plain(logits, labels, rows, classes, ld, ignore_index, lse, partial, nullptr, nullptr);
     return sigma::ce_launch_fwd<sigma::kPlain>(p, 0.0f, stream);
 }
 
 int sigma_softmax_ce_bwd_ld(const float* logits, const int64_t* labels, const float* lse, const float* scale, int64_t rows, int32_t classes,
                             int32_t ld, int64_t ignore_index, float* dlogits, void* stream) {
-    if (rows < 0 || classes < 1 || ld % 4 != 0 || ld < classes) return SIGMA_OPS_ERR_ARG;
+    if (rows < 0 || classes < 1 || ld % 4 != 0 || ld < classes)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "rows %lld must not be negative, classes %d be at least 1 and ld %d a multiple of 4, at least classes",
+                           (long long)rows, classes, ld);
     if (rows == 0) return SIGMA_OPS_OK;
-    if (!logits || !labels || !lse || !scale || !dlogits || !sigma::al16(logits) || !sigma::al16(dlogits)) return SIGMA_OPS_ERR_ARG;
+    if (!logits || !labels || !lse || !scale || !dlogits || !sigma::aligned(logits, 16) || !sigma::aligned(dlogits, 16))
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "logits, labels, lse, scale and dlogits must be non-NULL device pointers, logits and dlogits 16-byte aligned");
     const sigma_ce_opt_params p = sigma::ce_plain(logits, labels, rows, classes, ld, ignore_index, lse, nullptr, scale, dlogits);
     return sigma::ce_launch_bwd<sigma::kPlain>(p, 0.0f, stream);
 }
@@ -692,31 +705,38 @@ int sigma_softmax_ce_bwd_ld(const float* logits, const int64_t* labels, const fl
 // everything the _opt_ and _focal_ entry points check alike in both directions, before any launch.  gamma (focal only, else
 // NULL): smoothing is refused, and an exponent that is NaN, negative or in (0, 1)
 static int ce_opt_check(const sigma_ce_opt_params* p, const float* gamma) {
-    if (!p || p->rows < 0 || p->classes < 1 || p->ld % 4 != 0 || p->ld < p->classes) return SIGMA_OPS_ERR_ARG;
-    if (!(p->label_smoothing >= 0.0f && p->label_smoothing <= 1.0f)) return SIGMA_OPS_ERR_ARG;      // NaN fails both
-    if (!sigma::al4(p->weight) || !sigma::al4(p->lse) || !sigma::al4(p->row_loss) || !sigma::al4(p->partial) ||
-        !sigma::al4(p->scale) || !sigma::al4(p->row_grad) || (reinterpret_cast<uintptr_t>(p->labels) & 7u) != 0)
-        return SIGMA_OPS_ERR_ARG;
+    if (!p) return sigma::fail(SIGMA_OPS_ERR_ARG, "params is NULL");
+    if (p->rows < 0 || p->classes < 1 || p->ld % 4 != 0 || p->ld < p->classes)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "rows %lld must not be negative, classes %d be at least 1 and ld %d a multiple of 4, at least classes",
+                           (long long)p->rows, p->classes, p->ld);
+    if (!(p->label_smoothing >= 0.0f && p->label_smoothing <= 1.0f))      // NaN fails both
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "label_smoothing %g must be in [0, 1]", (double)p->label_smoothing);
+    if (!sigma::aligned(p->weight, 4) || !sigma::aligned(p->lse, 4) || !sigma::aligned(p->row_loss, 4) || !sigma::aligned(p->partial, 4) ||
+        !sigma::aligned(p->scale, 4) || !sigma::aligned(p->row_grad, 4) || !sigma::aligned(p->labels, 8))
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "alignment: weight, lse, row_loss, partial, scale and row_grad need 4 bytes, labels 8");
     if (gamma) {
-        if (p->label_smoothing != 0.0f) return SIGMA_OPS_ERR_ARG;
-        if (!(*gamma == 0.0f || (*gamma >= 1.0f && *gamma <= 3.0e38f))) return SIGMA_OPS_ERR_ARG;      // NaN and inf fail both
+        if (p->label_smoothing != 0.0f) return sigma::fail(SIGMA_OPS_ERR_ARG, "the focal loss takes no label_smoothing (got %g)", (double)p->label_smoothing);
+        if (!(*gamma == 0.0f || (*gamma >= 1.0f && *gamma <= 3.0e38f)))      // NaN and inf fail both
+            return sigma::fail(SIGMA_OPS_ERR_ARG, "gamma %g must be 0 or finite and at least 1", (double)*gamma);
     }
     return SIGMA_OPS_OK;
 }
 
 static int ce_opt_fwd_check(const sigma_ce_opt_params* p, const float* gamma) {
     if (const int rc = ce_opt_check(p, gamma)) return rc;
-    if (!p->partial) return SIGMA_OPS_ERR_ARG;
-    if (p->rows > 0 && (!p->logits || !p->labels || !p->lse || !sigma::al16(p->logits))) return SIGMA_OPS_ERR_ARG;
+    if (!p->partial) return sigma::fail(SIGMA_OPS_ERR_ARG, "partial is NULL");
+    if (p->rows > 0 && (!p->logits || !p->labels || !p->lse || !sigma::aligned(p->logits, 16)))
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "logits, labels and lse must be non-NULL device pointers, logits 16-byte aligned");
     return SIGMA_OPS_OK;
 }
 
 // no rows: nothing is launched and no buffer is looked at
 static int ce_opt_bwd_check(const sigma_ce_opt_params* p, const float* gamma) {
     if (const int rc = ce_opt_check(p, gamma)) return rc;
-    if ((p->scale != nullptr) == (p->row_grad != nullptr)) return SIGMA_OPS_ERR_ARG;      // one of them, not both
-    if (p->rows > 0 && (!p->logits || !p->labels || !p->lse || !p->dlogits || !sigma::al16(p->logits) || !sigma::al16(p->dlogits)))
-        return SIGMA_OPS_ERR_ARG;
+    if ((p->scale != nullptr) == (p->row_grad != nullptr))      // one of them, not both
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "exactly one of scale (%p) and row_grad (%p) must be given", (const void*)p->scale, (const void*)p->row_grad);
+    if (p->rows > 0 && (!p->logits || !p->labels || !p->lse || !p->dlogits || !sigma::aligned(p->logits, 16) || !sigma::aligned(p->dlogits, 16)))
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "logits, labels, lse and dlogits must be non-NULL device pointers, logits and dlogits 16-byte aligned");
     return SIGMA_OPS_OK;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include "capi_error.h"    // sigma::fail
 #include "scan_device.h"
 
 namespace sigma {
@@ -97,9 +98,5 @@ static hipError_t launch_bwd_pair(int grid, int block, size_t lds, const BwdArgs
     if (e != hipSuccess) return e;
     return launch_reduce_after(a, stream);
 }
-
-// Error report of the C ABI (capi.hip): formats the thread-local message that sigma_scan_last_error() returns and
-// hands `code` back.  Internal to the library: not part of include/sigma_scan.h.
-__attribute__((visibility("hidden"))) int fail(int code, const char* fmt, ...);
 
 }  // namespace sigma

@@ -26,15 +26,13 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/sigma_ops.h"
+#include "ops_host.h"
 
 namespace sigma {
 namespace {
 
 constexpr int kSegThreads = 256;
 constexpr unsigned kSegMaxGrid = 512;       // two workgroups per CU; a lane then walks ~1-3 pixels of a 480 x 640 image
-
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 template <int V>
 __global__ __launch_bounds__(kSegThreads) void seg_accumulate_kernel(const float* __restrict__ score, double* __restrict__ acc,
@@ -219,10 +217,15 @@ void dispatch_confusion(const ConfArgs& a, bool from_acc, bool lds_hist, int pix
 extern "C" {
 
 int sigma_seg_accumulate(const sigma_seg_accumulate_params* p, void* stream) {
-    if (!p || p->pixels < 0 || p->classes < 1 || p->classes > 65535) return SIGMA_OPS_ERR_ARG;
-    if (p->first != 0 && p->first != 1) return SIGMA_OPS_ERR_ARG;
-    if (p->score_plane_stride < p->pixels || p->acc_plane_stride < p->pixels) return SIGMA_OPS_ERR_ARG;
-    if (!p->score || !p->acc || !sigma::aligned(p->score, 4) || !sigma::aligned(p->acc, 8)) return SIGMA_OPS_ERR_ARG;
+    if (!p) return sigma::fail(SIGMA_OPS_ERR_ARG, "params is NULL");
+    if (p->pixels < 0 || p->classes < 1 || p->classes > 65535)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "pixels %lld must not be negative and classes %d be in [1, 65535]", (long long)p->pixels, p->classes);
+    if (p->first != 0 && p->first != 1) return sigma::fail(SIGMA_OPS_ERR_ARG, "first must be 0 or 1 (got %d)", p->first);
+    if (p->score_plane_stride < p->pixels || p->acc_plane_stride < p->pixels)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "score_plane_stride %lld and acc_plane_stride %lld must be at least pixels (%lld)",
+                           (long long)p->score_plane_stride, (long long)p->acc_plane_stride, (long long)p->pixels);
+    if (!p->score || !p->acc || !sigma::aligned(p->score, 4) || !sigma::aligned(p->acc, 8))
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "score must be a non-NULL 4-byte aligned and acc a non-NULL 8-byte aligned device pointer");
     if (p->pixels == 0) return SIGMA_OPS_OK;
     const bool vec = p->pixels % 4 == 0 && p->score_plane_stride % 4 == 0 && p->acc_plane_stride % 2 == 0 &&
                      sigma::aligned(p->score, 16) && sigma::aligned(p->acc, 16);
@@ -237,26 +240,33 @@ int sigma_seg_accumulate(const sigma_seg_accumulate_params* p, void* stream) {
     else
         hipLaunchKernelGGL(sigma::seg_accumulate_kernel<1>, grid, dim3(sigma::kSegThreads), 0, s, p->score, p->acc, (long)p->pixels,
                            (long)p->score_plane_stride, (long)p->acc_plane_stride, (int)p->first);
-    return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    return sigma::launched("seg_accumulate_kernel");
 }
 
 int sigma_seg_argmax_confusion(const sigma_seg_confusion_params* p, void* stream) {
-    if (!p || p->pixels < 0 || p->pixels > 2147483647L) return SIGMA_OPS_ERR_ARG;
-    if (p->n_cl < 1 || p->n_cl > 256) return SIGMA_OPS_ERR_ARG;
-    if ((p->gt_elem_size != 1 && p->gt_elem_size != 8) || (p->pred_elem_size != 1 && p->pred_elem_size != 8)) return SIGMA_OPS_ERR_ARG;
+    if (!p) return sigma::fail(SIGMA_OPS_ERR_ARG, "params is NULL");
+    if (p->pixels < 0 || p->pixels > 2147483647L) return sigma::fail(SIGMA_OPS_ERR_ARG, "pixels %lld must be in [0, 2^31 - 1]", (long long)p->pixels);
+    if (p->n_cl < 1 || p->n_cl > 256) return sigma::fail(SIGMA_OPS_ERR_ARG, "n_cl %d must be in [1, 256]", p->n_cl);
+    if ((p->gt_elem_size != 1 && p->gt_elem_size != 8) || (p->pred_elem_size != 1 && p->pred_elem_size != 8))
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "gt_elem_size %d and pred_elem_size %d must each be 1 or 8", p->gt_elem_size, p->pred_elem_size);
     const bool from_acc = p->acc != nullptr;
     if (from_acc) {
-        if (p->classes < 1 || p->classes > 65535 || p->acc_plane_stride < p->pixels || !sigma::aligned(p->acc, 8)) return SIGMA_OPS_ERR_ARG;
-        if (p->pred_elem_size == 1 && p->classes > 256) return SIGMA_OPS_ERR_ARG;    // a uint8 pred could not hold the index
+        if (p->classes < 1 || p->classes > 65535 || p->acc_plane_stride < p->pixels || !sigma::aligned(p->acc, 8))
+            return sigma::fail(SIGMA_OPS_ERR_ARG, "with acc: classes %d must be in [1, 65535], acc_plane_stride %lld at least pixels (%lld), acc 8-byte aligned",
+                               p->classes, (long long)p->acc_plane_stride, (long long)p->pixels);
+        if (p->pred_elem_size == 1 && p->classes > 256)      // a uint8 pred could not hold the index
+            return sigma::fail(SIGMA_OPS_ERR_ARG, "pred_elem_size 1 cannot hold the index of %d classes", p->classes);
     } else {
-        if (p->classes != 0 || !p->pred) return SIGMA_OPS_ERR_ARG;
+        if (p->classes != 0 || !p->pred) return sigma::fail(SIGMA_OPS_ERR_ARG, "without acc: classes must be 0 (got %d) and pred non-NULL", p->classes);
     }
-    if (p->pred && !sigma::aligned(p->pred, (uintptr_t)p->pred_elem_size)) return SIGMA_OPS_ERR_ARG;
+    if (!sigma::aligned(p->pred, (uintptr_t)p->pred_elem_size))
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "pred must be aligned to pred_elem_size (%d bytes)", p->pred_elem_size);
     if (!p->gt) {
-        if (!from_acc || !p->pred) return SIGMA_OPS_ERR_ARG;                  // arg-max only: pred must be written
+        if (!from_acc || !p->pred) return sigma::fail(SIGMA_OPS_ERR_ARG, "without gt (arg-max only) acc and pred must be non-NULL");
     } else {
-        if (!sigma::aligned(p->gt, (uintptr_t)p->gt_elem_size)) return SIGMA_OPS_ERR_ARG;
-        if (!p->hist || !p->counts || !sigma::aligned(p->hist, 8) || !sigma::aligned(p->counts, 8)) return SIGMA_OPS_ERR_ARG;
+        if (!sigma::aligned(p->gt, (uintptr_t)p->gt_elem_size)) return sigma::fail(SIGMA_OPS_ERR_ARG, "gt must be aligned to gt_elem_size (%d bytes)", p->gt_elem_size);
+        if (!p->hist || !p->counts || !sigma::aligned(p->hist, 8) || !sigma::aligned(p->counts, 8))
+            return sigma::fail(SIGMA_OPS_ERR_ARG, "with gt: hist and counts must be non-NULL 8-byte aligned device pointers");
     }
     if (p->pixels == 0) return SIGMA_OPS_OK;
 
@@ -272,7 +282,7 @@ int sigma_seg_argmax_confusion(const sigma_seg_confusion_params* p, void* stream
         if (p->pred_elem_size == 1) sigma::dispatch_confusion<int64_t, uint8_t>(a, from_acc, lds_hist, pix, s);
         else sigma::dispatch_confusion<int64_t, int64_t>(a, from_acc, lds_hist, pix, s);
     }
-    return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    return sigma::launched("seg_confusion_kernel");
 }
 
 }  // extern "C"

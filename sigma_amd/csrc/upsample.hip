@@ -12,7 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/sigma_ops.h"
+#include "ops_host.h"
 
 namespace sigma {
 namespace {
@@ -100,8 +100,10 @@ up2x_bwd_kernel(const float4* __restrict__ g, float4* __restrict__ din, int B, i
 
 extern "C" int sigma_upsample2x_nhwc(const float* in, float* out, int32_t batch, int32_t height, int32_t width, int32_t channels,
                                      int32_t backward, void* stream) {
-    if (!in || !out || batch < 0 || height <= 0 || width <= 0 || channels <= 0 || channels % 4 != 0) return SIGMA_OPS_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) return SIGMA_OPS_ERR_ARG;
+    if (!in || !out || batch < 0 || height <= 0 || width <= 0 || channels <= 0 || channels % 4 != 0)
+        return sigma::fail(SIGMA_OPS_ERR_ARG, "in/out must be non-NULL, batch >= 0, height and width > 0 and channels a positive multiple of 4 "
+                           "(in=%p out=%p batch=%d height=%d width=%d channels=%d)", (const void*)in, (void*)out, batch, height, width, channels);
+    if (!sigma::aligned(in, 16) || !sigma::aligned(out, 16)) return sigma::fail(SIGMA_OPS_ERR_ARG, "in and out must be 16-byte aligned");
     if (batch == 0) return SIGMA_OPS_OK;
     const int C4 = channels / 4;
     const long work = backward ? (long)batch * height * width * C4 : (long)batch * 4 * height * width * C4;
@@ -114,5 +116,5 @@ extern "C" int sigma_upsample2x_nhwc(const float* in, float* out, int32_t batch,
     else
         hipLaunchKernelGGL(sigma::up2x_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(in),
                            reinterpret_cast<float4*>(out), batch, height, width, C4);
-    return hipGetLastError() == hipSuccess ? SIGMA_OPS_OK : SIGMA_OPS_ERR_LAUNCH;
+    return sigma::launched(backward ? "up2x_bwd_kernel" : "up2x_fwd_kernel");
 }

@@ -117,8 +117,8 @@ def _run(name, p, dev):
         p.workspace, p.workspace_bytes = ws.data_ptr(), need
     rc = _launch.call(name, ctypes.byref(p), device=dev)
     del ws
-    if rc != 0:
-        raise RuntimeError(f"{name} failed (sigma_ops status {rc}): M={p.M} N={p.N} K={p.K} lda={p.lda} ldb={p.ldb}")
+    if rc != 0:         # (the shape text is formatted for a failure only)
+        _capi.check(rc, f"{name} failed, M={p.M} N={p.N} K={p.K} lda={p.lda} ldb={p.ldb}")
 
 
 def _check2d(*ts):

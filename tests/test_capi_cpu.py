@@ -8,6 +8,7 @@ import re
 import pytest
 
 from sigma_amd import _capi
+from tests.capi_refusals import assert_refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -127,13 +128,13 @@ def _params(**kw):
 
 def test_host_validation_without_gpu():
     lib = _capi.load()
-    assert lib.sigma_selective_scan_fwd(None, None) == 1                       # NULL params
+    assert_refused(lib.sigma_selective_scan_fwd, None, None, says="NULL")      # NULL params
     assert lib.sigma_selective_scan_fwd(ctypes.byref(_params(io_dtype=7)), None) == 3
     assert lib.sigma_selective_scan_fwd(ctypes.byref(_params(n_groups=3)), None) == 2   # dim % groups
     assert "dividable" in _capi.last_error()
     assert lib.sigma_selective_scan_fwd(ctypes.byref(_params(dstate=257)), None) == 2
     assert lib.sigma_selective_scan_fwd(ctypes.byref(_params(n_chunks=2)), None) == 2
-    assert lib.sigma_selective_scan_fwd(ctypes.byref(_params()), None) == 1             # NULL tensors
+    assert_refused(lib.sigma_selective_scan_fwd, ctypes.byref(_params()), None, says="non-NULL")      # NULL tensors
     # empty problems are a no-op success (nothing is launched)
     assert lib.sigma_selective_scan_fwd(ctypes.byref(_params(seqlen=0, n_chunks=0)), None) == 0
     assert lib.sigma_selective_scan_fwd(ctypes.byref(_params(batch=0)), None) == 0
@@ -245,9 +246,9 @@ def test_gemm_workspace_query_is_host_side_planning():
     sh = params(112, 768, 1200, 1200, 1200, 768, batch=32, c_mod=2, strideA=112 * 1200, strideB=768 * 1200, strideC=112 * 768, accumulate=1)
     assert q(sh, 0) == 2 * 16 * 112 * 768 * 4
     # bad arguments
-    assert q(params(19200, 1536, 384, 384, 384, 1536), 7) == -1
+    assert_refused(q, params(19200, 1536, 384, 384, 384, 1536), 7, code=-1, says="form")
     bad = params(19200, 1536, 383, 384, 384, 1536)
-    assert q(bad, 0) == -1
+    assert_refused(q, bad, 0, code=-1, says="K")
 
 
 def test_gemm_ragged_shared_outputs_and_transposed_range_are_planned_on_the_host():
@@ -292,7 +293,7 @@ def test_gemm_ragged_shared_outputs_and_transposed_range_are_planned_on_the_host
         setattr(bad, field, value)
         if field == "batch":
             bad.strideA, bad.strideB = 64 * 32, 128 * 32
-        assert q(bad, 0) == -1, field
+        assert_refused(q, bad, 0, code=-1, says="t_cols", msg=field)
 
 
 def test_gemm_plan_reports_the_kernel_variant_on_the_host():
@@ -351,6 +352,11 @@ def test_gemm_plan_reports_the_kernel_variant_on_the_host():
         f, out = _capi.GEMM_FORMS[form], (ctypes.c_int32 * 8)()
         planned = int(lib.sigma_gemm_plan(ctypes.byref(p), f, ctypes.byref(out)))
         assert planned != 0, "accepted: not launched on the fake pointers"
+        # the three answers, each with a reason of its own in the error text -- the same one, as they share the plan
+        reasons = [assert_refused(lib.sigma_gemm_plan, ctypes.byref(p), f, ctypes.byref(out), code=planned),
+                   assert_refused(getattr(lib, f"sigma_gemm_{form}_split3"), ctypes.byref(p), None, code=planned),
+                   assert_refused(lib.sigma_gemm_workspace_bytes, ctypes.byref(p), f, code=-1)]
+        assert len(set(reasons)) == 1, reasons
         return (int(getattr(lib, f"sigma_gemm_{form}_split3")(ctypes.byref(p), None)), planned, int(lib.sigma_gemm_workspace_bytes(ctypes.byref(p), f)))
 
     for form, ldb in (("nt", 1536), ("nn", 768)):

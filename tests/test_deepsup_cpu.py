@@ -14,6 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from sigma_amd import _capi
+from tests.capi_refusals import assert_refused
 from tests.deepsup_bounds import CASE_IDS, CASES, U, bounds, deepsup_inputs, emulate_fp32
 from tests.deepsup_fp64_twin import VARIANTS, twin, upsample
 from tests.deepsup_utils import build_ds_model
@@ -198,24 +199,24 @@ def test_refused_arguments_return_err_arg_without_a_device(field, value):
     for fn in (lib.sigma_upsample_ce_fwd, lib.sigma_upsample_ce_bwd):
         p = _good_params()
         setattr(p, field, value)
-        assert fn(ctypes.byref(p), None) == 1
+        assert_refused(fn, ctypes.byref(p), None, says=field)
 
 
 def test_refused_sizes_and_direction_specific_pointers():
     lib = _capi.load()
     for fn in (lib.sigma_upsample_ce_fwd, lib.sigma_upsample_ce_bwd):
-        assert fn(None, None) == 1
+        assert_refused(fn, None, None, says="NULL")
         p = _good_params()                             # 2^31 fine pixels: one more than the kernels index
         p.batch, p.height, p.width, p.scale = 2, 1024, 1024, 32
-        assert fn(ctypes.byref(p), None) == 1
+        assert_refused(fn, ctypes.byref(p), None, says="fine pixels")
         p.batch, p.height, p.width, p.scale = 2 ** 31 - 1, 2 ** 31 - 1, 2 ** 31 - 1, 32
-        assert fn(ctypes.byref(p), None) == 1
+        assert_refused(fn, ctypes.byref(p), None, says="pixels")
     for fn, field, bad in ((lib.sigma_upsample_ce_fwd, "partial", None), (lib.sigma_upsample_ce_fwd, "partial", 0x4002),
                            (lib.sigma_upsample_ce_bwd, "scale_grad", None), (lib.sigma_upsample_ce_bwd, "scale_grad", 0x5001),
                            (lib.sigma_upsample_ce_bwd, "dlogits", None), (lib.sigma_upsample_ce_bwd, "dlogits", 0x6008)):
         p = _good_params()
         setattr(p, field, bad)
-        assert fn(ctypes.byref(p), None) == 1
+        assert_refused(fn, ctypes.byref(p), None, says=field)
 
 
 def test_kernel_family_is_one_forward_and_one_backward_template(tmp_path):

@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 from sigma_amd import _capi
+from tests.capi_refusals import assert_refused
 from tests.deepsup_fp64_twin import upsample
 from tests.deepsup_loss_bounds import (CASE_IDS, CASES, G1_CASE, G1_KIND, IGNORE, KIND_IDS, KINDS, OHEM_IDS, OHEM_PAIRS, bounds,
                                        class_weights, deepsup_inputs, emulate_fp32, ohem_gap, upstream_of)
@@ -159,15 +160,16 @@ REFUSED_BWD = [dict(scale_grad=None), dict(row_grad=0x50000), dict(dlogits=None)
 def test_host_validation_without_gpu():
     """every refusal of include/sigma_ops.h returns SIGMA_OPS_ERR_ARG before any launch"""
     lib = _capi.load()
-    assert lib.sigma_upsample_loss_fwd(None, None) == 1 and lib.sigma_upsample_loss_bwd(None, None) == 1
+    assert_refused(lib.sigma_upsample_loss_fwd, None, None, says="NULL")
+    assert_refused(lib.sigma_upsample_loss_bwd, None, None, says="NULL")
     for kw in REFUSED_BOTH:
         p = _params(**kw)
-        assert lib.sigma_upsample_loss_fwd(ctypes.byref(p), None) == 1, kw
-        assert lib.sigma_upsample_loss_bwd(ctypes.byref(p), None) == 1, kw
+        assert_refused(lib.sigma_upsample_loss_fwd, ctypes.byref(p), None, msg=kw)
+        assert_refused(lib.sigma_upsample_loss_bwd, ctypes.byref(p), None, msg=kw)
     for kw in REFUSED_FWD:
-        assert lib.sigma_upsample_loss_fwd(ctypes.byref(_params(**kw)), None) == 1, kw
+        assert_refused(lib.sigma_upsample_loss_fwd, ctypes.byref(_params(**kw)), None, msg=kw)
     for kw in REFUSED_BWD:
-        assert lib.sigma_upsample_loss_bwd(ctypes.byref(_params(**kw)), None) == 1, kw
+        assert_refused(lib.sigma_upsample_loss_bwd, ctypes.byref(_params(**kw)), None, msg=kw)
 
 
 def test_front_end_declines_without_a_gpu_and_by_criterion(monkeypatch):

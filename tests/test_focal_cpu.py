@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from sigma_amd import _capi
+from tests.capi_refusals import assert_refused
 from tests import focal_bounds as fb
 from tests.focal_fp64_twin import VARIANTS, twin
 from tests.test_stream_fp64_gpu import check, rejects
@@ -219,24 +220,26 @@ def _params(**kw):
 
 def test_entry_points_refuse_bad_arguments_before_any_launch():
     lib = _capi.load()
-    ERR = 1                                                   # SIGMA_OPS_ERR_ARG
-    fwd = lambda p, gamma=2.0: lib.sigma_softmax_focal_fwd(ctypes.byref(p), gamma, None)
-    bwd = lambda p, gamma=2.0: lib.sigma_softmax_focal_bwd(ctypes.byref(p), gamma, None)
-    assert lib.sigma_softmax_focal_fwd(None, 2.0, None) == ERR and lib.sigma_softmax_focal_bwd(None, 2.0, None) == ERR
+    # every refusal is SIGMA_OPS_ERR_ARG (1) with a reason of its own in the error text
+    fwd = lambda p, gamma=2.0, **kw: assert_refused(lib.sigma_softmax_focal_fwd, ctypes.byref(p), gamma, None, **kw)
+    bwd = lambda p, gamma=2.0, **kw: assert_refused(lib.sigma_softmax_focal_bwd, ctypes.byref(p), gamma, None, **kw)
+    assert_refused(lib.sigma_softmax_focal_fwd, None, 2.0, None, says="NULL")
+    assert_refused(lib.sigma_softmax_focal_bwd, None, 2.0, None, says="NULL")
     for call in (fwd, bwd):
         for gamma in (float("nan"), -1.0, -0.0001, 0.5, 0.999, 1e-30, float("inf")):
-            assert call(_params(), gamma) == ERR, gamma
-        assert call(_params(label_smoothing=0.1)) == ERR
+            call(_params(), gamma, says="gamma", msg=gamma)
+        call(_params(label_smoothing=0.1), says="label_smoothing")
         # everything the option entry points refuse
         for kw in (dict(rows=-1), dict(classes=0), dict(ld=6), dict(ld=4), dict(logits=None), dict(labels=None), dict(lse=None),
                    dict(logits=0x10004), dict(labels=0x20004), dict(lse=0x30002), dict(weight=0x70002), dict(row_loss=0x80002),
                    dict(partial=0x40002), dict(scale=0x50002), dict(row_grad=0x90002)):
-            assert call(_params(**kw)) == ERR, kw
-    assert fwd(_params(partial=None)) == ERR
-    assert bwd(_params(dlogits=None)) == ERR and bwd(_params(dlogits=0x60004)) == ERR
-    assert bwd(_params(scale=None)) == ERR                    # neither scale nor row_grad
-    assert bwd(_params(row_grad=0x90000)) == ERR              # both
-    assert bwd(_params(rows=0)) == 0                          # nothing to do is a success without a launch
+            call(_params(**kw), msg=kw)
+    fwd(_params(partial=None), says="partial")
+    bwd(_params(dlogits=None), says="dlogits")
+    bwd(_params(dlogits=0x60004), says="dlogits")
+    bwd(_params(scale=None), says="row_grad")                 # neither scale nor row_grad
+    bwd(_params(row_grad=0x90000), says="row_grad")           # both
+    assert lib.sigma_softmax_focal_bwd(ctypes.byref(_params(rows=0)), 2.0, None) == 0      # nothing to do is a success without a launch
     header = open(os.path.join(ROOT, "include", "sigma_ops.h")).read()
     for name in ("sigma_softmax_focal_fwd", "sigma_softmax_focal_bwd"):
         assert name in _capi.OPS_SYMBOLS and f"int {name}(const sigma_ce_opt_params *params, float gamma, void *stream);" in header

@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from sigma_amd import _capi
+from tests.capi_refusals import assert_refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sigma_softmax_ce_fwd_ld", "sigma_softmax_ce_bwd_ld")
@@ -69,11 +70,15 @@ def test_new_entry_points_check_their_arguments_before_any_launch():
     ok = ctypes.c_void_p(0x10000)                                # 16-byte aligned, never dereferenced: every call below is refused
     odd = ctypes.c_void_p(0x10004)
 
-    def fwd(rows=8, classes=9, ld=12, logits=ok, labels=ok, lse=ok, partial=ok):
+    def fwd_status(rows=8, classes=9, ld=12, logits=ok, labels=ok, lse=ok, partial=ok):
         return lib.sigma_softmax_ce_fwd_ld(logits, labels, rows, classes, ld, 255, lse, partial, _null())
 
-    def bwd(rows=8, classes=9, ld=12, logits=ok, labels=ok, lse=ok, scale=ok, dl=ok):
+    def bwd_status(rows=8, classes=9, ld=12, logits=ok, labels=ok, lse=ok, scale=ok, dl=ok):
         return lib.sigma_softmax_ce_bwd_ld(logits, labels, lse, scale, rows, classes, ld, 255, dl, _null())
+
+    # fwd / bwd: the status of a call that must be refused -- with a reason of its own in the error text (assert_refused)
+    fwd = lambda **kw: assert_refused(lambda: fwd_status(**kw), code=ERR, msg=kw) and ERR
+    bwd = lambda **kw: assert_refused(lambda: bwd_status(**kw), code=ERR, msg=kw) and ERR
 
     for f in (fwd, bwd):
         assert f(ld=10) == ERR and f(ld=9) == ERR and f(ld=13) == ERR           # ld % 4 != 0
@@ -84,10 +89,10 @@ def test_new_entry_points_check_their_arguments_before_any_launch():
         assert f(logits=odd) == ERR                                             # alignment
     assert fwd(partial=_null()) == ERR and fwd(rows=0, partial=_null()) == ERR
     assert bwd(scale=_null()) == ERR and bwd(dl=_null()) == ERR and bwd(dl=odd) == ERR
-    assert bwd(rows=0, logits=_null(), dl=_null()) == 0                         # nothing to write: success without a launch
+    assert bwd_status(rows=0, logits=_null(), dl=_null()) == 0                  # nothing to write: success without a launch
     # the contiguous entry points still want classes % 4 == 0
-    assert lib.sigma_softmax_ce_fwd(ok, ok, 8, 9, 255, ok, ok, _null()) == ERR
-    assert lib.sigma_softmax_ce_bwd(ok, ok, ok, ok, 8, 9, 255, ok, _null()) == ERR
+    assert_refused(lib.sigma_softmax_ce_fwd, ok, ok, 8, 9, 255, ok, ok, _null(), says="classes")
+    assert_refused(lib.sigma_softmax_ce_bwd, ok, ok, ok, ok, 8, 9, 255, ok, _null(), says="classes")
 
 
 _CTYPES = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}

@@ -40,6 +40,7 @@ def test_status_is_raised_by_launch_and_returned_by_call():
     with pytest.raises(RuntimeError) as e:
         _launch.launch("sigma_ohem_select", None, device=dev, what="ohem_select")      # NULL params: refused before any launch
     assert str(e.value).startswith("ohem_select:") and "sigma_status 1" in str(e.value)
+    assert "params is NULL" in str(e.value)                 # the reason of THIS refusal, from the library's error text
     assert _launch.call("sigma_ohem_select", None, device=dev) == 1
     src, acc = _operands(dev)
     want = acc + src.sum(1)

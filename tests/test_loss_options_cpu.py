@@ -13,6 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from sigma_amd import _capi
+from tests.capi_refusals import assert_refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IGNORE = 255
@@ -107,9 +108,12 @@ def _params(**kw):
 def test_entry_points_check_their_arguments_before_any_launch():
     lib = _capi.load()
     ERR = 1                                                      # SIGMA_OPS_ERR_ARG
-    fwd = lambda **kw: lib.sigma_softmax_ce_opt_fwd(ctypes.byref(_params(**kw)), None)
-    bwd = lambda **kw: lib.sigma_softmax_ce_opt_bwd(ctypes.byref(_params(**kw)), None)
-    assert lib.sigma_softmax_ce_opt_fwd(None, None) == ERR and lib.sigma_softmax_ce_opt_bwd(None, None) == ERR
+    # fwd / bwd: the status of a call that must be refused -- with a reason of its own in the error text (assert_refused)
+    fwd = lambda **kw: assert_refused(lib.sigma_softmax_ce_opt_fwd, ctypes.byref(_params(**kw)), None, code=ERR, msg=kw) and ERR
+    bwd = lambda **kw: assert_refused(lib.sigma_softmax_ce_opt_bwd, ctypes.byref(_params(**kw)), None, code=ERR, msg=kw) and ERR
+    bwd_status = lambda **kw: lib.sigma_softmax_ce_opt_bwd(ctypes.byref(_params(**kw)), None)
+    assert_refused(lib.sigma_softmax_ce_opt_fwd, None, None, says="NULL")
+    assert_refused(lib.sigma_softmax_ce_opt_bwd, None, None, says="NULL")
     for f in (fwd, bwd):
         assert f(classes=0) == ERR and f(classes=-3) == ERR                      # classes < 1
         assert f(ld=10) == ERR and f(ld=9) == ERR and f(ld=13) == ERR            # ld % 4 != 0
@@ -126,9 +130,9 @@ def test_entry_points_check_their_arguments_before_any_launch():
         assert bwd(rows=rows, scale=OK, row_grad=OK) == ERR and bwd(rows=rows, scale=None, row_grad=None) == ERR
     assert bwd(row_grad=ODD4, scale=None) == ERR and bwd(scale=ODD4) == ERR
     # nothing to write: success without a launch, with either gradient and with the optional pointers absent
-    assert bwd(rows=0, logits=None, dlogits=None, weight=None) == 0
-    assert bwd(rows=0, logits=None, dlogits=None, scale=None, row_grad=OK, label_smoothing=0.0) == 0
-    assert bwd(rows=0, label_smoothing=1.0) == 0
+    assert bwd_status(rows=0, logits=None, dlogits=None, weight=None) == 0
+    assert bwd_status(rows=0, logits=None, dlogits=None, scale=None, row_grad=OK, label_smoothing=0.0) == 0
+    assert bwd_status(rows=0, label_smoothing=1.0) == 0
 
 
 class _Sub(nn.CrossEntropyLoss):

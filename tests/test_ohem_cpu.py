@@ -21,6 +21,7 @@ import pytest
 import torch
 
 from sigma_amd import _capi
+from tests.capi_refusals import assert_refused
 from tests.ohem_fp64_twin import VARIANTS, twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -174,22 +175,22 @@ def _ohem_params(**kw):
 
 def test_select_refuses_bad_arguments_before_any_launch():
     lib = _capi.load()
-    ERR = 1                                                   # SIGMA_OPS_ERR_ARG
-    call = lambda p: lib.sigma_ohem_select(ctypes.byref(p), None)
-    assert lib.sigma_ohem_select(None, None) == ERR
+    # every refusal is SIGMA_OPS_ERR_ARG (1) with a reason of its own in the error text
+    refused = lambda p, **kw: assert_refused(lib.sigma_ohem_select, ctypes.byref(p), None, **kw)
+    assert_refused(lib.sigma_ohem_select, None, None, says="NULL")
     for field in ("nll", "labels", "mined", "tau", "counts", "workspace"):
-        assert call(_ohem_params(**{field: None})) == ERR, field
+        refused(_ohem_params(**{field: None}), says=field, msg=field)
     for field, addr in (("nll", 0x10002), ("tau", 0x40001), ("labels", 0x20004), ("mined", 0x30004), ("counts", 0x50004),
                         ("workspace", 0x60008), ("weight", 0x70002), ("row_loss", 0x80002), ("partial", 0x90002)):
-        assert call(_ohem_params(**{field: addr})) == ERR, field
+        refused(_ohem_params(**{field: addr}), says="align", msg=field)
     need = int(lib.sigma_ohem_workspace_bytes(100))
-    assert call(_ohem_params(workspace_bytes=need - 1)) == ERR
-    assert call(_ohem_params(workspace_bytes=0)) == ERR
+    refused(_ohem_params(workspace_bytes=need - 1), says="workspace")
+    refused(_ohem_params(workspace_bytes=0), says="workspace")
     for th in (0.0, -0.5, 1.0000001, float("nan"), float("inf")):
-        assert call(_ohem_params(thresh=th)) == ERR, th
-    assert call(_ohem_params(rows=-1)) == ERR
-    assert call(_ohem_params(rows=2 ** 31)) == ERR
-    assert call(_ohem_params(classes=0)) == ERR
+        refused(_ohem_params(thresh=th), says="thresh", msg=th)
+    refused(_ohem_params(rows=-1), says="rows")
+    refused(_ohem_params(rows=2 ** 31), says="rows")
+    refused(_ohem_params(classes=0), says="classes")
 
 
 def test_workspace_query():
@@ -199,7 +200,8 @@ def test_workspace_query():
         b = int(lib.sigma_ohem_workspace_bytes(rows))
         assert b > 0 and b % 16 == 0 and b >= last, (rows, b)
         last = b
-    assert int(lib.sigma_ohem_workspace_bytes(-1)) == -1 and int(lib.sigma_ohem_workspace_bytes(2 ** 31)) == -1
+    assert_refused(lib.sigma_ohem_workspace_bytes, -1, code=-1, says="rows")
+    assert_refused(lib.sigma_ohem_workspace_bytes, 2 ** 31, code=-1, says="rows")
 
 
 def test_ohem_struct_layout_matches_header(tmp_path):

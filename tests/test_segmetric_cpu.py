@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 from sigma_amd import _capi
+from tests.capi_refusals import assert_refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEG_SYMBOLS = ("sigma_seg_accumulate", "sigma_seg_argmax_confusion")
@@ -63,12 +64,12 @@ def _acc(**kw):
                          ids=lambda d: ",".join(f"{k}={v}" for k, v in d.items()))
 def test_accumulate_refuses_bad_arguments(bad):
     lib = _capi.load()
-    assert lib.sigma_seg_accumulate(ctypes.byref(_acc(**bad)), None) == ERR_ARG
+    assert_refused(lib.sigma_seg_accumulate, ctypes.byref(_acc(**bad)), None, code=ERR_ARG, says=next(iter(bad)))
 
 
 def test_accumulate_null_params_and_empty_image():
     lib = _capi.load()
-    assert lib.sigma_seg_accumulate(None, None) == ERR_ARG
+    assert_refused(lib.sigma_seg_accumulate, None, None, code=ERR_ARG, says="NULL")
     assert lib.sigma_seg_accumulate(ctypes.byref(_acc(pixels=0, score_plane_stride=0, acc_plane_stride=0)), None) == 0
 
 
@@ -99,11 +100,11 @@ def _conf(**kw):
 ], ids=lambda d: ",".join(f"{k}={v}" for k, v in d.items()))
 def test_argmax_confusion_refuses_bad_arguments(bad):
     lib = _capi.load()
-    assert lib.sigma_seg_argmax_confusion(ctypes.byref(_conf(**bad)), None) == ERR_ARG
+    assert_refused(lib.sigma_seg_argmax_confusion, ctypes.byref(_conf(**bad)), None, code=ERR_ARG, says=next(iter(bad)))
 
 
 def test_argmax_confusion_null_params_and_empty_image():
     lib = _capi.load()
-    assert lib.sigma_seg_argmax_confusion(None, None) == ERR_ARG
+    assert_refused(lib.sigma_seg_argmax_confusion, None, None, code=ERR_ARG, says="NULL")
     for kw in (dict(), dict(acc=None, classes=0), dict(gt=None, hist=None, counts=None), dict(n_cl=256, pred_elem_size=1)):
         assert lib.sigma_seg_argmax_confusion(ctypes.byref(_conf(pixels=0, **kw)), None) == 0, kw
