@@ -24,6 +24,10 @@
                    ProbOhemCrossEntropy2d -- on sigma_upsample_loss_fwd / _bwd and, for OHEM, the selection kernels in
                    between (the other kinds of ``UpsampledLossFn``).
 
+``region_loss``    a soft region-overlap loss -- Dice, Jaccard, Tversky, optionally summed with the mean cross entropy -- on the
+                   same logits: per-class sums without atomics, the coefficient table on the device, a one-pass backward
+                   (csrc/region.hip, C ABI include/sigma_region.h bound by ``_capi_region``; ``RegionLossFn``).
+
 The three front-ends share their checks (``_loss_rows``); the three Functions with options share one forward
 (``_rows_forward`` / ``_rows_finish``: buffers, parameters, saved tensors, reduction) and one backward (``_dlogits``), and
 differ in the entry point they name.
@@ -41,6 +45,7 @@ import torch.nn.functional as F
 from . import _capi
 from ._handoff import offer_padded_grad_buffer
 from ._launch import launch, ptr
+from ._launch import workspace as _workspace
 
 
 def _mlp(pooled, w1, w2, batch):
@@ -731,3 +736,74 @@ def cross_entropy_deterministic(criterion, logits: torch.Tensor, label: torch.Te
     if eps > 0.0:
         per_pixel = (1.0 - eps) * per_pixel - (eps / nc) * lsm_w.sum(dim=1)
     return _det_reduce(per_pixel * validf, wy, criterion.reduction)
+
+
+REGION_KINDS = {"dice": (0.5, 0.5), "jaccard": (1.0, 1.0)}      # (a, b) of the Tversky index; "tversky" takes its own
+REGION_MAX_CLASSES = 64      # include/sigma_region.h
+
+
+class RegionLossFn(torch.autograd.Function):
+    """The soft region-overlap loss of include/sigma_region.h on the rows of ``SoftmaxCEFn`` (csrc/region.hip):
+    region_weight * (1 - mean over the labelled classes of the Tversky index (a, b) with smoothing s) + ce_weight * the mean
+    cross entropy, the sums taken over the valid rows of this call.  Forward: sigma_region_loss_fwd -- the sums and the
+    coefficient table on the device, nothing read back; backward: sigma_region_loss_bwd, one pass, the upstream gradient as a
+    device scalar.  Returns (loss, terms, sums): the 0-dim loss, (region, cross entropy) and (3, classes) = I, P, Y; only the
+    loss carries a gradient.  No labelled pixel at all: loss 0 and a zero gradient."""
+
+    @staticmethod
+    def _params(logits2, labels, lse, coef, ignore_index, ld, a, b, s, rw, cw):
+        from ._capi_region import RegionParams
+        p = RegionParams()
+        p.rows, p.classes, p.ld, p.ignore_index = logits2.shape[0], logits2.shape[1], ld, int(ignore_index)
+        p.alpha, p.beta, p.smooth, p.region_weight, p.ce_weight = float(a), float(b), float(s), float(rw), float(cw)
+        p.logits, p.labels, p.lse, p.coef = logits2.data_ptr(), labels.data_ptr(), lse.data_ptr(), coef.data_ptr()
+        return p
+
+    @staticmethod
+    def forward(ctx, logits2, labels, ignore_index, ld, a, b, s, rw, cw):
+        from . import _capi_region
+        lib = _capi_region.load()
+        rows, nc = logits2.shape
+        dev = logits2.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        lse, coef = torch.empty(rows, **f32), torch.empty(2 * nc + 1, **f32)
+        out = torch.empty(3 + 3 * nc, **f32)                  # loss, the two terms, the sums
+        p = RegionLossFn._params(logits2, labels, lse, coef, ignore_index, ld, a, b, s, rw, cw)
+        ws = _workspace(int(lib.sigma_region_loss_workspace_bytes(ctypes.byref(p))), dev, "region_loss_workspace_bytes")
+        p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+        p.loss, p.terms, p.sums = out.data_ptr(), out[1:].data_ptr(), out[3:].data_ptr()
+        launch("sigma_region_loss_fwd", ctypes.byref(p), device=dev, what="region_loss_fwd")
+        ctx.save_for_backward(logits2, labels, lse, coef)
+        ctx.args = (int(ignore_index), ld, a, b, s, rw, cw)
+        terms, sums = out[1:3], out[3:].view(3, nc)
+        ctx.mark_non_differentiable(terms, sums)
+        return out[0], terms, sums
+
+    @staticmethod
+    def backward(ctx, g, _gt, _gs):
+        logits2, labels, lse, coef = ctx.saved_tensors
+        rows, nc = logits2.shape
+        ld = ctx.args[1]
+        scale = g.float().reshape(1).contiguous()
+        full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
+        p = RegionLossFn._params(logits2, labels, lse, coef, ctx.args[0], ld, *ctx.args[2:])
+        p.scale, p.dlogits = scale.data_ptr(), full.data_ptr()
+        launch("sigma_region_loss_bwd", ctypes.byref(p), device=logits2.device, what="region_loss_bwd")
+        return (_hand_off_padded(full, nc),) + (None,) * 8
+
+
+def region_loss(logits: torch.Tensor, label: torch.Tensor, ignore_index=255, alpha=0.5, beta=0.5, smooth=0.0, region_weight=1.0,
+                ce_weight=0.0, with_terms=False):
+    """The region-overlap loss (``RegionLossFn``: Tversky index (alpha, beta); Dice = (0.5, 0.5), Jaccard = (1, 1)) on the
+    channels-last logits ``cross_entropy`` takes (same layouts, same treatment of labels outside [0, classes)), or None
+    when this path does not apply: another layout, dtype or device, more than 64 classes, beta <= 0, or a negative alpha,
+    smooth or weight.  `with_terms`: (loss, terms, sums) instead of the loss."""
+    a, b, s, rw, cw = float(alpha), float(beta), float(smooth), float(region_weight), float(ce_weight)
+    if logits.dim() != 4 or not 1 <= logits.shape[1] <= REGION_MAX_CLASSES or not (b > 0.0 and a >= 0.0 and s >= 0.0 and rw >= 0.0 and cw >= 0.0):
+        return None
+    args = _loss_rows(logits, label, None)
+    if args is None:
+        return None
+    logits2, lab, _, ld = args
+    out = RegionLossFn.apply(logits2, lab, int(ignore_index), ld, a, b, s, rw, cw)
+    return out if with_terms else out[0]

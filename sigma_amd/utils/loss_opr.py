@@ -17,6 +17,10 @@ pixels, 1 elsewhere):
 reads it: its exponent is the literal 2.  Here ``exponent=None`` keeps that, a float ``exponent`` selects another one; on
 the classifier's channels-last logits the loss runs on sigma_softmax_focal_fwd / _bwd (``pointwise.focal_cross_entropy``)
 for e = 0 or e >= 1, anything else -- 0 < e < 1 included -- takes the torch formulation.
+
+``RegionLoss2d`` is NOT one of the reference's criteria: a soft region-overlap loss (Dice, Jaccard, Tversky), optionally summed
+with the mean cross entropy, for the same background-dominated datasets; on the classifier's channels-last logits it runs on
+the kernels of csrc/region.hip (``pointwise.region_loss``, up to 64 classes), anything else takes its torch formulation.
 """
 from __future__ import annotations
 
@@ -105,3 +109,74 @@ class ProbOhemCrossEntropy2d(nn.Module):
             if loss is not None:
                 return loss
         return self.criterion(pred, mined)
+
+
+class RegionLoss2d(nn.Module):
+    """A soft region-overlap loss, a criterion of the project's own (the reference has none): the overlap score the
+    evaluator reports, made differentiable.  With p = softmax(input) and sums over the valid pixels of the batch (valid:
+    target != ignore_index and inside [0, classes)):
+
+        I_c = sum p_c [y = c]    P_c = sum p_c    Y_c = sum [y = c]
+        T_c = (I_c + s) / ((1 - a - b) I_c + a P_c + b Y_c + s)              the Tversky index of class c
+        region = mean over the classes with Y_c > 0 of 1 - T_c               (0 when nothing is labelled)
+        loss = region_weight * region + ce_weight * mean cross entropy       (CE term 0 when nothing is labelled)
+
+    ``kind``: "dice" (a = b = 0.5), "jaccard" (a = b = 1) or "tversky" (``alpha`` = a >= 0 weighs false positives, ``beta`` =
+    b > 0 false negatives; both required, and rejected for the other two).  ``smooth`` = s >= 0.  On the channels-last
+    logits of the classifier the loss runs on the kernels of csrc/region.hip (``pointwise.region_loss``, up to 64 classes)
+    and ``last_terms`` then holds the device tensor (region, cross entropy) of that forward; anything else -- CPU tensors,
+    other layouts, more classes -- takes ``torch_formulation``, element-wise ops and fixed-order sums only (one-hot by
+    comparison), which is therefore also what runs under the deterministic flag.  Under DistributedDataParallel the sums
+    are per rank: each rank's loss is the overlap on its own pixels."""
+
+    def __init__(self, kind="dice", ignore_index=255, smooth=0.0, alpha=None, beta=None, ce_weight=0.0, region_weight=1.0):
+        super().__init__()
+        from ..pointwise import REGION_KINDS
+        if kind == "tversky":
+            if alpha is None or beta is None:
+                raise ValueError("RegionLoss2d: kind 'tversky' needs alpha and beta")
+            self.alpha, self.beta = float(alpha), float(beta)
+            if not self.alpha >= 0.0:
+                raise ValueError(f"RegionLoss2d: alpha {alpha!r} is negative or NaN")
+            if not self.beta > 0.0:
+                raise ValueError(f"RegionLoss2d: beta {beta!r} is not positive")
+        elif kind in REGION_KINDS:
+            if alpha is not None or beta is not None:
+                raise ValueError(f"RegionLoss2d: kind {kind!r} fixes alpha and beta; pass them with kind='tversky'")
+            self.alpha, self.beta = REGION_KINDS[kind]
+        else:
+            raise ValueError(f"RegionLoss2d: kind {kind!r} is not one of 'dice', 'jaccard', 'tversky'")
+        self.kind = kind
+        self.ignore_index = int(ignore_index)
+        self.smooth, self.ce_weight, self.region_weight = float(smooth), float(ce_weight), float(region_weight)
+        for name in ("smooth", "ce_weight", "region_weight"):
+            if not getattr(self, name) >= 0.0:
+                raise ValueError(f"RegionLoss2d: {name} {getattr(self, name)!r} is negative or NaN")
+        self.last_terms = None
+
+    def torch_formulation(self, input, target):
+        nc = input.shape[1]
+        lab = target.long()
+        valid = ((lab != self.ignore_index) & (lab >= 0) & (lab < nc)).unsqueeze(1)
+        hit = (lab.unsqueeze(1) == torch.arange(nc, device=input.device).view(1, nc, 1, 1)) & valid
+        onehot, validf = hit.to(input.dtype), valid.to(input.dtype)
+        lsm = F.log_softmax(input, dim=1)
+        p = lsm.exp()
+        I, P, Y = (p * onehot).sum(dim=(0, 2, 3)), (p * validf).sum(dim=(0, 2, 3)), onehot.sum(dim=(0, 2, 3))
+        a, b, s = self.alpha, self.beta, self.smooth
+        present = Y > 0
+        D = torch.where(present, (1.0 - a - b) * I + a * P + b * Y + s, torch.ones_like(I))
+        miss = torch.where(present, 1.0 - (I + s) / D, torch.zeros_like(I))
+        region = miss.sum() / present.sum().clamp_min(1)
+        nll = -torch.where(hit, lsm, torch.zeros_like(lsm)).sum()
+        return self.region_weight * region + self.ce_weight * (nll / validf.sum().clamp_min(1.0))
+
+    def forward(self, input, target):
+        from ..pointwise import region_loss
+        if input.is_cuda:
+            out = region_loss(input, target, self.ignore_index, self.alpha, self.beta, self.smooth, self.region_weight,
+                              self.ce_weight, with_terms=True)
+            if out is not None:
+                self.last_terms = out[1]
+                return out[0]
+        return self.torch_formulation(input, target)

@@ -70,7 +70,16 @@ between two device events) at 8 x 480 x 640 rows for (classes, pitch) = (68, 68)
 takes (above 64 classes), and (40, 40), a register row, as the control.  One line per shape with the median and spread and
 the bytes the launch moves; ``--tag`` names the build the line belongs to (the library is chosen by SIGMA_HIP_LIB), so that
 two builds can alternate process by process in one session.
-"""
+
+    python tools/head_bench.py --region --out profiles/region_loss_mi355x.jsonl
+
+``--region`` times the region-overlap loss (csrc/region.hip) at 8 x 480 x 640 rows for (classes, pitch) = (40, 40) and
+(9, 12), every launch through the C ABI between two device events, the routes alternating in one process:
+region_fwd / region_bwd   sigma_region_loss_fwd (the sums and the coefficient kernel) and sigma_region_loss_bwd, Dice + CE;
+ce_fwd / ce_bwd           sigma_softmax_ce_opt_fwd / _bwd on the same buffers: the yardstick, because they move the same
+                          bytes -- logits and labels in, lse out; logits, labels and lse in, dlogits out;
+and, forward + backward through autograd, ``RegionLoss2d`` on the kernels (function) and its torch formulation (torch).
+The line reports the ratios to the cross-entropy pair; a backward above 1.25 is a finding to explain, not a failure."""
 import argparse
 import json
 import os
@@ -397,6 +406,79 @@ def loss_fwd_main(a, dev):
     return lines
 
 
+def region_main(a, dev):
+    import ctypes
+    from sigma_amd import _capi, _capi_region
+    from sigma_amd.utils.loss_opr import RegionLoss2d
+    lib = _capi_region.load()
+    st = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lines = []
+    for B, H, W, nc, ld in OHEM_SHAPES:
+        rows = B * H * W
+        g = torch.Generator().manual_seed(1234)
+        buf = torch.zeros(rows, ld)
+        buf[:, :nc] = torch.randn(rows, nc, generator=g) * 3.0
+        label = torch.randint(0, nc, (rows,), generator=g)
+        label[torch.rand(rows, generator=g) < 0.1] = IGNORE
+        buf, label = buf.to(dev), label.to(dev)
+        f32 = dict(device=dev, dtype=torch.float32)
+        lse, dl, scale = torch.empty(rows, **f32), torch.empty(rows, ld, **f32), torch.ones(1, **f32)
+        out, coef = torch.empty(3 + 3 * nc, **f32), torch.empty(2 * nc + 1, **f32)
+        r = _capi_region.RegionParams()
+        r.rows, r.classes, r.ld, r.ignore_index = rows, nc, ld, IGNORE
+        r.alpha, r.beta, r.smooth, r.region_weight, r.ce_weight = 0.5, 0.5, 1.0, 1.0, 1.0
+        r.logits, r.labels, r.lse, r.coef = buf.data_ptr(), label.data_ptr(), lse.data_ptr(), coef.data_ptr()
+        ws = torch.empty(int(lib.sigma_region_loss_workspace_bytes(ctypes.byref(r))), device=dev, dtype=torch.uint8)
+        r.workspace, r.workspace_bytes = ws.data_ptr(), ws.numel()
+        r.loss, r.terms, r.sums = out.data_ptr(), out[1:].data_ptr(), out[3:].data_ptr()
+        r.scale, r.dlogits = scale.data_ptr(), dl.data_ptr()
+        partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, **f32)
+        c = _capi.CeOptParams()
+        c.rows, c.classes, c.ld, c.ignore_index = rows, nc, ld, IGNORE
+        c.logits, c.labels, c.lse, c.partial = buf.data_ptr(), label.data_ptr(), lse.data_ptr(), partial.data_ptr()
+        c.scale, c.dlogits = scale.data_ptr(), dl.data_ptr()
+        launches = {"region_fwd": lambda: lib.sigma_region_loss_fwd(ctypes.byref(r), st()),
+                    "ce_fwd": lambda: lib.sigma_softmax_ce_opt_fwd(ctypes.byref(c), st()),
+                    "region_bwd": lambda: lib.sigma_region_loss_bwd(ctypes.byref(r), st()),
+                    "ce_bwd": lambda: lib.sigma_softmax_ce_opt_bwd(ctypes.byref(c), st())}
+        crit = RegionLoss2d("dice", ignore_index=IGNORE, smooth=1.0, ce_weight=1.0)
+        leaf = buf.view(B, H, W, ld).requires_grad_()
+        view = lambda: leaf[..., :nc].permute(0, 3, 1, 2)
+        label3 = label.view(B, H, W)
+        routes = {"function": lambda: crit(view(), label3), "torch": lambda: crit.torch_formulation(view(), label3)}
+        times = {k: [] for k in (*launches, *routes)}
+        losses = {}
+        for i in range(a.warmup + a.reps):
+            for k in times:
+                leaf.grad = None
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                if k in launches:
+                    _capi.check(launches[k](), k)
+                else:
+                    loss = routes[k]()
+                    loss.backward()
+                    losses[k] = loss.detach()
+                t1.record()
+                t1.synchronize()
+                if i >= a.warmup:
+                    times[k].append(t0.elapsed_time(t1))
+        assert crit.last_terms is not None
+        sp = {k: spread(v) for k, v in times.items()}
+        med = lambda k: sp[k]["median_ms"]
+        line = {"mode": "region", "rows": rows, "classes": nc, "ld": ld, "kind": "dice", "ce_weight": 1.0, "reps": a.reps, "warmup": a.warmup,
+                **sp, "fwd_over_ce": round(med("region_fwd") / med("ce_fwd"), 4), "bwd_over_ce": round(med("region_bwd") / med("ce_bwd"), 4),
+                "bwd_above_1p25": med("region_bwd") > 1.25 * med("ce_bwd"),
+                "function_over_torch": round(med("function") / med("torch"), 4),
+                "fwd_bytes": rows * (4 * ld + 8 + 4), "bwd_bytes": rows * (8 * ld + 8 + 4),
+                "loss_function": float(losses["function"]), "loss_torch": float(losses["torch"]), "device": torch.cuda.get_device_name(0)}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del buf, label, lse, dl, leaf, ws
+        torch.cuda.empty_cache()
+    return lines
+
+
 def spread(ts):
     q = statistics.quantiles(ts, n=4)
     return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4),
@@ -414,6 +496,7 @@ def main():
     ap.add_argument("--focal", action="store_true", help="time the focal loss against the plain loss and the torch formulation")
     ap.add_argument("--deepsup", action="store_true", help="time the fused upsample + loss of a deep-supervision head against the expansion")
     ap.add_argument("--loss-fwd", action="store_true", help="time the forward loss kernel alone at 68, 65 and 40 classes")
+    ap.add_argument("--region", action="store_true", help="time the region-overlap loss against the cross-entropy kernels and its torch formulation")
     ap.add_argument("--tag", default="tree", help="--loss-fwd: the name of the build the lines belong to")
     ap.add_argument("--run", type=int, default=None, help="--deepsup / --loss-fwd: tag every line with this run number (one process per run)")
     ap.add_argument("--append", action="store_true", help="--deepsup / --loss-fwd: add the lines to --out instead of replacing it")
@@ -421,8 +504,8 @@ def main():
     if a.reps < 30:
         ap.error("at least 30 repetitions")
     dev = torch.device("cuda", 0)
-    if a.ohem or a.focal or a.deepsup or a.loss_fwd:
-        lines = ohem_main(a, dev) if a.ohem else focal_main(a, dev) if a.focal else deepsup_main(a, dev) if a.deepsup else loss_fwd_main(a, dev)
+    if a.ohem or a.focal or a.deepsup or a.loss_fwd or a.region:
+        lines = region_main(a, dev) if a.region else ohem_main(a, dev) if a.ohem else focal_main(a, dev) if a.focal else deepsup_main(a, dev) if a.deepsup else loss_fwd_main(a, dev)
         if a.out:
             with open(a.out, "a" if (a.deepsup or a.loss_fwd) and a.append else "w") as f:
                 for line in lines:
