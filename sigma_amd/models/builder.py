@@ -141,7 +141,37 @@ class EncoderDecoder(nn.Module):
             loss = loss + (term if term is not None else self._loss(expand_logits(z, s), label))
         return loss
 
+    def attach_teacher(self, teacher, criterion):
+        """Distillation: from here on ``forward(rgb, modal_x, label)`` returns ``criterion(student logits, label, teacher
+        logits)`` (a ``DistillLoss2d``) with the teacher run under no_grad on the same batch; ``self.criterion`` is not used on
+        that path and nothing else changes.  The teacher -- an ``EncoderDecoder`` of the same class count on the same device --
+        is put in eval(), its parameters are frozen, and it is held UNREGISTERED: it is not in parameters(), state_dict() or
+        modules(), and train() and to() do not touch it, so optimizers, checkpoints and DDP see the student alone."""
+        if getattr(self, "deep_supervision", False):
+            raise ValueError("attach_teacher: a student with deep_supervision is not supported (there is no fused upsample + "
+                             "distillation loss for the auxiliary heads)")
+        nc, nc_t = self.decode_head.num_classes, teacher.decode_head.num_classes
+        if nc_t != nc:
+            raise ValueError(f"attach_teacher: the teacher has {nc_t} classes, the student {nc}")
+        dev, dev_t = next(self.parameters()).device, next(teacher.parameters()).device
+        if dev_t != dev:
+            raise ValueError(f"attach_teacher: the teacher is on {dev_t}, the student on {dev}")
+        teacher.eval()
+        teacher.requires_grad_(False)
+        self._distill = (teacher, criterion)           # a tuple: nn.Module registers nothing inside it
+
+    def detach_teacher(self):
+        """forward is again what it was before ``attach_teacher``"""
+        self._distill = None
+
     def forward(self, rgb, modal_x, label=None):
+        distill = getattr(self, "_distill", None)
+        if distill is not None and label is not None:
+            teacher, criterion = distill
+            with torch.no_grad():
+                # the logits as the classifier lays them out (channels-last rows): forward() would re-lay them as (B, nc, H, W)
+                t = teacher(rgb, modal_x) if getattr(teacher, "deep_supervision", False) else teacher.encode_decode(rgb, modal_x)
+            return criterion(self.encode_decode(rgb, modal_x), label, t)
         if getattr(self, "deep_supervision", False):
             return self._forward_deep(rgb, modal_x, label)
         out = self.encode_decode(rgb, modal_x)

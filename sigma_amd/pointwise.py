@@ -28,6 +28,11 @@
                    same logits: per-class sums without atomics, the coefficient table on the device, a one-pass backward
                    (csrc/region.hip, C ABI include/sigma_region.h bound by ``_capi_region``; ``RegionLossFn``).
 
+``distill_loss``   the distillation loss against a frozen teacher's logits of the same layout (either pitch each): the KL
+                   divergence at a temperature, optionally summed with the mean cross entropy; both rows in registers, sums
+                   without atomics, the two scale factors on the device, a one-pass backward (csrc/distill.hip, C ABI
+                   include/sigma_distill.h bound by ``_capi_distill``; ``DistillLossFn``).  The teacher gets no gradient.
+
 The three front-ends share their checks (``_loss_rows``); the three Functions with options share one forward
 (``_rows_forward`` / ``_rows_finish``: buffers, parameters, saved tensors, reduction) and one backward (``_dlogits``), and
 differ in the entry point they name.
@@ -806,4 +811,84 @@ def region_loss(logits: torch.Tensor, label: torch.Tensor, ignore_index=255, alp
         return None
     logits2, lab, _, ld = args
     out = RegionLossFn.apply(logits2, lab, int(ignore_index), ld, a, b, s, rw, cw)
+    return out if with_terms else out[0]
+
+
+DISTILL_MAX_CLASSES = 64      # include/sigma_distill.h
+
+
+class DistillLossFn(torch.autograd.Function):
+    """The distillation loss of include/sigma_distill.h on the rows of ``SoftmaxCEFn`` (csrc/distill.hip), student rows
+    logits2 at the pitch `ld` and teacher rows teacher2 at `ld_t`: kd_weight * T^2 * mean over the set S of
+    KL(softmax(t / T) || softmax(x / T)) + ce_weight * the mean cross entropy; S = the valid rows, or every row with `kd_all`.
+    Forward: sigma_distill_loss_fwd -- the sums and both scale factors on the device, nothing read back; backward:
+    sigma_distill_loss_bwd, one pass, the upstream gradient as a device scalar.  Returns (loss, terms): the 0-dim loss and
+    (kd, cross entropy), both unweighted; only the loss carries a gradient, and only to the student's logits.  An empty S:
+    KD term 0; no valid row: CE term 0; both: a zero gradient."""
+
+    @staticmethod
+    def _params(logits2, teacher2, labels, lse, coef, ignore_index, ld, ld_t, T, kw, cw, kd_all):
+        from ._capi_distill import DistillParams
+        p = DistillParams()
+        p.rows, p.classes, p.ld, p.ld_t = logits2.shape[0], logits2.shape[1], ld, ld_t
+        p.kd_all, p.ignore_index = int(bool(kd_all)), int(ignore_index)
+        p.temperature, p.kd_weight, p.ce_weight = float(T), float(kw), float(cw)
+        p.logits, p.teacher, p.labels = logits2.data_ptr(), teacher2.data_ptr(), labels.data_ptr()
+        p.lse, p.coef = lse.data_ptr(), coef.data_ptr()
+        return p
+
+    @staticmethod
+    def forward(ctx, logits2, teacher2, labels, ignore_index, ld, ld_t, T, kw, cw, kd_all):
+        from . import _capi_distill
+        lib = _capi_distill.load()
+        rows, nc = logits2.shape
+        dev = logits2.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        lse, coef = torch.empty(rows, 3, **f32), torch.empty(2, **f32)
+        out = torch.empty(3, **f32)                           # loss, the two terms
+        p = DistillLossFn._params(logits2, teacher2, labels, lse, coef, ignore_index, ld, ld_t, T, kw, cw, kd_all)
+        ws = _workspace(int(lib.sigma_distill_loss_workspace_bytes(ctypes.byref(p))), dev, "distill_loss_workspace_bytes")
+        p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+        p.loss, p.terms = out.data_ptr(), out[1:].data_ptr()
+        launch("sigma_distill_loss_fwd", ctypes.byref(p), device=dev, what="distill_loss_fwd")
+        ctx.save_for_backward(logits2, teacher2, labels, lse, coef)
+        ctx.args = (int(ignore_index), ld, ld_t, T, kw, cw, kd_all)
+        terms = out[1:3]
+        ctx.mark_non_differentiable(terms)
+        return out[0], terms
+
+    @staticmethod
+    def backward(ctx, g, _gt):
+        logits2, teacher2, labels, lse, coef = ctx.saved_tensors
+        rows, nc = logits2.shape
+        ld = ctx.args[1]
+        scale = g.float().reshape(1).contiguous()
+        full = torch.empty((rows, ld), device=logits2.device, dtype=torch.float32)
+        p = DistillLossFn._params(logits2, teacher2, labels, lse, coef, *ctx.args)
+        p.scale, p.dlogits = scale.data_ptr(), full.data_ptr()
+        launch("sigma_distill_loss_bwd", ctypes.byref(p), device=logits2.device, what="distill_loss_bwd")
+        return (_hand_off_padded(full, nc),) + (None,) * 9
+
+
+def distill_loss(logits: torch.Tensor, teacher_logits: torch.Tensor, label: torch.Tensor, ignore_index=255, temperature=1.0,
+                 kd_weight=1.0, ce_weight=0.0, kd_all=False, with_terms=False):
+    """The distillation loss (``DistillLossFn``) on the channels-last logits ``cross_entropy`` takes, student and teacher each
+    at its own pitch (same layouts, same treatment of labels outside [0, classes)), or None when this path does not apply:
+    either tensor of another layout, dtype or device, shapes that disagree, more than 64 classes, a temperature that is not
+    positive or a negative weight.  The teacher's logits are read as they are and get no gradient.  `with_terms`: (loss,
+    terms) instead of the loss."""
+    T, kw, cw = float(temperature), float(kd_weight), float(ce_weight)
+    if logits.dim() != 4 or tuple(teacher_logits.shape) != tuple(logits.shape) or not 1 <= logits.shape[1] <= DISTILL_MAX_CLASSES:
+        return None
+    if not (T > 0.0 and kw >= 0.0 and cw >= 0.0):
+        return None
+    args = _loss_rows(logits, label, None)
+    if args is None or teacher_logits.device != logits.device:
+        return None
+    teacher = _channels_last_rows(teacher_logits.detach(), label)
+    if teacher is None:
+        return None
+    logits2, lab, _, ld = args
+    nhwc_t, nc, ld_t = teacher
+    out = DistillLossFn.apply(logits2, nhwc_t.reshape(-1, nc), lab, int(ignore_index), ld, ld_t, T, kw, cw, bool(kd_all))
     return out if with_terms else out[0]

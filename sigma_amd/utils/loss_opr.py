@@ -21,6 +21,11 @@ for e = 0 or e >= 1, anything else -- 0 < e < 1 included -- takes the torch form
 ``RegionLoss2d`` is NOT one of the reference's criteria: a soft region-overlap loss (Dice, Jaccard, Tversky), optionally summed
 with the mean cross entropy, for the same background-dominated datasets; on the classifier's channels-last logits it runs on
 the kernels of csrc/region.hip (``pointwise.region_loss``, up to 64 classes), anything else takes its torch formulation.
+
+``DistillLoss2d`` is not one of the reference's criteria either: the loss of a student against a frozen teacher's logits (KL
+at a temperature, optionally summed with the mean cross entropy), ``forward(input, target, teacher_logits)``; on the
+classifier's channels-last logits it runs on the kernels of csrc/distill.hip (``pointwise.distill_loss``, up to 64 classes),
+anything else takes its torch formulation.  ``EncoderDecoder.attach_teacher`` is what calls it with three arguments.
 """
 from __future__ import annotations
 
@@ -180,3 +185,61 @@ class RegionLoss2d(nn.Module):
                 self.last_terms = out[1]
                 return out[0]
         return self.torch_formulation(input, target)
+
+
+class DistillLoss2d(nn.Module):
+    """The distillation loss, a criterion of the project's own (the reference has none): the student's logits `input` held to
+    a frozen teacher's `teacher_logits` of the same shape.  With T = temperature, p = softmax(input / T), q = softmax(teacher
+    / T), valid pixels as everywhere (target != ignore_index and inside [0, classes)) and S = the valid pixels, or every
+    pixel with ``kd_all``:
+
+        kd   = T^2 * mean over S of sum_c [q_c > 0] q_c (log q_c - log p_c)     (0 when S is empty)
+        ce   = mean over the valid pixels of the cross entropy of input          (0 when nothing is labelled)
+        loss = kd_weight * kd + ce_weight * ce
+
+    The teacher gets no gradient.  On the channels-last logits of the classifier (either pitch for either tensor) the loss
+    runs on the kernels of csrc/distill.hip (``pointwise.distill_loss``, up to 64 classes) and ``last_terms`` then holds the
+    device tensor (kd, ce) of that forward; anything else -- CPU tensors, other layouts, more classes -- takes
+    ``torch_formulation``, element-wise ops and fixed-order sums only (one-hot by comparison), which is therefore also what
+    runs under the deterministic flag."""
+
+    def __init__(self, temperature=1.0, kd_weight=1.0, ce_weight=0.0, ignore_index=255, kd_all=False):
+        super().__init__()
+        self.temperature, self.kd_weight, self.ce_weight = float(temperature), float(kd_weight), float(ce_weight)
+        if not (self.temperature > 0.0 and self.temperature != float("inf")):
+            raise ValueError(f"DistillLoss2d: temperature {temperature!r} is not a positive number")
+        for name in ("kd_weight", "ce_weight"):
+            if not getattr(self, name) >= 0.0:
+                raise ValueError(f"DistillLoss2d: {name} {getattr(self, name)!r} is negative or NaN")
+        self.ignore_index = int(ignore_index)
+        self.kd_all = bool(kd_all)
+        self.last_terms = None
+
+    def torch_formulation(self, input, target, teacher_logits):
+        nc = input.shape[1]
+        lab = target.long()
+        valid = ((lab != self.ignore_index) & (lab >= 0) & (lab < nc)).unsqueeze(1)
+        hit = (lab.unsqueeze(1) == torch.arange(nc, device=input.device).view(1, nc, 1, 1)) & valid
+        T = self.temperature
+        teacher = teacher_logits.detach().to(input.dtype)
+        lp, lq = F.log_softmax(input / T, dim=1), F.log_softmax(teacher / T, dim=1)
+        q = lq.exp()
+        kl = torch.where(q > 0, q * (lq - lp), torch.zeros_like(q))
+        if self.kd_all:
+            kd = kl.sum() / max(kl.numel() // nc, 1)
+        else:
+            kd = torch.where(valid, kl, torch.zeros_like(kl)).sum() / valid.to(input.dtype).sum().clamp_min(1.0)
+        lsm = F.log_softmax(input, dim=1)
+        nll = -torch.where(hit, lsm, torch.zeros_like(lsm)).sum()
+        ce = nll / valid.to(input.dtype).sum().clamp_min(1.0)
+        return self.kd_weight * (T * T) * kd + self.ce_weight * ce
+
+    def forward(self, input, target, teacher_logits):
+        from ..pointwise import distill_loss
+        if input.is_cuda:
+            out = distill_loss(input, teacher_logits, target, self.ignore_index, self.temperature, self.kd_weight, self.ce_weight,
+                               self.kd_all, with_terms=True)
+            if out is not None:
+                self.last_terms = out[1]
+                return out[0]
+        return self.torch_formulation(input, target, teacher_logits)

@@ -79,7 +79,19 @@ region_fwd / region_bwd   sigma_region_loss_fwd (the sums and the coefficient ke
 ce_fwd / ce_bwd           sigma_softmax_ce_opt_fwd / _bwd on the same buffers: the yardstick, because they move the same
                           bytes -- logits and labels in, lse out; logits, labels and lse in, dlogits out;
 and, forward + backward through autograd, ``RegionLoss2d`` on the kernels (function) and its torch formulation (torch).
-The line reports the ratios to the cross-entropy pair; a backward above 1.25 is a finding to explain, not a failure."""
+The line reports the ratios to the cross-entropy pair; a backward above 1.25 is a finding to explain, not a failure.
+
+    python tools/head_bench.py --distill --out profiles/distill_mi355x.jsonl
+
+``--distill`` times the distillation loss (csrc/distill.hip) at the same rows and shapes, teacher and student at the same
+pitch, T = 2, kd_all (every row in the KD term, which is what the torch composition below computes), the routes alternating in
+one process:
+distill_fwd / distill_bwd   sigma_distill_loss_fwd (the sums and the coefficient kernel) and sigma_distill_loss_bwd, KD + CE;
+ce_fwd / ce_bwd             sigma_softmax_ce_opt_fwd / _bwd on the student's buffers: the yardstick.  The distillation launches
+                            read a second row per pixel: about 2 x the bytes forward and 1.5 x backward;
+and, forward + backward through autograd, ``DistillLoss2d`` on the kernels (function) and the torch composition
+F.kl_div(log_softmax(x / T), softmax(t / T), "batchmean") T^2 + F.cross_entropy (torch).  The line reports each time ratio
+beside its byte ratio; a time ratio above 1.3 x its byte ratio is a finding to explain, not a failure."""
 import argparse
 import json
 import os
@@ -479,6 +491,95 @@ def region_main(a, dev):
     return lines
 
 
+def distill_main(a, dev):
+    import ctypes
+    import torch.nn.functional as F
+    from sigma_amd import _capi, _capi_distill
+    from sigma_amd.utils.loss_opr import DistillLoss2d
+    lib = _capi_distill.load()
+    st = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    T, kw, cw = 2.0, 1.0, 1.0
+    lines = []
+    for B, H, W, nc, ld in OHEM_SHAPES:
+        rows = B * H * W
+        g = torch.Generator().manual_seed(1234)
+        buf, tbuf = torch.zeros(rows, ld), torch.zeros(rows, ld)
+        buf[:, :nc] = torch.randn(rows, nc, generator=g) * 3.0
+        tbuf[:, :nc] = 0.7 * buf[:, :nc] + torch.randn(rows, nc, generator=g) * 2.0
+        label = torch.randint(0, nc, (rows,), generator=g)
+        label[torch.rand(rows, generator=g) < 0.1] = IGNORE
+        buf, tbuf, label = buf.to(dev), tbuf.to(dev), label.to(dev)
+        f32 = dict(device=dev, dtype=torch.float32)
+        lse, lse3, dl, scale = torch.empty(rows, **f32), torch.empty(rows, 3, **f32), torch.empty(rows, ld, **f32), torch.ones(1, **f32)
+        out, coef = torch.empty(3, **f32), torch.empty(2, **f32)
+        d = _capi_distill.DistillParams()
+        d.rows, d.classes, d.ld, d.ld_t, d.kd_all, d.ignore_index = rows, nc, ld, ld, 1, IGNORE
+        d.temperature, d.kd_weight, d.ce_weight = T, kw, cw
+        d.logits, d.teacher, d.labels, d.lse, d.coef = buf.data_ptr(), tbuf.data_ptr(), label.data_ptr(), lse3.data_ptr(), coef.data_ptr()
+        ws = torch.empty(int(lib.sigma_distill_loss_workspace_bytes(ctypes.byref(d))), device=dev, dtype=torch.uint8)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+        d.loss, d.terms = out.data_ptr(), out[1:].data_ptr()
+        d.scale, d.dlogits = scale.data_ptr(), dl.data_ptr()
+        partial = torch.empty(_capi.SIGMA_CE_BLOCKS, 2, **f32)
+        c = _capi.CeOptParams()
+        c.rows, c.classes, c.ld, c.ignore_index = rows, nc, ld, IGNORE
+        c.logits, c.labels, c.lse, c.partial = buf.data_ptr(), label.data_ptr(), lse.data_ptr(), partial.data_ptr()
+        c.scale, c.dlogits = scale.data_ptr(), dl.data_ptr()
+        launches = {"distill_fwd": lambda: lib.sigma_distill_loss_fwd(ctypes.byref(d), st()),
+                    "ce_fwd": lambda: lib.sigma_softmax_ce_opt_fwd(ctypes.byref(c), st()),
+                    "distill_bwd": lambda: lib.sigma_distill_loss_bwd(ctypes.byref(d), st()),
+                    "ce_bwd": lambda: lib.sigma_softmax_ce_opt_bwd(ctypes.byref(c), st())}
+        crit = DistillLoss2d(T, kw, cw, ignore_index=IGNORE, kd_all=True)
+        leaf = buf.view(B, H, W, ld).requires_grad_()
+        view = lambda: leaf[..., :nc].permute(0, 3, 1, 2)
+        tview = tbuf.view(B, H, W, ld)[..., :nc].permute(0, 3, 1, 2)
+        label3 = label.view(B, H, W)
+
+        def composition():
+            x2, t2 = leaf[..., :nc].reshape(-1, nc), tbuf.view(B, H, W, ld)[..., :nc].reshape(-1, nc)
+            kd = F.kl_div(F.log_softmax(x2 / T, dim=1), F.softmax(t2 / T, dim=1), reduction="batchmean") * (T * T)
+            return kw * kd + cw * F.cross_entropy(x2, label, ignore_index=IGNORE)
+
+        routes = {"function": lambda: crit(view(), label3, tview), "torch": composition}
+        times = {k: [] for k in (*launches, *routes)}
+        losses = {}
+        for i in range(a.warmup + a.reps):
+            for k in times:
+                leaf.grad = None
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                if k in launches:
+                    _capi.check(launches[k](), k)
+                else:
+                    loss = routes[k]()
+                    loss.backward()
+                    losses[k] = loss.detach()
+                t1.record()
+                t1.synchronize()
+                if i >= a.warmup:
+                    times[k].append(t0.elapsed_time(t1))
+        assert crit.last_terms is not None
+        sp = {k: spread(v) for k, v in times.items()}
+        med = lambda k: sp[k]["median_ms"]
+        by = dict(distill_fwd=rows * (8 * ld + 8 + 12), ce_fwd=rows * (4 * ld + 8 + 4), distill_bwd=rows * (12 * ld + 8 + 12),
+                  ce_bwd=rows * (8 * ld + 8 + 4))
+        fwd_t, bwd_t = med("distill_fwd") / med("ce_fwd"), med("distill_bwd") / med("ce_bwd")
+        fwd_b, bwd_b = by["distill_fwd"] / by["ce_fwd"], by["distill_bwd"] / by["ce_bwd"]
+        line = {"mode": "distill", "rows": rows, "classes": nc, "ld": ld, "ld_t": ld, "temperature": T, "kd_all": True, "ce_weight": cw,
+                "reps": a.reps, "warmup": a.warmup, **sp,
+                "fwd_over_ce": round(fwd_t, 4), "fwd_bytes_over_ce": round(fwd_b, 4), "fwd_above_1p3_bytes": fwd_t > 1.3 * fwd_b,
+                "bwd_over_ce": round(bwd_t, 4), "bwd_bytes_over_ce": round(bwd_b, 4), "bwd_above_1p3_bytes": bwd_t > 1.3 * bwd_b,
+                "torch_over_function": round(med("torch") / med("function"), 4), **{k + "_bytes": v for k, v in by.items()},
+                "fwd_tb_per_s": round(by["distill_fwd"] / med("distill_fwd") / 1e9, 3),
+                "bwd_tb_per_s": round(by["distill_bwd"] / med("distill_bwd") / 1e9, 3),
+                "loss_function": float(losses["function"]), "loss_torch": float(losses["torch"]), "device": torch.cuda.get_device_name(0)}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del buf, tbuf, label, lse, lse3, dl, leaf, ws
+        torch.cuda.empty_cache()
+    return lines
+
+
 def spread(ts):
     q = statistics.quantiles(ts, n=4)
     return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4),
@@ -497,6 +598,7 @@ def main():
     ap.add_argument("--deepsup", action="store_true", help="time the fused upsample + loss of a deep-supervision head against the expansion")
     ap.add_argument("--loss-fwd", action="store_true", help="time the forward loss kernel alone at 68, 65 and 40 classes")
     ap.add_argument("--region", action="store_true", help="time the region-overlap loss against the cross-entropy kernels and its torch formulation")
+    ap.add_argument("--distill", action="store_true", help="time the distillation loss against the cross-entropy kernels and the torch composition")
     ap.add_argument("--tag", default="tree", help="--loss-fwd: the name of the build the lines belong to")
     ap.add_argument("--run", type=int, default=None, help="--deepsup / --loss-fwd: tag every line with this run number (one process per run)")
     ap.add_argument("--append", action="store_true", help="--deepsup / --loss-fwd: add the lines to --out instead of replacing it")
@@ -504,8 +606,8 @@ def main():
     if a.reps < 30:
         ap.error("at least 30 repetitions")
     dev = torch.device("cuda", 0)
-    if a.ohem or a.focal or a.deepsup or a.loss_fwd or a.region:
-        lines = region_main(a, dev) if a.region else ohem_main(a, dev) if a.ohem else focal_main(a, dev) if a.focal else deepsup_main(a, dev) if a.deepsup else loss_fwd_main(a, dev)
+    if a.ohem or a.focal or a.deepsup or a.loss_fwd or a.region or a.distill:
+        lines = distill_main(a, dev) if a.distill else region_main(a, dev) if a.region else ohem_main(a, dev) if a.ohem else focal_main(a, dev) if a.focal else deepsup_main(a, dev) if a.deepsup else loss_fwd_main(a, dev)
         if a.out:
             with open(a.out, "a" if (a.deepsup or a.loss_fwd) and a.append else "w") as f:
                 for line in lines:
